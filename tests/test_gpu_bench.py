@@ -30,7 +30,7 @@ SMALL = ['--steps', '4', '--warmup', '1', '--min-timed-frames', '8', '--preheat-
 
 
 def test_bench_single_gpu_line(built):
-    out = run_bench(['--gpus', '1', '--cpu-seconds', '1'] + SMALL)
+    out = run_bench(['--gpus', '1', '--full', '--cpu-seconds', '1'] + SMALL)
     assert out['n_gpus'] == 1 and out['steps'] == 4 and out['unit'] == 'Msamples/s' and out['value'] > 1000
     assert out['config']['fuse'] == 256 and out['config']['fuse_short']['fuse'] == 64        # the reference's schedule is the default
     assert out['config']['timed_frames'] == 8
@@ -54,6 +54,23 @@ def test_bench_single_gpu_line(built):
     assert out['config']['stream_lanes']['lanes'] == 2
 
 
+def test_bench_plain_line_and_dumped_frame(built, tmp_path):
+    """Without --full the line holds the headline alone, the timed region is exactly --steps frames, and --dump-outputs
+    writes the last timed frame as float32."""
+    import numpy as np
+    out = run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--preheat-seconds', '0', '--dump-outputs', str(tmp_path)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert out['steps'] == 3 and out['config']['timed_frames'] == 3 and out['value'] > 1000 and out['ms_per_step'] > 0
+    assert abs(out['value'] - out['config']['samples_per_frame'] / (out['ms_per_step'] * 1e-3) / 1e6) < 0.01 * out['value']
+    for k in ('roofline', 'de_filter', 'kernel_ms_per_frame', 'cpu_baseline'):
+        assert k not in out, k
+    assert 'fuse_short' not in out['config']
+    frame = np.load(str(tmp_path / 'frame.npy'))
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4)
+    assert frame.min() >= 0 and frame.max() <= 255 and frame[..., 3].max() > 0
+
+
 def test_counter_files_are_quoted_only_for_the_library_they_were_measured_on(built, tmp_path):
     """roofline.traffic, k_iter.valu_issue_frac and de_filter.valu_frac come from counter files under profiles/ that carry the sha256
     of the library they were measured on (tools/pmc_traffic.sh, pmc_sq.sh, de_slot_budget.sh).  Another build of the library — here the
@@ -64,7 +81,7 @@ def test_counter_files_are_quoted_only_for_the_library_they_were_measured_on(bui
     shutil.copy(_lib.LIB_PATH, lib2)
     with open(lib2, 'ab') as f:
         f.write(b'\0')
-    out = run_bench(['--gpus', '1', '--cpu-seconds', '0'] + SMALL, env={'FLAME_HIP_LIB': lib2})
+    out = run_bench(['--gpus', '1', '--full', '--cpu-seconds', '0'] + SMALL, env={'FLAME_HIP_LIB': lib2})
     r = out['roofline']
     assert r['traffic'] is None and r['traffic_source'] is None and 'another build' in r['traffic_note']
     assert r['k_iter']['valu_issue_frac'] is None and 'another build' in r['k_iter']['bound']
@@ -74,7 +91,7 @@ def test_counter_files_are_quoted_only_for_the_library_they_were_measured_on(bui
 
 def test_bench_counter_notes_belong_to_the_config(built):
     """A cfg3 line must not carry cfg2's counters: its notes name cfg3 (and a cfg3 file) or say that nothing was measured."""
-    out = run_bench(['--gpus', '1', '--cpu-seconds', '0', '--config', 'cfg3', '--steps', '2', '--warmup', '1', '--min-timed-frames', '2',
+    out = run_bench(['--gpus', '1', '--full', '--cpu-seconds', '0', '--config', 'cfg3', '--steps', '2', '--warmup', '1', '--min-timed-frames', '2',
                      '--preheat-seconds', '0'])
     for note in (out['roofline']['k_iter']['bound'], out['de_filter']['bound']):
         assert 'cfg3' in note and 'cfg2' not in note

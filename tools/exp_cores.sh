@@ -5,7 +5,7 @@
 out=${1:-gpurun_out/exp_cores}; mkdir -p $out
 run() { # name, lib, env...
   name=$1; lib=$2; shift 2
-  env "$@" FLAME_HIP_LIB=$PWD/cuburn_amd/_lib/$lib python bench.py --steps 40 --warmup 5 --cpu-seconds 0 > $out/$name.json 2> $out/$name.err
+  env "$@" FLAME_HIP_LIB=$PWD/cuburn_amd/_lib/$lib python bench.py --full --steps 40 --warmup 5 --cpu-seconds 0 > $out/$name.json 2> $out/$name.err
   python - "$out/$name.json" "$name" <<'PY'
 import json, sys
 try:

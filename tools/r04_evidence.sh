@@ -2,6 +2,7 @@
 # Round 4: rocprofv3 evidence for one BASELINE config: kernel stats, TCC traffic, SQ counters of the iterate and
 # accumulate kernels, and the bench line.  Usage: tools/r04_evidence.sh cfg5 [sq]   -> gpurun_out/r04_<cfg>_*
 cfg=$1; sq=$2
+O=${O:-out}; mkdir -p $O          # where the bench line goes
 export BENCH_ARGS="--config $cfg"
 tools/prof_kernels.sh r04_$cfg --config $cfg > gpurun_out/r04_${cfg}_kernels.txt 2>&1
 cp gpurun_out/prof_r04_$cfg/bench_kernel_stats.csv gpurun_out/r04_${cfg}_kernel_stats.csv
@@ -23,5 +24,5 @@ out = {c: sorted(d.values())[len(d) // 2] for c, d in acc.items()}
 json.dump(out, open("gpurun_out/sq_r04_${cfg}_accum.json", "w"), indent=1, sort_keys=True)
 PY
 fi
-python3 bench.py --config $cfg --steps 6 --warmup 2 --cpu-seconds 0 --preheat-seconds 2 --min-timed-frames 24 > gpurun_out/r04_${cfg}_bench.json 2> gpurun_out/r04_${cfg}_bench.err
-tail -c 600 gpurun_out/r04_${cfg}_bench.json
+python3 bench.py --full --config $cfg --steps 6 --warmup 2 --cpu-seconds 0 --preheat-seconds 2 --min-timed-frames 24 > $O/r04_${cfg}_bench.json 2> $O/r04_${cfg}_bench.err
+tail -c 600 $O/r04_${cfg}_bench.json

@@ -2,7 +2,7 @@
 # Round 4: the measurement artefacts kept under profiles/ (run on the GPU box; everything lands in gpurun_out/r04f_*)
 export TMPDIR=/tmp
 O=gpurun_out
-python3 bench.py > $O/r04f_bench.json 2> $O/r04f_bench.err
+python3 bench.py --full > $O/r04f_bench.json 2> $O/r04f_bench.err
 tools/prof_kernels.sh r04f_cfg2 > $O/r04f_cfg2_kernels.txt 2>&1
 cp $O/prof_r04f_cfg2/bench_kernel_stats.csv $O/r04f_bench_kernel_stats.csv
 BENCH_ARGS="" tools/pmc_traffic.sh r04f_cfg2 > $O/r04f_cfg2_traffic.txt 2>&1

@@ -4,7 +4,7 @@
 #   cfg3 / cfg4 / cfg5: kernel stats, TCC traffic, SQ counters of iterate + accumulate, bench line; the DE slot budget (cfg2)
 export TMPDIR=/tmp
 O=gpurun_out
-python3 bench.py > $O/r05f_bench.json 2> $O/r05f_bench.err
+python3 bench.py --full > $O/r05f_bench.json 2> $O/r05f_bench.err
 tools/prof_kernels.sh r05f_cfg2 > $O/r05f_cfg2_kernels.txt 2>&1
 cp $O/prof_r05f_cfg2/bench_kernel_stats.csv $O/r05f_bench_kernel_stats.csv
 BENCH_ARGS="" tools/pmc_traffic.sh r05f_cfg2 > $O/r05f_cfg2_traffic.txt 2>&1

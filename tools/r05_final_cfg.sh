@@ -24,7 +24,7 @@ json.dump({c: sorted(d.values())[len(d) // 2] for c, d in acc.items()}, open("gp
 PY
 cp $O/sq_r05f_${cfg}_iter.json profiles/r05_${cfg}_sq_counters_k_iter_spec.json
 unset BENCH_ARGS
-python3 bench.py --config $cfg > $O/r05f_${cfg}_bench.json 2> $O/r05f_${cfg}_bench.err
+python3 bench.py --full --config $cfg > $O/r05f_${cfg}_bench.json 2> $O/r05f_${cfg}_bench.err
 mkdir -p $O/keep
 cp $O/r05f_* $O/keep/ 2>/dev/null
 cp $O/pmc_r05f_*_traffic.json $O/sq_r05f_*.json $O/keep/ 2>/dev/null

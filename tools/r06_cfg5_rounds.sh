@@ -6,5 +6,5 @@ python bench.py --config cfg5 --steps 2 --warmup 1 --cpu-seconds 0 --preheat-sec
 for r in ${ROUNDS:-16 14 12 10}; do
   export FLAME_BIN_ROUNDS=$r
   echo -n "== rounds $r  "
-  python bench.py --config cfg5 --cpu-seconds 0 --steps 12 --warmup 2 --min-timed-frames 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame'])"
+  python bench.py --full --config cfg5 --cpu-seconds 0 --steps 12 --warmup 2 --min-timed-frames 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame'])"
 done

@@ -44,12 +44,12 @@ for cfg in $what; do
     cp $O/r06_de_slot_budget.txt profiles/r06_de_slot_budget.txt; cp profiles/r06_de_slot_budget.txt $K/
     tools/prof_kernels.sh r06f_cfg2 > $K/r06_cfg2_kernels.txt 2>&1
     cp $O/prof_r06f_cfg2/bench_kernel_stats.csv $K/r06_bench_kernel_stats.csv
-    python3 bench.py > $K/r06_bench.json 2> $K/r06_bench.err
+    python3 bench.py --full > $K/r06_bench.json 2> $K/r06_bench.err
     ;;
   atomic)
     tools/prof_kernels.sh r06f_atomic --accum atomic --min-timed-frames 40 > $K/r06_atomic_kernels.txt 2>&1
     cp $O/prof_r06f_atomic/bench_kernel_stats.csv $K/r06_atomic_kernel_stats.csv
-    python3 bench.py --accum atomic --steps 10 --warmup 2 --min-timed-frames 40 --cpu-seconds 0 > $K/r06_atomic_bench.json 2> $K/r06_atomic_bench.err
+    python3 bench.py --full --accum atomic --steps 10 --warmup 2 --min-timed-frames 40 --cpu-seconds 0 > $K/r06_atomic_bench.json 2> $K/r06_atomic_bench.err
     ;;
   cfg3|cfg4|cfg5)
     export BENCH_ARGS="--config $cfg"
@@ -62,7 +62,7 @@ for cfg in $what; do
     unset BENCH_ARGS
     tools/prof_kernels.sh r06f_$cfg --config $cfg > $K/r06_${cfg}_kernels.txt 2>&1
     cp $O/prof_r06f_$cfg/bench_kernel_stats.csv $K/r06_${cfg}_kernel_stats.csv
-    python3 bench.py --config $cfg --cpu-seconds 0 > $K/r06_${cfg}_bench.json 2> $K/r06_${cfg}_bench.err
+    python3 bench.py --full --config $cfg --cpu-seconds 0 > $K/r06_${cfg}_bench.json 2> $K/r06_${cfg}_bench.err
     ;;
   esac
 done

@@ -7,6 +7,6 @@ for rep in 1 2; do
   for pad in ${PADS:-0 512 1024 1536 2048 3072 4096 6144 8192 12288}; do
     export FLAME_X_ITER_LDS_PAD=$pad
     echo -n "== pad $pad (rep $rep)  "
-    python bench.py --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame']['iter'])"
+    python bench.py --full --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame']['iter'])"
   done
 done

@@ -9,6 +9,6 @@ for rep in 1 2 3; do
     if [ $v = other ]; then export FLAME_HIP_LIB=$other; else unset FLAME_HIP_LIB; fi
     echo "== $v (rep $rep)"
     tools/prof_kernels.sh libab_${v}_$rep --preheat-seconds 1.0 "$@" 2>&1 | grep -E "k_iter|k_accum" | head -2
-    python bench.py --cpu-seconds 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
+    python bench.py --full --cpu-seconds 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
   done
 done

@@ -8,6 +8,6 @@ for case in "cfg3 536870912" "cfg3 1073741824" "cfg3 2147483648" "cfg2 536870912
   for n in 1536 1280 1024; do
     export FLAME_NSLOTS=$n FLAME_BENCH_SAMPLES=$2
     echo -n "== $1 samples $2 slots $n  "
-    python bench.py --config $1 --cpu-seconds 0 --min-timed-frames 60 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
+    python bench.py --full --config $1 --cpu-seconds 0 --min-timed-frames 60 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
   done
 done

@@ -7,5 +7,5 @@ python bench.py --steps 4 --warmup 1 --cpu-seconds 0 --preheat-seconds 2 > /dev/
 for p in 16 8 12 24 16; do
   export FLAME_BIN_PARTS=$p
   echo "== parts $p"; tools/prof_kernels.sh parts_$p --preheat-seconds 1.5 | grep -E "k_accum"
-  python bench.py --steps 8 --warmup 2 --cpu-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms_per_frame'])"
+  python bench.py --full --steps 8 --warmup 2 --cpu-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms_per_frame'])"
 done 2>&1 | tee gpurun_out/r06_ninth_parts.txt

@@ -7,6 +7,6 @@ for rep in 1 2; do
   for r in 16 12 10 8 6; do
     export FLAME_BIN_ROUNDS=$r
     echo "== rounds $r (rep $rep)"
-    python bench.py --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
+    python bench.py --full --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
   done
 done

@@ -7,6 +7,6 @@ for rep in 1 2; do
   for n in 1024 768 896 512; do
     export FLAME_NSLOTS=$n
     echo "== slots $n (rep $rep)"
-    python bench.py --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame'])"
+    python bench.py --full --cpu-seconds 0 $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_frame'])"
   done
 done

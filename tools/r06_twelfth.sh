@@ -2,7 +2,7 @@
 # Round 6: walker slots x rounds per batch on the frame loop (LDS per workgroup = 6 KB swap + 1 KB x rounds + 4.3 KB)
 mkdir -p gpurun_out
 python bench.py --steps 4 --warmup 1 --cpu-seconds 0 --preheat-seconds 2 > /dev/null 2>&1
-run() { python bench.py --steps 8 --warmup 2 --cpu-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1'.ljust(22), d['value'], d['ms_per_step'], d['kernel_ms_per_frame'], d['roofline']['frac'])"; }
+run() { python bench.py --full --steps 8 --warmup 2 --cpu-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1'.ljust(22), d['value'], d['ms_per_step'], d['kernel_ms_per_frame'], d['roofline']['frac'])"; }
 for rep in 1 2; do
   run default
   FLAME_NSLOTS=1280 FLAME_BIN_ROUNDS=12 run s1280r12
