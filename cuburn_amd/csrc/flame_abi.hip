@@ -42,6 +42,8 @@ struct Lane {
     u64 *d_atom = nullptr;
     uint32_t *d_hot = nullptr;
     void *d_outpix = nullptr;         // w*h*8 bytes
+    uint32_t *d_de_tmax = nullptr;    // FL_FILT_DE: largest 16h per 64 x 16 tile [nbins / 256 + 64]
+    float *d_de_sinv = nullptr;       // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
     size_t outpix_bytes = 0;
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
     // accumulate + flush of launch k run on `aux` while launch k+1 iterates on `stream` into the other set
@@ -186,12 +188,20 @@ void fl_calc_dim(uint32_t w, uint32_t h, fl_dim *o)
 
 static void flush_pending(fl_ctx *c);
 
+// the normalisers of the `de` filter depend on nothing but the quantised radius: computed once per process
+static const float *de_norms()
+{
+    static const std::vector<float> t = [] { std::vector<float> v(16 * FL_DE_MAX_RADIUS + 1); de_adaptive_norms(v.data()); return v; }();
+    return t.data();
+}
+
 static void free_fb(fl_ctx *c)
 {
     hipFree(L(c).d_front); hipFree(L(c).d_back); hipFree(L(c).d_side); hipFree(L(c).d_blur);
-    hipFree(L(c).d_atom); hipFree(L(c).d_hot); hipFree(L(c).d_outpix);
+    hipFree(L(c).d_atom); hipFree(L(c).d_hot); hipFree(L(c).d_outpix); hipFree(L(c).d_de_tmax); hipFree(L(c).d_de_sinv);
     L(c).d_front = L(c).d_back = L(c).d_side = nullptr; L(c).d_blur = nullptr; L(c).d_atom = nullptr;
-    L(c).d_hot = nullptr; L(c).d_outpix = nullptr; L(c).nbins = 0; L(c).outpix_bytes = 0;
+    L(c).d_hot = nullptr; L(c).d_outpix = nullptr; L(c).d_de_tmax = nullptr; L(c).d_de_sinv = nullptr;
+    L(c).nbins = 0; L(c).outpix_bytes = 0;
     L(c).pend_yuv = L(c).pend_finish = L(c).pend_log = false;      // whatever was deferred dies with the buffers
 }
 
@@ -207,7 +217,10 @@ static int ensure_fb(fl_ctx *c, const fl_dim &d)
     if ((e = hipMalloc(&L(c).d_front, 16 * nbins)) || (e = hipMalloc(&L(c).d_back, 16 * nbins)) ||
         (e = hipMalloc(&L(c).d_side, 16 * nbins)) || (e = hipMalloc(&L(c).d_blur, 4 * nbins)) ||
         (e = hipMalloc(&L(c).d_atom, 8 * nbins)) || (e = hipMalloc(&L(c).d_hot, 4 * (nbins / 16))) ||
-        (e = hipMalloc(&L(c).d_outpix, ob))) {
+        (e = hipMalloc(&L(c).d_outpix, ob)) ||
+        (e = hipMalloc(&L(c).d_de_tmax, 4 * (nbins / 256 + 64))) ||
+        (e = hipMalloc(&L(c).d_de_sinv, 4 * (16 * FL_DE_MAX_RADIUS + 1))) ||
+        (e = hipMemcpyAsync(L(c).d_de_sinv, de_norms(), 4 * (16 * FL_DE_MAX_RADIUS + 1), hipMemcpyHostToDevice, L(c).stream))) {
         free_fb(c);
         (void)hipGetLastError();
         return fail(e == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, "framebuffer allocation", __FILE__, __LINE__, e);
@@ -876,6 +889,16 @@ int fl_filter(fl_ctx *c, int id, uint32_t w, uint32_t h, const float *p, uint32_
         launch_logencode(st, d, L(c).d_back, L(c).d_front, p[0]);
         std::swap(L(c).d_front, L(c).d_back);
         break;
+    case FL_FILT_DE: {                   // not part of the deferred bilateral chain
+        flush_pending(c);
+        REQUIRE(np >= 3, "de needs R,Rmin,curve");
+        REQUIRE(!(p[0] > (float)FL_DE_MAX_RADIUS), "de: R above 96 px");
+        REQUIRE(p[2] > 0.0f, "de: curve must be > 0");
+        if (!(p[0] > 0.0f)) break;       // R <= 0: every bin stays where it is
+        // in place on d_front; d_back / d_blur hold the staged sources
+        launch_de_adaptive(st, d, L(c).d_front, L(c).d_back, L(c).d_blur, L(c).d_de_tmax, L(c).d_de_sinv,
+                           p[0], std::min(std::max(p[1], 0.0f), p[0]), p[2]);
+    } break;
     default:
         return fail(FL_E_UNSUPPORTED, "unknown filter id", __FILE__, __LINE__);
     }

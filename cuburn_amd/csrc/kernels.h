@@ -87,6 +87,13 @@ void launch_de_dir(hipStream_t st, fl_dim d, int pattern, float4 *Nout, const fl
 // applies `tail`'s tone filters as it stores; round 5 removed the separate normalise / finish kernels, the persistent and the
 // overlapped eight-direction launches of round 4 (de_chain.hip: git history, commit 58f1875) and round 1's blur + packed-math pair)
 
+// de_adaptive.hip: the `de` filter (FL_FILT_DE), in place on buf; stage_c / stage_a / tmax are scratch of nbins float4 /
+// nbins float / de_adaptive_tiles() words, sinv the 16 * FL_DE_MAX_RADIUS + 1 normalisers of de_adaptive_norms()
+void launch_de_adaptive(hipStream_t st, fl_dim d, float4 *buf, float4 *stage_c, float *stage_a, uint32_t *tmax,
+                        const float *sinv, float R, float Rmin, float curve);
+size_t de_adaptive_tiles(fl_dim d);
+void de_adaptive_norms(float *out);
+
 // output.hip
 void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng, uint32_t nrng, int fmt, void *dst);
 

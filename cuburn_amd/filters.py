@@ -59,6 +59,23 @@ class Bilateral(_Simple):
                 f32(params.density_pow(tc)), f32(params.gradient(tc))]
 
 
+@Filter.register('de')
+class DensityEstimation(_Simple):
+    """flam3's adaptive density estimator: a bin's kernel radius falls from R as its density grows."""
+    max_radius = 96                 # FL_DE_MAX_RADIUS: also the filter's reach (distributed.FILTER_REACH)
+
+    def scalars(self, gprof, params, dim, tc):
+        # radius in 1080p pixels, as Bilateral's spatial_std; minimum is a fraction of the radius (genome/convert.py)
+        R = params.radius(tc) * dim.w / 1920.
+        curve = params.curve(tc)
+        if not curve > 0:
+            raise ValueError('de: curve must be > 0 (got %g)' % curve)
+        if R > self.max_radius:
+            raise ValueError('de: radius %g px at width %d is above the %d px limit' % (R, dim.w, self.max_radius))
+        minimum = min(max(params.minimum(tc), 0.0), 1.0)
+        return [f32(R), f32(minimum * R), f32(curve)]
+
+
 @Filter.register('logscale')
 class Logscale(_Simple):
     def scalars(self, gprof, params, dim, tc):

@@ -196,8 +196,10 @@ enum {
     FL_FILT_SMEARCLIP = 4, /* smearclip chain  filters.py:142-163      width,gam_m_1,lin,lingam     */
     FL_FILT_HALOCLIP = 5,  /* haloclip chain   filters.py:113-130      gam_m_1                      */
     FL_FILT_PLAINCLIP = 6, /* plainclip        code/filters.py:332-350 gam_m_1,lin,lingam,brightness*/
-    FL_FILT_LOGENCODE = 7  /* logencode        code/filters.py:81-90   degamma                      */
+    FL_FILT_LOGENCODE = 7, /* logencode        code/filters.py:81-90   degamma                      */
+    FL_FILT_DE = 8         /* adaptive DE      DESIGN.md §4 (flam3)    R,Rmin,curve (R <= 96, curve > 0) */
 };
+#define FL_DE_MAX_RADIUS 96    /* FL_FILT_DE: the largest R in px, and so the filter's reach */
 int fl_filter(fl_ctx *ctx, int filter_id, uint32_t w, uint32_t h, const float *params, uint32_t nparams);
 
 /* cuburn/output.py:83-88,120-125,150-158,212-219,323-338 (convert + copy of every Output class):
