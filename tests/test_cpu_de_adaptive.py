@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from common import REPO
-from de_model import de_filter, kernel, radii16
+from de_model import (KERNEL_CUT, de_filter, de_gather_at, kernel, kernel_exponent, near_half_densities, radii16,
+                      radii16_float)
 from cuburn_amd import _lib, configs, distributed, filters, output, profile, render
 from cuburn_amd.genome import convert
 
@@ -134,6 +135,92 @@ def test_model_conserves_and_spreads():
     edge = np.zeros((16, 16, 4), np.float32)
     edge[0, 0] = (1, 1, 1, 1)
     assert 0.25 < de_filter(edge, 6.0, 0.0, 0.6)[..., 3].sum() < 0.5
+
+
+def sparse_accum(H, W, seed):
+    """Sparse bins for the two model forms: densities in (0, 1) (h = R), spreading bins of many radii, bins that stay
+    (w = 0, w < 0, or so dense that h < 1) beside spreading ones, and bins on every edge and corner."""
+    rs = np.random.RandomState(seed)
+    w = np.where(rs.uniform(size=(H, W)) < 0.08, rs.choice([0.3, 0.9, 1.0, 2.5, 7.0, 40.0, 1e3, 1e5], (H, W)), 0.0)
+    w *= rs.uniform(0.8, 1.2, (H, W))
+    edge = np.zeros((H, W), bool)
+    edge[0, ::7] = edge[-1, 3::7] = edge[::5, 0] = edge[2::5, -1] = True
+    edge[0, 0] = edge[0, -1] = edge[-1, 0] = edge[-1, -1] = True
+    w[edge] = rs.uniform(0.2, 6.0, edge.sum())
+    w[H // 2, W // 2 - 1:W // 2 + 2] = (0.0, 0.5, -2.0)             # stays (w = 0), spreads at h = R, stays (w < 0)
+    w[H // 3, W // 3:W // 3 + 2] = (5e4, 0.7)                        # h < 1 (unless Rmin says otherwise) beside h = R
+    buf = np.zeros((H, W, 4), np.float32)
+    buf[..., 3] = w
+    lit = (w != 0) | (rs.uniform(size=(H, W)) < 0.05)                 # some colour without density: it stays
+    buf[..., :3] = rs.uniform(1, 1e3, (H, W, 3)) * lit[..., None]
+    buf[H // 2, W // 2 - 1, :3] = (7.0, 8.0, 9.0)
+    return buf
+
+
+@pytest.mark.parametrize('vals,shape,seed', [((96.0, 0.0, 1.0), (40, 72), 1), ((11.0, 4.4, 0.6), (56, 80), 2),
+                                             ((23.0, 0.0, 0.4), (48, 64), 3)])
+def test_model_gather_form_equals_scatter_form(vals, shape, seed):
+    """de_gather_at (gather form written from the DESIGN.md §4.6 text, S summed directly over the disc) and de_filter
+    (scatter form through kernel()) agree to 1e-12 at every output pixel.  Together the parameter sets cover R = 96,
+    Rmin > 0, densities in (0, 1), spreading bins on every edge of the buffer and bins that stay beside spreading ones."""
+    buf = sparse_accum(*shape, seed)
+    w = buf[..., 3]
+    m = radii16(w, *vals)
+    spreads = m >= 16
+    assert ((w > 0) & (w < 1)).any()
+    assert spreads[0].any() and spreads[-1].any() and spreads[:, 0].any() and spreads[:, -1].any()
+    assert (~spreads & (np.roll(spreads, 1, 1) | np.roll(spreads, -1, 1))).any()
+    if vals[0] == 96:
+        assert (m == 1536).any() and ((m > 0) & (m < 16)).any()
+    if vals[1] > 0:
+        assert (m == np.floor(16 * vals[1] + 0.5)).sum() > 10            # clamped at Rmin
+    g = de_gather_at(buf, *vals, np.argwhere(np.ones(shape, bool))).reshape(buf.shape)
+    s = de_filter(buf, *vals)
+    err = np.abs(g - s) - (1e-12 * np.abs(s) + 1e-15 * np.abs(s).max())
+    assert not (err > 0).any(), (err.max(), np.unravel_index(np.argmax(err), err.shape))
+
+
+def test_kernel_cut_is_exact_at_every_radius():
+    """k_de_gather keeps a tap when its float32 exponent e = fma(a, dy^2, a dx^2), a = kA / m^2, is >= kCut
+    (de_model.kernel_exponent restates that arithmetic).  DESIGN.md §4.6 argues that this is exactly the integer disc
+    test 256 (dx^2 + dy^2) <= m^2, because 256 n - m^2 is never 1..6 and e's rounding is far below the cut's 1e-6 margin.
+    Checked for every m = 16 .. 1536 over the disc's bounding box and one ring beyond it (the gather also visits offsets
+    up to its tile's largest radius; further out e only falls, as every step is a monotone rounding); e depends on dx^2
+    and dy^2 alone, so the quadrant dx, dy >= 0 stands for the box.  The margin is needed: without it, points exactly on
+    the edge (256 n == m^2, so m a multiple of 16) are lost at some radii."""
+    assert not any((-m * m) % 256 in range(1, 7) for m in range(16, 1537))
+    cut0 = np.float32(-4.5 * 1.4426950408889634)            # the cut without its margin
+    evals = on_edge = 0
+    lost = []
+    for m in range(16, 1537):
+        I = m // 16 + 1
+        dy, dx = np.mgrid[0:I + 1, 0:I + 1]
+        n = dx * dx + dy * dy
+        e = kernel_exponent(m, dx * dx, dy * dy)
+        inside = 256 * n <= m * m
+        assert np.array_equal(e >= KERNEL_CUT, inside), (m, np.argwhere((e >= KERNEL_CUT) != inside)[:4])
+        edge = 256 * n == m * m
+        evals += n.size
+        on_edge += edge.sum()
+        if (edge & (e < cut0)).any():
+            lost.append(m)
+    assert evals > 4.9e6 and on_edge > 0
+    assert lost and all(m % 16 == 0 for m in lost) and 48 in lost and 80 in lost, lost
+
+
+@pytest.mark.parametrize('curve', [1.0, 0.6])
+def test_radius_rounding_needs_double(curve):
+    """near_half_densities: float32 densities whose 16 h lies within 1e-5 of a rounding half, on both sides and no
+    closer than 1e-9.  radii16 (h in double: the contract) rounds each to the nearer integer; a float32 pow and rounding
+    (radii16_float) picks the other m for about 30 % of them (most of those below the half), which
+    test_gpu_de_radii.test_de_rounds_h_in_double would catch."""
+    w, below = near_half_densities(96.0, curve)
+    assert below.sum() >= 150 and (~below).sum() >= 150
+    s = 16.0 * (96.0 * w.astype(np.float64) ** -curve)
+    m = radii16(w, 96.0, 0.0, curve)
+    assert np.array_equal(m, np.where(below, np.floor(s), np.ceil(s)))
+    flips = radii16_float(w, 96.0, 0.0, curve) != m
+    assert 0.25 < flips.mean() < 0.35 and flips[below].mean() > 0.5, (flips.mean(), flips[below].mean())
 
 
 def test_reach_and_band_path():

@@ -1503,7 +1503,8 @@ def test_deferred_filter_fusion_is_bit_identical(mgr):
     dim = mgr.fb.calc_dim(FW, FH)
     buf = synth_accum(dim)
     steps = {'yuv': [], 'bilateral': [6.0 * FW / 1920., 0.05, 1.5, 0.8, 4.0], 'logscale': [4.1875, 0.002],
-             'colorclip': [1.0, -1.0, 0.25, 0.01, 0.01 ** (0.25 - 1)], 'smearclip': [0.7, 0.25 - 1, 0.01, 0.01 ** (0.25 - 1)]}
+             'colorclip': [1.0, -1.0, 0.25, 0.01, 0.01 ** (0.25 - 1)], 'smearclip': [0.7, 0.25 - 1, 0.01, 0.01 ** (0.25 - 1)],
+             'de': [9.0, 0.9, 0.6]}
 
     def run(chain, peek):
         _lib.check(lib.fl_debug_clear(mgr.fb.ctx, dim.w, dim.h, 0))
@@ -1517,7 +1518,9 @@ def test_deferred_filter_fusion_is_bit_identical(mgr):
 
     for chain in (['yuv', 'bilateral', 'logscale', 'colorclip'], ['yuv', 'bilateral', 'logscale', 'smearclip'],
                   ['yuv', 'bilateral'], ['bilateral', 'colorclip'], ['yuv', 'logscale', 'colorclip'],
-                  ['yuv', 'bilateral', 'bilateral', 'logscale'], ['yuv', 'yuv'], ['bilateral', 'logscale', 'logscale', 'colorclip']):
+                  ['yuv', 'bilateral', 'bilateral', 'logscale'], ['yuv', 'yuv'], ['bilateral', 'logscale', 'logscale', 'colorclip'],
+                  ['yuv', 'de', 'logscale', 'colorclip'], ['yuv', 'bilateral', 'de', 'logscale', 'smearclip'], ['de', 'de'],
+                  ['yuv', 'de', 'bilateral', 'logscale']):
         a, b = run(chain, False), run(chain, True)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), chain
         assert np.isfinite(a).all()
