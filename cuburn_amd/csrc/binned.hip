@@ -35,10 +35,8 @@ __device__ __forceinline__ void spill_cell(u64 cur, uint32_t gi, float *__restri
 }
 
 // Sum of the packed values of the lanes in `grp`, spilled to the float accumulator by the group's first lane
-#ifndef HOT_GROUP_INLINE
-#define HOT_GROUP_INLINE __forceinline__      /* a real call in the record loop keeps everything that lives across it in the few callee-saved VGPRs: spills */
-#endif
-__device__ HOT_GROUP_INLINE void hot_group(u64 v, unsigned long long grp, uint32_t gi, float *__restrict__ out4)
+// (inlined: a real call in the record loop keeps everything that lives across it in the few callee-saved VGPRs: spills)
+__device__ __forceinline__ void hot_group(u64 v, unsigned long long grp, uint32_t gi, float *__restrict__ out4)
 {
 #pragma unroll
     for (int sh = 1; sh < 64; sh <<= 1) {
@@ -49,7 +47,7 @@ __device__ HOT_GROUP_INLINE void hot_group(u64 v, unsigned long long grp, uint32
 }
 
 // the same for k_accum_tiles_p3
-__device__ HOT_GROUP_INLINE void hot_group_sw(u64 v, unsigned long long grp, uint32_t gi, float *__restrict__ out4)
+__device__ __forceinline__ void hot_group_sw(u64 v, unsigned long long grp, uint32_t gi, float *__restrict__ out4)
 {
     // (xor 1 .. 16 as ds_swizzle with the pattern in the instruction: the lane addresses of six __shfl_xor are loop-invariant, the
     // compiler computes them in front of the record loop and keeps — or spills — five registers for a path that is almost never taken)
@@ -94,56 +92,10 @@ __device__ __forceinline__ uint32_t wave_incl_maxscan(uint32_t v) {             
     return v;
 }
 
-#ifndef ACC_ILP_WIDE
-#define ACC_ILP_WIDE 4     /* records per lane in flight, 256x64 tiles (one 16-wave workgroup per CU) */
-#endif
-#ifndef ACC_ILP
-#define ACC_ILP 3          /* records per lane and step, 128x64 tiles: two steps are in flight (ACC_PIPE), and four per step do not fit 64 VGPRs without spills */
-#endif
-#ifndef ACC_GATHER_AHEAD
-#define ACC_GATHER_AHEAD 4     /* palette entries requested this many records ahead of their add (4: all of a step's at once; fewer: fewer VGPRs) */
-#endif
-#ifndef ACC_DIR_AHEAD
-#define ACC_DIR_AHEAD 1        /* a group's directory words are requested one group ahead (the first group's before the tile is zeroed) */
-#endif
-#ifndef ACC_BYTE_MARKS
-#define ACC_BYTE_MARKS 1       /* run lookup: one LDS exchange of byte marks per step + ds_bpermute, instead of one exchange of word marks per 64 records */
-#endif
-#ifndef ACC_LOAD_MOD
-#define ACC_LOAD_MOD ""        /* cache policy of the record loads (" nt", " sc1", ...): experiment, see profiles/r03_accum_cache_policy.txt */
-#endif
-#ifndef ACC_PIPE
-#define ACC_PIPE 1             /* the next step's record loads are in flight while the current step's records are added */
-#endif
-#ifndef ACC_ADD_ILP
-#define ACC_ADD_ILP 8          /* returning global atomics in flight per thread when the tile is added to the accumulator */
-#endif
-#ifndef ACC_ROWS_MAX
-#define ACC_ROWS_MAX 5         /* palette rows staged per narrow workgroup (2 KB each) */
-#endif
-#ifndef ACC_THREADS
-#define ACC_THREADS 1024        /* threads per accumulate workgroup (narrow tiles) */
-#endif
-
-// -DACC_X_TIMES: every workgroup stores its start and end (100 MHz ticks) in acc_wg_times[blockIdx.x]; fl_debug_acc_times
-// copies them out (tools/acc_times.py: which tiles' workgroups run longest, and when)
-#ifdef ACC_X_TIMES
-#define ACC_X_MAXWG 65536
-__device__ unsigned long long acc_wg_times[ACC_X_MAXWG][4];      // start, tile zeroed + first palette rows staged, records done, tile added
-// wave 0 of every workgroup also sums the shader clocks (s_memtime) it spends requesting a step's records (run lookup:
-// the mark exchange), waiting for a step's records, and adding them; [3] = the whole record phase, [4] = steps
-__device__ unsigned long long acc_wg_steps[ACC_X_MAXWG][5];
-extern "C" __attribute__((visibility("default"))) int fl_debug_acc_steps(unsigned long long *out, unsigned n)
-{
-    if (n > ACC_X_MAXWG) n = ACC_X_MAXWG;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(acc_wg_steps), sizeof(unsigned long long) * 5 * n) == hipSuccess ? 0 : -1;
-}
-extern "C" __attribute__((visibility("default"))) int fl_debug_acc_times(unsigned long long *out, unsigned n)
-{
-    if (n > ACC_X_MAXWG) n = ACC_X_MAXWG;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(acc_wg_times), sizeof(unsigned long long) * 4 * n) == hipSuccess ? 0 : -1;
-}
-#endif
+constexpr int ACC_GATHER_AHEAD = 4;     // palette entries requested this many records ahead of their add (4: all of a step's at once; fewer: fewer VGPRs)
+constexpr int ACC_ADD_ILP = 8;          // returning global atomics in flight per thread when the tile is added to the accumulator
+constexpr int ACC_ROWS_MAX = 5;         // palette rows staged per narrow workgroup (2 KB each)
+constexpr int ACC_THREADS = 1024;       // threads per accumulate workgroup (narrow tiles)
 
 // The end of every accumulate workgroup: its LDS tile is added to the global packed accumulator, one row segment of 64 cells
 // per wave instruction (coalesced atomics), draining cells that reach 512 hits.
@@ -212,7 +164,9 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t TW = 1u << TWL, CELLS = TW * FL_TILE_H;
-    constexpr int ILP = TWL == 7u ? ACC_ILP : ACC_ILP_WIDE;
+    // records per lane and step.  128x64 tiles: 3 (two steps are in flight, and four per step do not fit 64 VGPRs without spills);
+    // 256x64 tiles (one 16-wave workgroup per CU): 4
+    constexpr int ILP = TWL == 7u ? 3 : 4;
     static_assert(FL_PAL_W == 256, "the palette column is the record's low byte, the row the mark's");
     // LDS: palette rows first (their gather then needs no base added), the waves' marks, the tile
     u64 *pal = reinterpret_cast<u64 *>(smem);                                                   // [rows_cap][256] palette rows in use
@@ -230,10 +184,6 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
         if (bin >= nbins) return;
     }
     const uint32_t tx = bin % tiles_x, ty = bin / tiles_x;
-#ifdef ACC_X_TIMES
-    if (tid == 0 && blockIdx.x < ACC_X_MAXWG) acc_wg_times[blockIdx.x][0] = __builtin_amdgcn_s_memrealtime();
-#endif
-
 
     // This workgroup's contiguous range of batches.  Batch id = slot * per_slot + batch_in_slot
     // (iter.hip), so the range covers a narrow range of SLOTS, and with them of palette rows (row of
@@ -252,10 +202,6 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
     const uint32_t chunk_slots = (rows_cap - 1u) * spr;
 
     if (b_lo >= b_hi) return;                                      // no batches for this part (tiny launches): nothing to add
-#ifdef ACC_X_TIMES
-    uint32_t x_fetch = 0, x_wait = 0, x_proc = 0, x_other = 0, x_steps = 0;
-    const uint32_t x_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
     for (uint32_t cb = b_lo; cb < b_hi;) {
     const uint32_t cs_lo = cb / per_slot;
     const uint32_t ce = min(b_hi, (cs_lo + chunk_slots) * per_slot);
@@ -270,9 +216,7 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
     }
     // (so are the directory words of the wave's first group; every group then requests the next group's words
     // before it walks its own records)
-#if ACC_DIR_AHEAD
     uint32_t e_next = cb + wv * 64 + lane < ce ? drow[cb + wv * 64 + lane] : 0u;
-#endif
     if (cb == b_lo) {
         for (uint32_t i = tid; i < CELLS; i += blockDim.x) tile[i] = 0ull;
         mk[lane] = 0u;
@@ -284,9 +228,6 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
         if (i < nrows * FL_PAL_W) pal[i] = stagev[q];
     }
     __syncthreads();
-#ifdef ACC_X_TIMES
-    if (tid == 0 && blockIdx.x < ACC_X_MAXWG && cb == b_lo) acc_wg_times[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-#endif
     for (uint32_t g0v = cb + wv * 64; g0v < ce; g0v += nwaves * 64) {
         const uint32_t g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g0v);      // wave-uniform
         // slot of the group's first batch and the remainder, once per group (scalar); run r < 64 of
@@ -294,12 +235,8 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
         const uint32_t s0 = g0 / per_slot, rem0 = g0 - s0 * per_slot;
         // 64 directory entries per wave; their runs form one virtual array of `total` records
         const uint32_t batch = g0 + lane;
-#if ACC_DIR_AHEAD
         const uint32_t e = e_next;
         e_next = batch + nwaves * 64 < ce ? drow[batch + nwaves * 64] : 0u;
-#else
-        const uint32_t e = batch < ce ? drow[batch] : 0u;
-#endif
         const uint32_t c = e & 0xffffu, first = e >> 16;
         const uint32_t incl = wave_incl_scan_b(c, lane);
         const uint32_t excl = incl - c;
@@ -307,7 +244,7 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
         // Which run does record v of the virtual array belong to?  Every non-empty run drops a mark at its first
         // position; a max-scan over the positions (DPP, pure VALU) then carries the latest mark to every position.
         // This replaces a 6-step shuffle binary search + two more shuffles per record (8 trips through the LDS pipe)
-        // by one predicated LDS write, one read and one clear per 64 records.  The mark holds everything a record
+        // by one predicated LDS write, one read and one clear per step.  The mark holds everything a record
         // needs from its run, computed ONCE per run by the run's directory lane:
         //   bits 8..: 1 + (lane * batch_records + first - excl) = 1 + (the record's index in the log, counted from
         //             the group's first batch) - (its position v in the virtual array)
@@ -322,12 +259,12 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
         uint32_t carry = 0;
         // One step = 64 * ILP records: `fetch` finds every record's run and requests it, `process` adds the records to
         // the tile.  The record loads are issued from inline asm so that the NEXT step's requests can be in flight while
-        // this step's records go through the palette and the tile (ACC_PIPE): the compiler would wait for them at once.
+        // this step's records go through the palette and the tile: the compiler would wait for them at once.
         // A step's results are its ILP records and one word with the ILP palette rows (one byte each).
         static_assert(ILP >= 2 && ILP <= 4, "up to four rows to a word");
         auto fetch = [&](const uint32_t v0, uint32_t (&rec)[ILP], uint32_t &rows) __attribute__((always_inline)) {
-#if ACC_BYTE_MARKS
-            // ONE exchange for the whole step: the runs that start inside it drop their lane number (+1) as a byte, every
+            // ONE exchange for the whole step (instead of one exchange of word marks per 64 records): the runs that start
+            // inside it drop their lane number (+1) as a byte, every
             // lane reads its ILP positions at once, the ILP max-scans are independent instruction chains (the wait states
             // of one are filled by the others), and the marks themselves come from the runs' lanes by ds_bpermute —
             // two waits on the LDS pipe per step instead of ILP.  (carry: the run number + 1 here, the mark below)
@@ -348,53 +285,24 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
                 carry = (uint32_t)__builtin_amdgcn_readlane((int)mm[k], 63);
                 mm[k] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((mm[k] - 1u) << 2), (int)mark_l);
             }
-#endif
 #pragma unroll
             for (int k = 0; k < ILP; ++k) {
                 const uint32_t lo = v0 + k * 64, v = lo + lane;
-#if ACC_BYTE_MARKS
                 const uint32_t m = mm[k];
-#else
-                if (c != 0u && excl - lo < 64u) mk[excl - lo] = mark_l;
-                wave_sync();                 // lanes exchange data through LDS: without it the compiler
-                uint32_t m = mk[lane];       // forwards this lane's own earlier "= 0" into the load
-                wave_sync();
-                mk[lane] = 0u;
-                m = wave_incl_maxscan(m);
-                m = max(m, carry);
-                carry = (uint32_t)__builtin_amdgcn_readlane((int)m, 63);
-#endif
                 // byte k of `rows` = the mark's low byte
                 rows = __builtin_amdgcn_perm(m, rows, k == 0 ? 0x03020104u : k == 1 ? 0x03020400u : k == 2 ? 0x03040100u : 0x04020100u);
-#ifdef ACC_X_NOLOG       /* timing experiments only (tools/exp_accum_parts.sh): synthesised records */
-                rec[k] = ((m * 2654435761u + v * 40503u) & ((1u << (TWL + FL_TILE_H_LOG2 + 8u)) - 1u));
-#elif 0
-                // 3-byte records: the two aligned words around the record's byte address in ONE 8-byte load (needs 4-byte
-                // alignment only), the record cut out with v_alignbyte — an unaligned 4-byte load measured +31 %
-                rec[k] = 0u;
-                if (v < total) {
-                    const size_t ba = ((size_t)g0 * batch_records + (v + (m >> 8) - 1u)) * 3u;
-                    struct __attribute__((packed, aligned(4))) W2 { uint32_t lo, hi; };
-                    const W2 w = *reinterpret_cast<const W2 *>(reinterpret_cast<const unsigned char *>(log) + (ba & ~(size_t)3));
-                    rec[k] = __builtin_amdgcn_alignbyte(w.hi, w.lo, (uint32_t)ba & 3u) & 0xffffffu;
-                }
-#else
                 // scalar base + 32-bit byte offset (at most 4 * 65 * batch_records); positions past the end of the
                 // virtual array read the group's first record (and are not used)
                 const uint32_t voff = v < total ? ((m >> 8) + v) << 2 : 4u;
-                asm volatile("global_load_dword %0, %1, %2" ACC_LOAD_MOD : "=v"(rec[k]) : "v"(voff), "s"(gbase) : "memory");
-#endif
+                // (default cache policy: " nt", " sc1", ... measured no better, profiles/r03_accum_cache_policy.txt)
+                asm volatile("global_load_dword %0, %1, %2" : "=v"(rec[k]) : "v"(voff), "s"(gbase) : "memory");
             }
         };
         auto process = [&](const uint32_t v0, uint32_t (&rec)[ILP], const uint32_t rows) __attribute__((always_inline)) {
             bool live[ILP];
             u64 val[ILP];
             auto gather = [&](const int k) __attribute__((always_inline)) {
-#ifdef ACC_X_NOPAL
-                val[k] = (1ull << 54) | (rows & 0xffu) | (rec[k] & 0xffu);
-#else
                 val[k] = pal[__builtin_amdgcn_perm(rows, rec[k], 0x0c0c0000u | ((4u + k) << 8))];      // (row << 8) | colour byte: FL_PAL_W == 256
-#endif
             };
 #pragma unroll
             for (int k = 0; k < ILP; ++k) {
@@ -431,11 +339,7 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
                 const uint32_t off = rec[k] >> 8;                                // (ly << TWL) | lx
                 if (k + ACC_GATHER_AHEAD < ILP) gather(k + ACC_GATHER_AHEAD);           // palette entries are requested ACC_GATHER_AHEAD records ahead of their add
                 if (!live[k]) continue;
-#ifdef ACC_X_NOATOM
-                const u64 old = tile[off ^ 1u]; if (val[k] == 0x1234567ull) tile[off] = old;
-#else
                 const u64 old = __hip_atomic_fetch_add(tile + off, val[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
                 if ((uint32_t)(old >> 32) >= (128u << 23)) {                     // 256 hits: drained early, three quarters of the count's range left for adds in flight
                     const u64 cur = __hip_atomic_exchange(tile + off, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if ((uint32_t)(cur >> 32) != 0u) {
@@ -451,44 +355,23 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
                             else asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(r[0]), "+v"(r[1]) :: "memory"); } while (0)
 #define ACC_WAIT_NEWER(r) do { if constexpr (ILP == 4) ACC_WAIT(4, r); else if constexpr (ILP == 3) ACC_WAIT(3, r); else ACC_WAIT(2, r); } while (0)       /* all but the ILP newest loads */
         constexpr uint32_t STEP = 64 * ILP;
-#if ACC_PIPE && !defined(ACC_X_NOLOG)
         // Two sets of results alternate (A, B): while one set's records are added, the other's are on their way.  Each
         // set has ONE place where it is requested, and B's processing trails into the next iteration: a second place
         // (a prologue, say) would make the compiler merge two definitions, i.e. copy registers whose loads are still
         // in flight (tools/check_asm_atomics.py looks for exactly that in the assembly).
         uint32_t recA[ILP] = {}, recB[ILP] = {}, rowsA = 0u, rowsB = 0u;
-#ifdef ACC_X_TIMES
-#define ACC_T(sum) do { const uint32_t t_ = (uint32_t)__builtin_amdgcn_s_memtime(); sum += t_ - x_t; x_t = t_; } while (0)
-        uint32_t x_t = (uint32_t)__builtin_amdgcn_s_memtime();
-#else
-#define ACC_T(sum) do { } while (0)
-#endif
         for (uint32_t v0 = 0; v0 < total; v0 += 2 * STEP) {
-            ACC_T(x_other); fetch(v0, recA, rowsA); ACC_T(x_fetch);
+            fetch(v0, recA, rowsA);
             // (the marker tells tools/check_asm_atomics.py that the branch around this block is the first step's: nothing of B in flight)
-            if (v0 != 0u) { asm volatile("; acc-guarded-block"); ACC_WAIT_NEWER(recB); ACC_T(x_wait); process(v0 - STEP, recB, rowsB); ACC_T(x_proc); }       // B is older than A: A stays in flight
-            if (v0 + STEP < total) { fetch(v0 + STEP, recB, rowsB); ACC_T(x_fetch); ACC_WAIT_NEWER(recA); } else ACC_WAIT(0, recA);
-            ACC_T(x_wait); process(v0, recA, rowsA); ACC_T(x_proc);
-#ifdef ACC_X_TIMES
-            x_steps += v0 + STEP < total ? 2 : 1;
-#endif
+            if (v0 != 0u) { asm volatile("; acc-guarded-block"); ACC_WAIT_NEWER(recB); process(v0 - STEP, recB, rowsB); }       // B is older than A: A stays in flight
+            if (v0 + STEP < total) { fetch(v0 + STEP, recB, rowsB); ACC_WAIT_NEWER(recA); } else ACC_WAIT(0, recA);
+            process(v0, recA, rowsA);
         }
         if (((total + STEP - 1u) / STEP & 1u) == 0u && total != 0u) {                     // an even number of steps: the last B
             ACC_WAIT(0, recB);
             process((total - 1u) / STEP * STEP, recB, rowsB);
         }
-#else
-        for (uint32_t v0 = 0; v0 < total; v0 += STEP) {
-            uint32_t rec[ILP], rows = 0u;
-            fetch(v0, rec, rows);
-#if !defined(ACC_X_NOLOG)
-            ACC_WAIT(0, rec);
-#endif
-            process(v0, rec, rows);
-        }
-#endif
 #undef ACC_WAIT
-#undef ACC_T
 #undef ACC_WAIT_NEWER
     }
     cb = ce;
@@ -497,15 +380,6 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
 
     // add the tile to the global packed accumulator: one row segment of 64 cells per wave
     // instruction (coalesced atomics), draining cells that reach 512 hits
-#ifdef ACC_X_TIMES
-    if (tid == 0 && blockIdx.x < ACC_X_MAXWG) {
-        unsigned long long *o = acc_wg_steps[blockIdx.x];
-        o[0] = x_fetch; o[1] = x_wait; o[2] = x_proc; o[3] = (uint32_t)__builtin_amdgcn_s_memtime() - x_t0; o[4] = x_steps;
-    }
-    __syncthreads();
-    if (tid == 0 && blockIdx.x < ACC_X_MAXWG) acc_wg_times[blockIdx.x][2] = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifndef ACC_NO_DRAIN     /* timing experiment only: tools/exp_drain.sh */
     // ACC_ADD_ILP returning atomics per thread are in flight before the first result is looked at (one at a time,
     // the loop was eight serial round trips to L2: 6.5 us of a 43 us workgroup)
     for (uint32_t i0 = tid; i0 < CELLS; i0 += blockDim.x * ACC_ADD_ILP) {
@@ -549,11 +423,6 @@ k_accum_tiles(const uint32_t *__restrict__ log, const uint32_t *__restrict__ dir
             }
         }
     }
-#endif
-#ifdef ACC_X_TIMES
-    __syncthreads();
-    if (tid == 0 && blockIdx.x < ACC_X_MAXWG) acc_wg_times[blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // ---- the accumulate of the packed log (FL_LOG_PACK3: 128x64 tiles, three 21-bit records per 64-bit word) ----------------------
@@ -684,7 +553,7 @@ k_accum_tiles_p3(const uint32_t *__restrict__ log, const uint32_t *__restrict__ 
                 voff = inside ? (m1 + v) << 3 : lane8;
             }
             // the ONE place this set is requested (the steps behind the last one still issue a load, so that every wait below is "all but the two newest")
-            asm volatile("global_load_dwordx2 %0, %1, %2" ACC_LOAD_MOD : "=v"(w) : "v"(voff), "s"(gbase) : "memory");
+            asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(w) : "v"(voff), "s"(gbase) : "memory");
         };
         auto process = [&](const u32x2_t w, const uint32_t meta) __attribute__((always_inline)) {
             const uint32_t wl = w.x, wh = w.y;

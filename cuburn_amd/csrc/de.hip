@@ -25,7 +25,7 @@
 //     instruction mix runs at 1.46 ns per wave-instruction per SIMD in isolation (tools/vgpr_bank_bench.hip) and the kernels reach ~80 %
 //     of that; LDS conflicts, ILP, packed FMAs and workgroups per CU measured nothing, three instructions fewer per tap -6 %
 //     (profiles/r04_de_instruction_experiments.txt, DESIGN.md 4.3 "Round 4").
-//   * (round 3's reading, tools/valu_bench.hip wall-clock + tools/de_phases.py): a workgroup's life is a staging
+//   * (round 3's reading, tools/valu_bench.hip wall-clock + tools/de_phases.py (removed; last in eadb359)): a workgroup's life is a staging
 //     phase that mostly waits (global loads, barriers: 2.6-4.6 us) and a tap phase that computes (the taps of all
 //     resident workgroups together run the vector ALU at ~80 % of its measured peak of one wave instruction per
 //     1.21 ns per SIMD); a kernel then pays ~8-10 us of ramp-up and tail on top (every workgroup stages at the start,
@@ -43,7 +43,7 @@
 //
 // Scalar (non-packed) math: on gfx950 v_pk_fma_f32 issues at ~1.6x the cost of v_fma_f32
 // (tools/valu_bench.hip), which does not pay for the 16-apart pixel pairing and ds_read2_b32
-// traffic the packed form needs; at <= 64 VGPRs a CU holds 32 waves (in workgroups of 256 threads, see DE_TW_).
+// traffic the packed form needs; at <= 64 VGPRs a CU holds 32 waves (in workgroups of 256 threads, see DeGeo::TW).
 #include "flame_device.h"
 #include "kernels.h"
 #include "tone_device.h"
@@ -87,57 +87,11 @@ __host__ __device__ constexpr bool de_hoisted(int P) { return P < 4; }      // i
 // (global loads, four barriers) and a tap phase that computes, and a CU holds 32 waves whatever their grouping:
 // smaller workgroups put more independent phases on a CU (512 threads: four per CU; 256: eight), and the
 // kernels are 10-18 % faster (profiles/r03_de_tile_shapes.txt).  Taller tiles (less halo) are slower.
-#ifndef DE_TW_
-#define DE_TW_ 8       /* directions 4..7 (half slopes): 32 rows x 8 columns, 256 threads (round 3: 32 x 16, 512 threads) */
-#endif
-#ifndef DE_TH_
-#define DE_TH_ 32
-#endif
-#ifndef DE_TWE_
-#define DE_TWE_ DE_TW_ /* directions 4 and 6 (two pixels per row: even shear, consecutive rows per wave) */
-#endif
-#ifndef DE_TWH_
-#define DE_TWH_ 8      /* directions 1..3 (integer steps, no column halo): 32 x 8, 256 threads */
-#endif
-#ifndef DE_THH_
-#define DE_THH_ 32
-#endif
-#ifndef DE_TW0_
-#define DE_TW0_ 64     /* the horizontal direction: DE_TH0_ x DE_TW0_ tiles (round 2: 8 x 128, round 3: 8 x 64) */
-#endif
-#ifndef DE_TH0_
-#define DE_TH0_ 4
-#endif
+// Round 3 had 32 x 16 (512 threads) for the half-slope directions and 8 x 64 for the horizontal one.
 // Round 4: every direction in 256-thread workgroups, eight to a CU.  The DE alone is 3 % faster than with round 3's mix of
 // 256 and 512 threads, the two-lane frame loop 4.7 % (1.458 -> 1.390 ms at cfg2: smaller workgroups and LDS blocks find room
-// beside the other lane's kernels; profiles/r04_de_shapes_frame.txt).
-#ifndef DE_MINW
-#define DE_MINW 8      /* waves per SIMD the kernels are compiled for (8: 64 registers) */
-#endif
-#ifndef DE_PRIO_STAGE
-#define DE_PRIO_STAGE 3
-#endif
-#ifndef DE_FAST_PREP
-#define DE_FAST_PREP 1
-#endif
-#ifndef DE_X_NOBORDER_EVAL
-#define DE_X_NOBORDER_EVAL 0  /* timing build (wrong results at the image edges): no direct evaluation of the blurs at clamped positions */
-#endif
-#ifndef DE_SKIP_OUTSIDE
-#define DE_SKIP_OUTSIDE 1
-#endif
-#ifndef DE_BOTTOM_FIRST
-#define DE_BOTTOM_FIRST 1
-#endif
-#ifndef DE_RUN
-#define DE_RUN 8u             /* tile order 2: tiles per run (a run stays on one XCD) */
-#endif
-#ifndef DE_INTERIOR_LOADS
-#define DE_INTERIOR_LOADS 1   /* tiles that touch no image edge load their staged region without clamps, one address per thread */
-#endif
-#ifndef DE_LANE_PAIRS
-#define DE_LANE_PAIRS 1       /* 8-pixel rows of the half-slope directions: two rows 8 slots apart per hardware lane group */
-#endif
+// beside the other lane's kernels; profiles/r04_de_shapes_frame.txt).  The shapes themselves: DeGeo::TW, TH.
+constexpr uint32_t DE_RUN = 8u;      // tile order 2: tiles per run (a run stays on one XCD)
 struct DeReach { int hu, hv; };
 // Largest row / column displacement (sheared coordinates) of any staged value a tile pixel needs:
 // tap r, then the second blur's tap 2i there, then the first blur's tap j there (each offset is
@@ -165,8 +119,10 @@ __host__ __device__ constexpr DeReach de_reach(int P, bool blur)
 template <int P> struct DeGeo {
     static constexpr int K = de_k(P);
     // output tile
-    static constexpr int TW = P == 0 ? DE_TW0_ : (de_hoisted(P) ? DE_TWH_ : (P == 4 || P == 6) ? DE_TWE_ : DE_TW_);
-    static constexpr int TH = P == 0 ? DE_TH0_ : (de_hoisted(P) ? DE_THH_ : DE_TH_);
+    // output tile: 4 rows x 64 columns for the horizontal direction, 32 rows x 8 columns for every other one (directions 1..3: integer
+    // steps, no column halo; 4 and 6: two pixels per row, even shear, consecutive rows per wave; 5 and 7: the other half slopes)
+    static constexpr int TW = P == 0 ? 64 : 8;
+    static constexpr int TH = P == 0 ? 4 : 32;
     static constexpr int NT = TW * TH;                  // threads of a workgroup: one output pixel each
     static_assert(NT % 64 == 0 && NT <= 1024 && (P == 0 ? TW % 64 == 0 : 64 % TW == 0 && TH % (128 / TW) == 0), "whole waves, rows of equal parity per wave");
     static constexpr bool HOIST = de_hoisted(P);
@@ -196,14 +152,14 @@ template <int P> struct DeGeo {
     // on a stride of 12 (plane A of directions 4 / 6: 8 + 2 * 2 columns) or of 10 with the equal-parity rows of directions 5 / 7 — plane B
     // of directions 4 / 6 has 10 columns and rows two apart, hence two columns of padding (round 5: its reads took 12 LDS cycles, not 4).
     static constexpr int BROWS = TH + 2 * HBU, BCOLS = TW + 2 * HBV;
-    static constexpr int BPAD = (!de_hoisted(P) && (K & 1) == 0 && TW == 8 && DE_LANE_PAIRS) ? 12 - BCOLS : 0;
+    static constexpr int BPAD = (!de_hoisted(P) && (K & 1) == 0 && TW == 8) ? 12 - BCOLS : 0;
     static constexpr int BSTR = BCOLS + BPAD, NPXB = BROWS * BSTR;
     static_assert(BPAD >= 0 && (BPAD == 0 || (2 * BSTR) % 16 == 8), "rows two apart must lie 8 float4 slots apart mod 16");
     static constexpr int RSB = (K & 1) ? (NT / BCOLS) & ~1 : NT / BCOLS, NACTB = ROWWISE ? RSB * BCOLS : NT;
     static constexpr int NITB = ROWWISE ? (BROWS + RSB - 1) / RSB : (NPXB + NT - 1) / NT;
     // LDS: A float4[NPXA] | B float4[NPXB] | (integer-step directions) the fast path's density plane float[NPX];
     // the nested preparation's two dense float planes live in B's space
-    static constexpr int MINW = DE_MINW;
+    static constexpr int MINW = 8;      // waves per SIMD the kernels are compiled for (8: 64 registers)
     static constexpr size_t LDS = (size_t)(NPXA + NPXB) * 16 + (de_hoisted(P) ? (size_t)NPX * 4 : 0) + 64;
     static constexpr int SPAN = de_shear(P, TH - 1) < 0 ? -de_shear(P, TH - 1) : de_shear(P, TH - 1);
     // Frame tables (tiles that touch an image edge, see "frame tables" in the kernel): every staged position outside the image clamps
@@ -290,7 +246,7 @@ __device__ __forceinline__ void de_out_px(int wv, int lane, int &ou, int &ov)
 {
     using G = DeGeo<P>;
     if (P == 0) { constexpr int WPR = G::TW / 64; ou = wv / WPR; ov = (wv % WPR) * 64 + lane; }
-    else if (G::TW == 8 && !G::HOIST && DE_LANE_PAIRS) {
+    else if (G::TW == 8 && !G::HOIST) {
         // 8-pixel rows, eight to a wave (the half-slope directions).  A hardware group of 16 lanes (quads {0, 3, 5, 6} or {1, 2, 4, 7}
         // of each half of the wave) takes TWO rows, two apart among the wave's eight: on the planes' strides (DeGeo::BSTR) their
         // float4 slots are 8 apart mod 16 and every read of the tap loop is served in 4 LDS cycles (tools/de_geometry_model.py;
@@ -327,11 +283,7 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 //   z, w = cs*|n_q|^2 + Kp,          gspeed / (avg(q) + 1e-6)     (half-slope directions: the gradient term stays in the loop)
 struct DeTap { f4v a, b; };
 
-#ifdef DE_X_NOLDS      /* timing build: the tap loop without its LDS reads (results are garbage) */
-#define DE_RD128(dst, addr, boff) asm volatile("; no read %1 %2" : "=v"(dst) : "v"(addr), "n"(boff) : "memory")
-#else
 #define DE_RD128(dst, addr, boff) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(boff) : "memory")
-#endif
 
 template <int P> __host__ __device__ constexpr int de_tap_reads(int r)       // LDS reads issued for tap r
 {
@@ -482,12 +434,9 @@ __device__ __forceinline__ void de_tap_loop(const float4 *__restrict__ sA, const
     res = make_float4(oxy.x * rn, oxy.y * rn, ozw.x * rn, wn);
 }
 
-#ifndef DE_SLOW_INLINE
-#define DE_SLOW_INLINE __forceinline__
-#endif
 // The rare form
 template <int P, int PAR>
-__device__ DE_SLOW_INLINE void de_tap_loop_slow(const float4 *__restrict__ sA, const float4 *__restrict__ sB, int wv,
+__device__ __forceinline__ void de_tap_loop_slow(const float4 *__restrict__ sA, const float4 *__restrict__ sB, int wv,
                                               float cs2, const DeSpatial &spk, float4 &res)
 {
     de_tap_loop<P, PAR, true>(sA, sB, wv, cs2, spk, res);
@@ -513,25 +462,6 @@ __device__ __forceinline__ float4 de_in_px(float4 p)
     const float rw = p.w > 0.0f ? frcp(p.w) : 0.0f;
     return make_float4(p.x * rw, p.y * rw, p.z * rw, p.w);
 }
-
-// -DDE_X_PHASES: every workgroup adds the 100 MHz ticks it spent in each phase to de_phase_ticks[direction][phase]
-// (0 = until the loads are in LDS, 1 = first blur, 2 = tap terms, 3 = plane B written, 4 = taps + store, 5 = workgroups);
-// fl_debug_de_phases reads and clears them (tools/de_phases.py).
-#if defined(DE_X_PHASES)
-#define DE_PH_MAXWG 16384
-__device__ unsigned long long de_phase_rec[8][DE_PH_MAXWG][6];      // per workgroup: no two writers share a word
-#define DE_PHASE(n) do { if (threadIdx.x == 0 && blockIdx.x < DE_PH_MAXWG) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); de_phase_rec[P][blockIdx.x][n] += now_ - tick_; tick_ = now_; } } while (0)
-extern "C" __attribute__((visibility("default"))) int fl_debug_de_phases(unsigned long long *out, int clear)
-{
-    static unsigned long long host[8][DE_PH_MAXWG][6];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(de_phase_rec), sizeof host) != hipSuccess) return -1;
-    for (int p = 0; p < 8; ++p) for (int n = 0; n < 6; ++n) { unsigned long long a = 0; for (int w = 0; w < DE_PH_MAXWG; ++w) a += host[p][w][n]; out[p * 6 + n] = a; }
-    if (clear) { if (hipMemset(nullptr, 0, 0) != hipSuccess) (void)hipGetLastError(); void *sym = nullptr; if (hipGetSymbolAddress(&sym, HIP_SYMBOL(de_phase_rec)) != hipSuccess || hipMemset(sym, 0, sizeof host) != hipSuccess) return -1; }
-    return 0;
-}
-#else
-#define DE_PHASE(n)
-#endif
 
 #define DE_IN_PX(p) de_in_px<IN>(p)
 template <int P, int IN, int OUT>
@@ -577,7 +507,7 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
         ty = (int)q; tx = (int)(rm - q * tiles_x);
         // (the bottom row of tiles first: its tiles touch the image's edge — the slow ones, frame tables — and dispatched last they
         // WERE the kernel's tail; the top row, the other slow one, has always been first)
-        if (DE_BOTTOM_FIRST) ty = ty == 0 ? (int)tiles_y - 1 : ty - 1;
+        ty = ty == 0 ? (int)tiles_y - 1 : ty - 1;
     }
     // x of column 0 of tile row 0; for K > 0 the band starts SPAN to the left so that its last row reaches x = 0
     const int bx0 = tx * G::TW - (G::K > 0 ? G::SPAN : 0), by0 = ty * G::TH;
@@ -617,16 +547,12 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
         ul = ub + G::HU - G::HBU; vl = vb + G::HV - G::HBV; idx = ul * G::COLS + vl; return bidx < G::NPXB; }
 
     // Timing builds (results are garbage): -DDE_X_TAPSONLY runs the taps on whatever the LDS holds, -DDE_X_STOP_AFTER=n
-    // ends the workgroup after staging phase n (1..4) — tools/ab_de.sh, profiles/r03_de_phases.txt.
+    // ends the workgroup after staging phase n (1..4) — tools/de_slot_budget.sh, tools/ab_de.sh, profiles/r03_de_phases.txt.
     // Staging is a few instructions between long waits (global loads, barriers), the taps are 550 instructions
     // back to back: with the arbiter's default order a young workgroup's staging instructions queue behind the
     // older workgroups' tap loops and its loads go out late.  Staging therefore runs at raised priority, the
     // taps at the default: the loads of the next tiles are in flight while the current tiles compute.
-    __builtin_amdgcn_s_setprio(DE_PRIO_STAGE);
-#if defined(DE_X_PHASES)
-    unsigned long long tick_ = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0 && blockIdx.x < DE_PH_MAXWG) de_phase_rec[P][blockIdx.x][5] += 1ull;
-#endif
+    __builtin_amdgcn_s_setprio(3);
 #ifdef DE_X_TAPSONLY
     if (gspeed != 12345.0f) goto taps;
 #endif
@@ -641,7 +567,7 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     // barrier -> tap terms -> barrier.  The regrouped sum differs from the nested one by float rounding only (1e-7
     // relative in `avg`); tiles that touch an image edge keep the nested form below, which follows the reference's
     // clamped fetches literally.
-    if (G::HOIST && !border && DE_FAST_PREP) {
+    if (G::HOIST && !border) {
         float4 tq[G::NIT];
         DE_S_THREAD();
 #pragma unroll
@@ -661,7 +587,6 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
         }
         __syncthreads();
         DE_X_STOP(1)
-        DE_PHASE(0);
         DE_B_THREAD();
 #pragma unroll
         for (int it = 0; it < G::NITB; ++it) {
@@ -679,13 +604,12 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
         }
         __syncthreads();
         DE_X_STOP(4)
-        DE_PHASE(2);
     } else {
     // ---- S0: stage N (edge-clamped) and the dense density plane ------------------------------
     float4 tn[G::NIT];
     {
     DE_S_THREAD();
-    if (G::ROWWISE && !border && DE_INTERIOR_LOADS) {
+    if (G::ROWWISE && !border) {
         // no staged position leaves the image: no clamps, and a thread's element of iteration `it` lies it * RS rows below its
         // first one — one address per thread, a wave-uniform step per iteration (RS * K is even, see DeGeo::RS)
         const int u0 = sr0 - G::HU;
@@ -715,7 +639,7 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     // clamp to positions ON its frame, many to the same one: the tile evaluates each frame position it can need ONCE (one thread per
     // position, its loads issued behind the tile's own, which are still in flight) and S1 / S2 look the values up.
     // Same functions on the same arguments as before: same bits.
-    if (border && !DE_X_NOBORDER_EVAL) {
+    if (border) {
         const int x0a = bx0 - G::HV, nrows_top = min(G::ROWS, G::HU - by0), first_bot = max(0, ymax + 1 - (by0 - G::HU));
         // x extent of the staged rows above / below the image (shear is monotonic in the row)
         int tlo = 1, thi = 0, blo = 1, bhi = 0;
@@ -757,7 +681,6 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     }
     __syncthreads();
     DE_X_STOP(1)
-    DE_PHASE(0);
 
     // ---- S1: first density blur (7 taps, step 1) ----------------------------------------------
     // Every staged position is evaluated; where a tap leaves the staged region it reads whatever
@@ -777,7 +700,7 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
             const int o = (G::K & 1) ? (par ? o1 : o0) : o0;
             den = fmaf(sW[idx + o], kc.k[j], den);
         }
-        if (border && !DE_X_NOBORDER_EVAL) {
+        if (border) {
             const int gxu = bx0 + (((ul - G::HU) * G::K) >> 1) + vl - G::HV, gyu = by0 + ul - G::HU;
             if (gxu < 0 || gxu > xmax || gyu < 0 || gyu > ymax)         // virtual position: the blur AT the clamped position
                 den = sF1[gxu < 0 ? ul : gxu > xmax ? G::ROWS + ul : 2 * G::ROWS + (gyu < 0 ? 0 : G::XS) + gxu - (bx0 - G::HV + G::SHMIN)];
@@ -787,7 +710,6 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     }
     __syncthreads();
     DE_X_STOP(2)
-    DE_PHASE(1);
 
     // ---- S2: per-pixel tap terms for every position a tap can land on -------------------------
     // second blur (7 taps, step 2) -> gspeed / (avg + 1e-6) -> gradient exponentials; |ds| * w^dpow;
@@ -808,7 +730,7 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
             const int o = (G::K & 1) ? (par ? o1 : o0) : o0;
             den = fmaf(s1[idx + o], kc.k[i], den);
         }
-        if (border && !DE_X_NOBORDER_EVAL) {
+        if (border) {
             const int gxu = bx0 + (((ul - G::HU) * G::K) >> 1) + vl - G::HV, gyu = by0 + ul - G::HU;
             if (gxu < 0 || gxu > xmax || gyu < 0 || gyu > ymax)
                 den = sF2[gxu < 0 ? ul : gxu > xmax ? G::ROWS + ul : 2 * G::ROWS + (gyu < 0 ? 0 : G::XS) + gxu - (bx0 - G::HV + G::SHMIN)];
@@ -834,7 +756,6 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     }
     __syncthreads();
     DE_X_STOP(3)
-    DE_PHASE(2);
     // ---- S3: the per-pixel plane replaces the preparation planes -------------------------------
     {
     DE_B_THREAD();
@@ -846,7 +767,6 @@ k_de_dir(fl_dim d, float4 *__restrict__ Nout_, const float4 *__restrict__ N_, De
     }
     __syncthreads();
     DE_X_STOP(4)
-    DE_PHASE(3);
 
     }
 #ifdef DE_X_TAPSONLY
@@ -866,7 +786,7 @@ taps:
         // outputs lies inside has helped to stage the tile and is done — 4.5 % of the waves at 1080p (round 5).
         {
             const int xq = bx0 + ((cu * G::K) >> 1) + cv, yq = by0 + cu;
-            if (DE_SKIP_OUTSIDE && __builtin_amdgcn_ballot_w64(xq >= 0 && xq <= xmax && yq <= ymax) == 0ull) continue;
+            if (__builtin_amdgcn_ballot_w64(xq >= 0 && xq <= xmax && yq <= ymax) == 0ull) continue;
         }
         // a wave with a dead centre (w_c = 0: the rim of the flame, sparse images) takes the form that handles one
         const bool slow = __builtin_amdgcn_ballot_w64(!(sA[(cu + G::HA) * G::COLS + cv + G::HV].w > 0.0f)) != 0ull;
@@ -887,7 +807,6 @@ taps:
         Nout.st((uint32_t)(yo * (int)d.astride + xo), res);
     }
     } while (false);
-    DE_PHASE(4);
 }
 
 template <int P, int IN, int OUT>

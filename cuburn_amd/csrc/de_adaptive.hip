@@ -23,9 +23,7 @@
 
 #define DEA_TW 64                 // tile width = one wave
 #define DEA_TH 16                 // tile height = four waves of four rows
-#ifndef DEA_RB
 #define DEA_RB 4                  // source rows per LDS band (8: 10 % slower, fewer workgroups per CU)
-#endif
 #define DEA_MAXW (DEA_TW + 2 * FL_DE_MAX_RADIUS)     // staged columns at the largest radius
 
 // log2(e) * 4.5 * 256: a = kA / m^2 for m = 16 h

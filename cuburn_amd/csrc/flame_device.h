@@ -84,9 +84,7 @@ __device__ __forceinline__ uint32_t trunca(float f) {
 
 // ---- binned accumulate geometry: 128 x 64 pixel tiles; record = {bin 11 | ly 6 | lx 7 | ci 8} --------
 #define FL_TILE_W 128u
-#ifndef FL_TILE_H_LOG2
 #define FL_TILE_H_LOG2 6u
-#endif
 #define FL_TILE_H (1u << FL_TILE_H_LOG2)
 #define FL_TILE_CELLS (FL_TILE_W * FL_TILE_H)
 #define FL_REC_BITS (15u + FL_TILE_H_LOG2)   /* ly + lx 7 + ci 8 */
@@ -102,9 +100,7 @@ __host__ __device__ static inline uint32_t fl_pack3_words(uint32_t batch_records
 #define FL_MAX_BINS 2047u                      /* 128x64 tiles: tile number shares the 32-bit staged record */
 #define FL_TILE_W_WIDE_LOG2 8u                 /* 256x64 tiles for larger images (tile number staged separately) */
 #define FL_MAX_BINS_WIDE 8191u
-#ifndef FL_BIN_R_MAX
 #define FL_BIN_R_MAX 16          /* rounds per sorted batch (records a thread holds in registers) */
-#endif
 
 // XCD id of the executing workgroup (HW_REG_XCC_ID, bits [3:0])
 __device__ __forceinline__ uint32_t xcc_id() { return __builtin_amdgcn_s_getreg(((4 - 1) << 11) | 20) & 7; }

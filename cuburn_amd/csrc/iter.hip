@@ -28,21 +28,10 @@
 #include <hip/hip_ext.h>
 #endif
 
-#ifndef FL_SCAN_SERIAL_MAX
-#define FL_SCAN_SERIAL_MAX 8u
-#endif
-#ifndef FL_SPLIT_MAX_XF
-#define FL_SPLIT_MAX_XF 9         /* per-genome kernels with more xforms keep a single copy of the walk */
-#endif
-#ifndef FL_CNT_SETS
 #define FL_CNT_SETS 3          /* sets of tile counters per 4-wave workgroup (LDS: an array of tiles + 1 words each) */
-#endif
-#ifndef FL_ITER_PRIO
-#define FL_ITER_PRIO 2         /* wave priority of the walk part of a round (0: no priority changes) */
-#endif
-#ifndef FL_LOG_NT
-#define FL_LOG_NT 1          /* the sample log leaves with non-temporal stores: written once, read by k_accum_tiles much later (k_accum_tiles 380 -> 347 us, k_iter unchanged) */
-#endif
+#define FL_CNT_SETS_BIG 2      /* the same for 8- and 16-wave workgroups (many tiles: scanning more sets costs more than it saves) */
+#define FL_SCATTER_DEPTH 4     /* returning cursor adds a thread keeps in flight in the scatter */
+// The three below can be set for the per-genome kernels through FLAME_RTC_FLAGS (tests/test_gpu_switches.py holds every setting to the same results)
 #ifndef FL_ITER_MERGE_MAX_XF
 #define FL_ITER_MERGE_MAX_XF 4 /* per-genome binned kernels of at most this many xforms run a round's plot inside the NEXT round's xform block
                                   (same results; 0: never.  cfg2, 3 xforms: k_iter_spec 653 -> 627 us; 8 xforms + final: -0.3 ... -1.2 %) */
@@ -52,15 +41,6 @@
 #endif
 #ifndef FL_SORT_LOCAL_TID
 #define FL_SORT_LOCAL_TID 1
-#endif
-#ifndef FL_SCATTER_DEPTH
-#define FL_SCATTER_DEPTH 4     /* returning cursor adds a thread keeps in flight in the scatter */
-#endif
-#ifndef FL_ITER_ROT3
-#define FL_ITER_ROT3 1
-#endif
-#ifndef FL_CNT_SETS_BIG
-#define FL_CNT_SETS_BIG 2      /* the same for 8- and 16-wave workgroups (many tiles: scanning more sets costs more than it saves) */
 #endif
 
 template <int NW>
@@ -72,9 +52,7 @@ __device__ __forceinline__ uint32_t shuffle_dest(uint32_t w, uint32_t l, uint32_
 // The first 18 words of an xform record (include/flame_hip.h (5)): affines, colour, structure
 // word, and the number + weight of the first variation.  Held in SGPRs.
 struct XfHead { float f[16]; int vid0; float w0; };
-#ifndef FL_XTAB_BYTES
 #define FL_XTAB_BYTES 256      /* LDS behind everything else: the per-xform operand table (kTab), 16 xforms */
-#endif
 
 __device__ __forceinline__ XfHead load_head(const float *__restrict__ xf) {
     XfHead h;
@@ -118,15 +96,12 @@ __device__ __forceinline__ void apply_xf(const XfHead &h, const float *__restric
 // variations, whether it has a post affine, and its variation numbers in order.
 #include "flame_spec.h"
 
-// FL_EARLY_TAIL (round 5): kernels whose records are fetched per round ask for the ten words behind the record's head — the first
+// The early tail (round 5): kernels whose records are fetched per round ask for the ten words behind the record's head — the first
 // variation's parameters and the second one's number and weight — a round ahead, together with the head, instead of at the top of the
 // xform's own block ~10 instructions before their use: a scalar load there was a scalar-cache latency per round that four waves per
 // SIMD only partly cover, and every lgkmcnt wait of the block waited for it.  cfg4 (eight xforms of two variations): k_iter_spec
 // 1.089 -> 1.019 ms, 30 -> 13 scalar loads and 40 -> 30 lgkmcnt waits in cfg5's loop (profiles/r05_early_tail.txt).  Same values from
-// the same words: bit-identical (the per-genome kernel is held to the interpreter in tests/).  -DFL_EARLY_TAIL=0: on demand, as before.
-#ifndef FL_EARLY_TAIL
-#define FL_EARLY_TAIL 1
-#endif
+// the same words: bit-identical (the per-genome kernel is held to the interpreter in tests/).
 constexpr int kTailFirst = FL_XF_HDR + 2, kTailWords = 10;
 struct XfTail { float w[kTailWords]; };
 // a variation's parameters: word `base + i` of the record, from the registers where the tail holds it
@@ -134,7 +109,7 @@ struct VTail {
     const float *__restrict__ p; const XfTail *t; int base;
     __device__ __forceinline__ float operator[](int i) const {
         const int wd = base + i;
-        return (FL_EARLY_TAIL && t && wd >= kTailFirst && wd < kTailFirst + kTailWords) ? t->w[wd - kTailFirst] : p[wd];
+        return (t && wd >= kTailFirst && wd < kTailFirst + kTailWords) ? t->w[wd - kTailFirst] : p[wd];
     }
 };
 template <int I, int J>
@@ -172,16 +147,13 @@ __device__ __forceinline__ void spec_apply_xf(const XfHead &h, const float *__re
 // does not change during a launch): the round then neither computes the next record's address nor loads it (three
 // scalar ALU instructions, up to five s_load and their share of the round's lgkmcnt waits — the scalar unit is on this
 // kernel's critical path).  Nine registers per xform (pre affine, colour, speed, first weight; six more with a post affine).
-#ifndef FL_RESIDENT_MAX_XF
-#define FL_RESIDENT_MAX_XF 4
-#endif
 __host__ __device__ constexpr int spec_resident_sgprs()
 {
     int n = 0;
     for (int i = 0; i < FL_SPEC_NXF; ++i) n += 9 + (kSpecPost[i] != 0 ? 6 : 0);
     return n;
 }
-constexpr bool kSpecResident = FL_SPEC_NXF <= FL_RESIDENT_MAX_XF && spec_resident_sgprs() <= 48;
+constexpr bool kSpecResident = FL_SPEC_NXF <= 4 && spec_resident_sgprs() <= 48;
 // ... and what a round would otherwise rebuild from those scalars with VECTOR instructions, every round, lives in vector registers
 // for the launch: a VALU instruction reads at most one scalar register, so `fma(a, x, fma(b, y, c))` with a, b, c in scalar
 // registers costs a v_mov for c, and the colour blend `fma(col, 1 - speed, colour * speed)` computes its two wave-uniform
@@ -198,7 +170,7 @@ constexpr bool kHoistAff = kHoistCol && 3 * FL_SPEC_NXF + 2 <= FL_HOIST_BUDGET;
 constexpr bool kHoistPost = kHoistAff && 3 * FL_SPEC_NXF + 2 + 2 * spec_npost() <= FL_HOIST_BUDGET;
 struct XfVec { float xo, yo, cprod, pxo, pyo; };
 // spec_apply_xf for a resident record: h.f[13] holds 1 - colour speed, v the vector-register copies
-// Kernels whose records are fetched per round (more than FL_RESIDENT_MAX_XF xforms) cannot keep every xform's operands in registers; they keep
+// Kernels whose records are fetched per round (more than four xforms, see kSpecResident) cannot keep every xform's operands in registers; they keep
 // them in a 16-byte-per-xform LDS table {x offset, y offset, 1 - colour speed, colour * speed}, filled once per launch, and read the entry of the
 // NEXT round's xform (chosen a round ahead) behind the swap: one address instruction and one ds_read_b128 per round instead of the two v_mov of
 // the affine and the v_sub + v_mov + v_mul of the colour blend.
@@ -256,7 +228,7 @@ template <int LO, int HI, class Extra>
 __device__ __forceinline__ void spec_dispatch_res(int k, const XfHead (&heads)[FL_SPEC_NXF], const XfVec (&hv)[FL_SPEC_NXF], const float *__restrict__ xf0, int xf_stride,
                                                   float &x, float &y, float &c, mwc_t &r, const XfTail (&tails)[FL_SPEC_NXF], Extra &&extra)
 {
-    if constexpr (HI - LO == 1) { extra(); spec_apply_xf_res<LO>(heads[LO], hv[LO], xf0 + LO * xf_stride, x, y, c, r, FL_EARLY_TAIL ? &tails[LO] : nullptr); }
+    if constexpr (HI - LO == 1) { extra(); spec_apply_xf_res<LO>(heads[LO], hv[LO], xf0 + LO * xf_stride, x, y, c, r, &tails[LO]); }
     else {
         constexpr int MID = (LO + HI) / 2;
         if (k < MID) spec_dispatch_res<LO, MID>(k, heads, hv, xf0, xf_stride, x, y, c, r, tails, extra);
@@ -466,10 +438,8 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
 #pragma unroll
         for (int i = 0; i < FL_SPEC_NXF; ++i) {
             heads[i] = load_head(P + xf_off + i * xf_stride);
-            if constexpr (FL_EARLY_TAIL) {
 #pragma unroll
-                for (int k = 0; k < kTailWords; ++k) tails[i].w[k] = (P + xf_off + i * xf_stride)[kTailFirst + k];
-            }
+            for (int k = 0; k < kTailWords; ++k) tails[i].w[k] = (P + xf_off + i * xf_stride)[kTailFirst + k];
             if constexpr (kHoistCol) {
                 const float csp = heads[i].f[13];
                 hv[i].cprod = heads[i].f[12] * csp;
@@ -485,10 +455,8 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     XfVec vfin = {};
     if constexpr (SPEC && kHoistFinal) {
         hfin_res = load_head(xf_final);
-        if constexpr (FL_EARLY_TAIL) {
 #pragma unroll
-            for (int k = 0; k < kTailWords; ++k) tfin.w[k] = xf_final[kTailFirst + k];
-        }
+        for (int k = 0; k < kTailWords; ++k) tfin.w[k] = xf_final[kTailFirst + k];
         const float csp = hfin_res.f[13];
         vfin.cprod = hfin_res.f[12] * csp;
         vfin.xo = hfin_res.f[2]; vfin.yo = hfin_res.f[5];
@@ -502,7 +470,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     XfHead hnext = RESIDENT ? XfHead{} : load_head(xf_next);
 #ifdef FL_RTC
     XfTail tail_next = {};
-    if constexpr (SPEC && kTab && FL_EARLY_TAIL) {
+    if constexpr (SPEC && kTab) {
 #pragma unroll
         for (int i = 0; i < kTailWords; ++i) tail_next.w[i] = xf_next[kTailFirst + i];
     }
@@ -530,15 +498,13 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         // waves that are packing records: k_iter_spec 672 -> 632 us ALONE (level 1, 2 or 3: the same; lowering it later, or
         // raising it only for the swap, gains less: profiles/r03_wave_priority.txt).  In the two-lane frame loop the other
         // lane's kernels already fill those issue slots: the frame time does not move; a single frame gains the 6 %.
-#if FL_ITER_PRIO
-        __builtin_amdgcn_s_setprio(FL_ITER_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(2);
         if (!isfinite(fabsf(x) + fabsf(y))) reseed(x, y, color, rctx);      // iter.py:225-229
 
         const int k_cur = k_next;
         const float *__restrict__ xf_cur = xf_next;
 #ifdef FL_RTC
-        XfTail tail = tail_next;          // (FL_EARLY_TAIL: requested a round ahead, with the head)
+        XfTail tail = tail_next;          // (the early tail: requested a round ahead, with the head)
 #endif
         sel_next = __builtin_amdgcn_readfirstlane(mwc_next(rctx));
         k_next = choose(sel_next);
@@ -549,14 +515,14 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         // arrive: k_iter 0.717 -> 0.70 ms, the interpreter kernel -15 %.
 #ifdef FL_RTC
         if constexpr (RESIDENT) spec_dispatch_res<0, FL_SPEC_NXF>(k_cur, heads, hv, P + xf_off, xf_stride, x, y, color, rctx, tails, extra);
-        else if constexpr (SPEC && kTab) spec_dispatch_tab<0, FL_SPEC_NXF>(k_cur, hnext, tcur, xf_cur, x, y, color, rctx, FL_EARLY_TAIL ? &tail : nullptr, extra);
+        else if constexpr (SPEC && kTab) spec_dispatch_tab<0, FL_SPEC_NXF>(k_cur, hnext, tcur, xf_cur, x, y, color, rctx, &tail, extra);
         else if constexpr (SPEC) spec_dispatch<0, FL_SPEC_NXF>(k_cur, hnext, xf_cur, x, y, color, rctx, extra);
         else
 #endif
         { extra(); apply_xf(hnext, xf_cur, var_stride, x, y, color, rctx); }
         if constexpr (!RESIDENT) hnext = load_head(xf_next);
 #ifdef FL_RTC
-        if constexpr (SPEC && kTab && FL_EARLY_TAIL) {
+        if constexpr (SPEC && kTab) {
 #pragma unroll
             for (int i = 0; i < kTailWords; ++i) tail_next.w[i] = xf_next[kTailFirst + i];
         }
@@ -565,23 +531,13 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
 
         // rotate walkers between waves (iter.py:274-294), double-buffered by round parity
         {
-#if defined(FL_X_NOSWAP)            /* timing experiments only (wrong results): no point swap at all ... */
-            (void)dst;
-#elif defined(FL_X_HALF_BARRIERS)   /* ... or a barrier every other round */
-            swp[par][0][dst] = x; swp[par][1][dst] = y; swp[par][2][dst] = color;
-            if (par) __syncthreads();
-            x = swp[par][0][tid]; y = swp[par][1][tid]; color = swp[par][2][tid];
-#else
             swp[par][0][dst] = x; swp[par][1][dst] = y; swp[par][2][dst] = color;
             __syncthreads();
             x = swp[par][0][tid]; y = swp[par][1][tid]; color = swp[par][2][tid];
-#endif
 #ifdef FL_RTC
             if constexpr (SPEC && kTab) tcur = xtab[half * 16u + k_next];          // the next round's operands: on their way while this round plots
 #endif
-#if FL_ITER_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
             par ^= 1u;
         }
     };
@@ -590,7 +546,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     // bookkeeping is ONE counter: the scalar unit is on this kernel's critical path.
     const uint32_t nfuse = min(fuse, nrounds);
 #ifdef FL_RTC
-    constexpr bool SPLIT_FUSE = !SPEC || FL_SPEC_NXF <= FL_SPLIT_MAX_XF;
+    constexpr bool SPLIT_FUSE = !SPEC || FL_SPEC_NXF <= 9;      // per-genome kernels with more xforms keep a single copy of the walk
 #else
     constexpr bool SPLIT_FUSE = true;
 #endif
@@ -599,7 +555,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     // The swap destination cycles through three values (phase = round % 3).  Rotating three registers costs three
     // v_mov per round; small kernels instead carry THREE copies of the round, one per destination, entered at the
     // current phase (ROT3; kernels of many heavy xforms keep one copy and rotate).
-    constexpr bool ROT3 = SPLIT_FUSE && FL_ITER_ROT3;
+    constexpr bool ROT3 = SPLIT_FUSE;
     uint32_t ph = 0;                                    // which of rot0 / rot1 / rot2 the next round uses (ROT3)
     auto next_dst = [&]() __attribute__((always_inline)) -> uint32_t {      // one copy: rotate
         const uint32_t dst = rot0;
@@ -629,7 +585,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         float fx = x, fy = y, fc = color;
 #ifdef FL_RTC
         if constexpr (SPEC) {
-            if constexpr (kHoistFinal) spec_apply_xf_res<FL_SPEC_NXF, true, true, true>(hfin_res, vfin, xf_final, fx, fy, fc, rctx, FL_EARLY_TAIL ? &tfin : nullptr);
+            if constexpr (kHoistFinal) spec_apply_xf_res<FL_SPEC_NXF, true, true, true>(hfin_res, vfin, xf_final, fx, fy, fc, rctx, &tfin);
             else if constexpr (FL_SPEC_FINAL != 0) { const XfHead hfin = load_head(xf_final); spec_apply_xf<FL_SPEC_NXF>(hfin, xf_final, fx, fy, fc, rctx); }
         } else
 #endif
@@ -690,9 +646,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             const uint32_t rec = __builtin_amdgcn_perm(t2, cbits, 0x06050400u);
             if (WIDE) skey[staged * NT + tid] = (uint16_t)bin;
             stage[staged * NT + tid] = rec;
-#ifndef FL_X_NO_CNT         /* timing experiment (wrong results): no count per record */
             __hip_atomic_fetch_add(my_cnt + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
         } else {
             // measurement mode: everything but the accumulate (ceiling of the walk itself)
             pend_old += ok ? val + gi : 0ull;
@@ -728,11 +682,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         plot_rest(fx, fy, fc, staged);
     });
     rd += blen;
-#ifdef FL_X_SKIP_SORT      /* timing experiment (wrong results): no batch epilogue at all */
-    if (false) {
-#else
     if (BINNED && plotting) {
-#endif
             // The batch epilogue, compiled twice: for the full batch — every "is there a record" test folds away and the scatter
             // is straight-line code — and for a launch's short last batch.
             auto sort_batch = [&](const uint32_t staged) __attribute__((always_inline)) {
@@ -765,10 +715,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                 // wave walking all 2109 tiles of an 8K image kept the other fifteen waiting for 15 %
                 // of the kernel.)
                 const uint32_t nchunk = (bg.nbins + 64u) >> 6;          // tiles 0..nbins, the last one = "no record"
-#ifdef FL_X_NO_SCAN         /* timing experiment (wrong results) */
-                if (true) { if (tid == 0) *s_nvalid = staged * NT; } else
-#endif
-                if (nchunk <= FL_SCAN_SERIAL_MAX) { // few tiles (1080p: 4 chunks): one wave is quicker than a second barrier
+                if (nchunk <= 8u) { // few tiles (1080p: 4 chunks): one wave is quicker than a second barrier
                     if (w == 0) {
                         uint32_t running = 0;
                         for (uint32_t c0 = 0; c0 <= bg.nbins; c0 += 64) {
@@ -824,7 +771,6 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                 __syncthreads();
                 // scatter, four records per thread in flight (the returning LDS atomic is a
                 // ~100-cycle round trip; one at a time this loop was a quarter of the kernel)
-#ifndef FL_X_NO_SCATTER     /* timing experiment (wrong results) */
 #pragma unroll
                 for (int q0 = 0; q0 < FL_BIN_R_MAX; q0 += FL_SCATTER_DEPTH) {
                     if ((uint32_t)q0 >= staged) break;
@@ -832,26 +778,13 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
 #pragma unroll
                     for (int q = 0; q < FL_SCATTER_DEPTH; ++q)
                         if (k2[q0 + q] != 0xffffffffu)
-#ifdef FL_X_SCATTER_READS   /* timing experiment (wrong results): a plain read of the cursor instead of the returning add */
-                            pos[q] = (my_cnt[k2[q0 + q]] + (uint32_t)(q0 + q) * NT + tid) & (uint32_t)(FL_BIN_R_MAX * NT - 1);
-#else
                             pos[q] = __hip_atomic_fetch_add(my_cnt + k2[q0 + q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
 #pragma unroll
                     for (int q = 0; q < FL_SCATTER_DEPTH; ++q)
-#if defined(FL_X_NO_SCAN)
-                        if (k2[q0 + q] != 0xffffffffu) stage[pos[q] & (uint32_t)(FL_BIN_R_MAX * NT - 1)] = r2[q0 + q] & ((1u << PAY_BITS) - 1u);
-#else
                         if (k2[q0 + q] != 0xffffffffu) stage[pos[q]] = r2[q0 + q] & ((1u << PAY_BITS) - 1u);
-#endif
                 }
-#endif
                 __syncthreads();
-#ifdef FL_X_NO_PACK         /* timing experiment (wrong results) */
-                const uint32_t nvalid = 0;
-#else
                 const uint32_t nvalid = *s_nvalid;
-#endif
                 if constexpr (PACK3) {
                     // three 21-bit records to an aligned 64-bit word (flame_device.h): the log is what the accumulate streams, and at
                     // 1080p it is bound by those bytes.  The slots behind the batch's last record hold whatever the LDS held (the
@@ -864,24 +797,17 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                         const uint32_t a = stage[3u * i], b = stage[3u * i + 1u], c3 = stage[3u * i + 2u];
                         u32x2_ o;
                         o.x = a | (b << 21); o.y = (b >> 11) | (c3 << 10);
-#if FL_LOG_NT      /* the log is written once and read by another kernel much later */
+                        // non-temporal: the log is written once and read by another kernel much later (k_accum_tiles 380 -> 347 us, k_iter unchanged)
                         __builtin_nontemporal_store(o, d2 + i);
-#else
-                        d2[i] = o;
-#endif
                     }
                 } else {
                 uint4 *dst = reinterpret_cast<uint4 *>(bin_log + (size_t)batch_id * bg.rounds * NT);
-#if FL_LOG_NT
                 {
                     typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
                     const u32x4_ *s4 = reinterpret_cast<const u32x4_ *>(stage);
                     u32x4_ *d4 = reinterpret_cast<u32x4_ *>(dst);
                     for (uint32_t i = tid; i * 4 < nvalid; i += NT) __builtin_nontemporal_store(s4[i], d4 + i);
                 }
-#else
-                for (uint32_t i = tid; i * 4 < nvalid; i += NT) dst[i] = reinterpret_cast<const uint4 *>(stage)[i];
-#endif
                 }
                 for (uint32_t i = tid; i < SETS * CNTW; i += NT) cnt[i] = 0;               // the cursors become counters again
                 ++batch_in_slot;
@@ -923,9 +849,6 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
 #ifdef FL_RTC
 // the kernel of ONE genome structure, walker geometry and accumulate mode (rtc.hip compiles it on
 // first use and caches the code object)
-#ifdef FL_X_WAVES_PER_EU    /* experiment: cap the vector registers (8: 64, 7: 72, 6: 80 ...) */
-__attribute__((amdgpu_waves_per_eu(FL_X_WAVES_PER_EU, FL_X_WAVES_PER_EU)))
-#endif
 extern "C" __global__ void __launch_bounds__(FL_SPEC_NW * 64) k_iter_spec(FL_ITER_ARGS)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

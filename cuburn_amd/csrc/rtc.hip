@@ -119,25 +119,10 @@ int rtc_compile(const IterSpec &spec, int nw, bool count, int acc, std::vector<c
     }
     const char *opts[] = {arch_opt.c_str(), "-O3", "-std=c++20", "-ffp-contract=off", "-DFL_RTC=1",
                           "-mllvm", "-structurizecfg-skip-uniform-regions=true",
-#ifdef FL_SCAN_SERIAL_MAX
-                          "-DFL_SCAN_SERIAL_MAX=" FL_STR(FL_SCAN_SERIAL_MAX),
-#endif
-#ifdef FL_CNT_SETS
-                          "-DFL_CNT_SETS=" FL_STR(FL_CNT_SETS),
-#endif
-#ifdef FL_CNT_SETS_BIG
-                          "-DFL_CNT_SETS_BIG=" FL_STR(FL_CNT_SETS_BIG),
-#endif
                           "-DFL_LOG_PACK3=" FL_STR(FL_LOG_PACK3),
-#ifdef FL_BIN_R_MAX
-                          "-DFL_BIN_R_MAX=" FL_STR(FL_BIN_R_MAX),
-#endif
-#ifdef FL_ITER_ROT3
-                          "-DFL_ITER_ROT3=" FL_STR(FL_ITER_ROT3),
-#endif
                           "-fno-slp-vectorize",
     };
-    // FLAME_RTC_FLAGS="-mllvm -x=y ...": extra options for code-generation experiments (tools/exp_rtc_flags.sh)
+    // FLAME_RTC_FLAGS="-mllvm -x=y ...": extra options, e.g. the switches of iter.hip that tests/test_gpu_switches.py sets
     std::vector<const char *> optv(opts, opts + sizeof opts / sizeof *opts);
     if (extra_opt) optv.push_back(extra_opt);
     std::vector<std::string> extra;

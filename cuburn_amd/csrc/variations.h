@@ -22,10 +22,7 @@
 // that reaches them is re-seeded within a few rounds): v_atan2 with max(|a|, |b|) > 2^126 — the reciprocal is a denormal, flushed: the
 // angle comes out as 0 or pi/2 — or with BOTH operands denormal (the FLT_MIN clamp); v_fmod with |b| > 2^126 (one subtraction
 // where up to three may be needed); v_fmod_pi next to multiples of pi, where the result may be a few ulp of pi below 0 or at pi.
-// -DFL_LIBM_MATH (through FLAME_RTC_FLAGS; FL_LIBM_ATAN2 is its round-4 name) compiles the device library's functions back in.
-#if defined(FL_LIBM_ATAN2) && !defined(FL_LIBM_MATH)
-#define FL_LIBM_MATH 1
-#endif
+// -DFL_LIBM_MATH (through FLAME_RTC_FLAGS) compiles the device library's functions back in.
 #ifndef FL_LIBM_MATH
 __device__ __forceinline__ float v_atan2(float a, float b)
 {

@@ -336,7 +336,8 @@ int fl_debug_counters(fl_ctx *ctx, uint64_t out4[4]);
  *                            capped at 1024 rounds, or at 2304 when that saves the frame a launch)
  *   FLAME_DE_ORDER=d|dddddddd tile order of the DE kernels, one digit for all or one per direction (0 per-XCD column-major runs,
  *                            1 row-major, 2 row-major in runs per XCD; default: by direction and image size, de.hip)
- * Compile-time timing builds (-DDE_X_*, -DACC_X_*) produce wrong pictures and exist only in libraries built for tools/. */
+ * The two compile-time timing builds (-DDE_X_TAPSONLY, -DDE_X_STOP_AFTER=n) produce wrong pictures and exist only in the
+ * libraries that tools/de_slot_budget.sh builds. */
 
 #ifdef __cplusplus
 }

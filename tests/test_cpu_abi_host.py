@@ -269,7 +269,7 @@ def test_per_genome_binned_kernel_register_budget(built, tmp_path, monkeypatch, 
 
 def test_asm_issued_loads_are_not_touched_in_flight(tmp_path):
     """k_accum_tiles issues its record loads and the tile add's returning atomics from inline asm and
-    waits for them itself (binned.hip: ACC_PIPE, ACC_ADD_ILP), so the compiler does not know those
+    waits for them itself (binned.hip: the pipelined record loop, ACC_ADD_ILP), so the compiler does not know those
     registers are in flight.  The device assembly of the shipped configuration is checked: no
     instruction may read or write such a register between its load / atomic and the wait, and the
     128x64 kernel must keep the budget that lets two workgroups share a CU (64 VGPRs, 80 SGPRs, no
@@ -363,3 +363,34 @@ def test_de_kernels_hold_32_waves_per_cu_without_scratch(tmp_path):
     for k in de:
         num = lambda key: int(re.search(key + r': (\d+)', k).group(1))
         assert num('VGPRs') <= 64 and num(r'ScratchSize \[bytes/lane\]') == 0 and num('TotalSGPRs') <= 80, k[:300]
+
+
+def test_documents_name_only_tools_that_exist():
+    """A `tools/<name>` path in the documents, the sources, the tests or bench.py is a file under tools/, unless its line says
+    that the tool was "(removed ..." — the record of what produced an old result stays readable, nothing points a reader to a
+    script that is not there.  tools/README.md has one row per file: every name in a row's first column exists, and every
+    file has a row."""
+    tool = re.compile(r'tools/([A-Za-z0-9_]+\.(?:sh|py|hip|c))\b')
+    paths = [os.path.join(REPO, p) for p in ('README.md', 'DESIGN.md', 'bench.py', 'tools/README.md', 'profiles/README.md')]
+    paths += [os.path.join(REPO, 'tests', f) for f in sorted(os.listdir(os.path.join(REPO, 'tests'))) if f.endswith('.py')]
+    for root, dirs, files in os.walk(os.path.join(REPO, 'cuburn_amd')):
+        dirs[:] = [d for d in dirs if not d.startswith(('build', '_lib', '__pycache__'))]       # build products are not sources
+        paths += [os.path.join(root, f) for f in sorted(files) if f.endswith(('.py', '.hip', '.h', '.md')) or f == 'Makefile']
+    have = set(os.listdir(os.path.join(REPO, 'tools')))
+    dangling = []
+    for p in paths:
+        for n, line in enumerate(open(p, errors='replace'), 1):
+            if '(removed' in line:
+                continue
+            dangling += ['%s:%d: %s' % (os.path.relpath(p, REPO), n, name) for name in tool.findall(line) if name not in have]
+    assert not dangling, '\n'.join(dangling)
+    assert len(paths) > 30 and sum(len(tool.findall(open(p, errors='replace').read())) for p in paths) > 100      # the scan found its subjects
+    # tools/README.md: the names of a row are the backticked words of its first column
+    rows = set()
+    for line in open(os.path.join(REPO, 'tools', 'README.md')):
+        if line.startswith('| `'):
+            rows |= set(re.findall(r'`([A-Za-z0-9_]+\.(?:sh|py|hip|c))\b', line.split('|')[1]))
+    assert not rows - have, sorted(rows - have)
+    # (a micro-benchmark built in place, `atomic_bench` next to `atomic_bench.hip`, is its source's product)
+    files = set(f for f in have if f != 'README.md' and not ('.' not in f and (f + '.hip' in have or f + '.c' in have)))
+    assert not files - rows, sorted(files - rows)
