@@ -395,10 +395,10 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     REQUIRE(nrows >= 1 && nrows <= 4096 && nops >= 1, "bad row / op count");
     uint32_t ps = prog[3];
     const int xo = prog[5], xs = prog[6], vs = prog[7], nrec = prog[1] + prog[2];
-    std::vector<int> nvar_seen(nrec, -1);
+    std::vector<int> nvar_seen(nrec, -1), opac_seen(nrec, 0), opac_ops(nrec, 0);
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;
-        REQUIRE(o[0] >= FL_OP_SPLINE && o[0] <= FL_OP_CONST, "bad op kind");
+        REQUIRE(o[0] >= FL_OP_SPLINE && o[0] <= FL_OP_OPACITY, "bad op kind");
         REQUIRE(o[1] >= 0 && (uint32_t)o[1] < ps, "op destination out of range");
         if (o[0] != FL_OP_CONST) {
             // every word an op writes and every spline row it reads must lie inside the block / row table
@@ -416,33 +416,41 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
             REQUIRE((uint32_t)o[1] + ndst <= ps, "op destination out of range");
             REQUIRE(o[2] >= 0 && (uint32_t)o[2] + nsrc <= nrows, "op row out of range");
             if (o[0] == FL_OP_RATIO2 || o[0] == FL_OP_PERSP) REQUIRE(o[3] >= 0 && (uint32_t)o[3] < nrows, "op row out of range");
+            if (o[0] == FL_OP_OPACITY) {        // word 15 of a selectable record (the final xform has no opacity)
+                const int rel = o[1] - xo;
+                REQUIRE(rel >= 0 && rel / xs < prog[1] && rel % xs == 15, "opacity op must write word 15 of a selectable xform record");
+                ++opac_ops[rel / xs];
+            }
             continue;
         }
-        // structure words: xform word 14 (nvar | post << 8) or a variation number
+        // structure words: xform word 14 (nvar | post << 8 | opacity << 9) or a variation number
         const int rel = o[1] - xo;
         REQUIRE(rel >= 0 && rel / xs < nrec, "structure word outside the xform records");
         const int w = rel % xs;
         if (w == 14) {
             const int nv = o[2] & 0xff;
-            REQUIRE(FL_XF_HDR + nv * vs <= xs && (o[2] >> 9) == 0, "bad variation count");
+            REQUIRE(FL_XF_HDR + nv * vs <= xs && (o[2] >> 10) == 0, "bad variation count");
+            REQUIRE(((o[2] >> 9) & 1) == 0 || rel / xs < prog[1], "the final xform has no opacity");
             nvar_seen[rel / xs] = nv;
+            opac_seen[rel / xs] = (o[2] >> 9) & 1;
         } else {
             REQUIRE(w >= FL_XF_HDR && (w - FL_XF_HDR) % vs == 0, "misplaced structure word");
             if (!known_var(o[2])) return fail(FL_E_UNSUPPORTED, "unknown variation id", __FILE__, __LINE__);
         }
     }
     for (int i = 0; i < nrec; ++i) REQUIRE(nvar_seen[i] >= 0, "xform record without a variation count");
+    for (int i = 0; i < nrec; ++i) REQUIRE(opac_ops[i] == opac_seen[i], "opacity flag and opacity op do not match");
     // structure tables for the specialised kernel: counts / post flags / variation numbers per record
     IterSpec spec;
     spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
     spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
-    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>());
+    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>());
     for (int i = 0; i < nrec; ++i) spec.vids[i].assign(nvar_seen[i], -1);
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;
         if (o[0] != FL_OP_CONST) continue;
         const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
-        if (w == 14) { spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; }
+        if (w == 14) { spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; spec.opac[rec] = (o[2] >> 9) & 1; }
         else {
             const int j = (w - FL_XF_HDR) / vs;
             if (j < (int)spec.vids[rec].size()) spec.vids[rec][j] = o[2];
@@ -1233,13 +1241,20 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
     IterSpec spec;
     spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
     spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
-    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>(16, 0));
+    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>(16, 0));
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;
+        if (o[0] == FL_OP_OPACITY) {
+            const int rel = o[1] - xo;
+            REQUIRE(rel >= 0 && rel / xs < prog[1] && rel % xs == 15, "opacity op must write word 15 of a selectable xform record");
+        }
         if (o[0] != FL_OP_CONST) continue;
         const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
         REQUIRE(rel >= 0 && rec < nrec, "structure word outside the xform records");
-        if (w == 14) { spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; }
+        if (w == 14) {
+            REQUIRE((o[2] >> 10) == 0 && (((o[2] >> 9) & 1) == 0 || rec < prog[1]), "bad structure word");
+            spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; spec.opac[rec] = (o[2] >> 9) & 1;
+        }
         else { const int j = (w - FL_XF_HDR) / vs; if (j >= (int)spec.vids[rec].size()) spec.vids[rec].resize(j + 1, 0); spec.vids[rec][j] = o[2]; }
     }
     std::vector<char> code;

@@ -118,6 +118,14 @@ k_interp_params(float *__restrict__ params, const float *__restrict__ times, con
             o[0] = pdist; o[1] = sinf(pang); o[2] = pdist * cosf(pang);
         } break;
         case FL_OP_CONST: o[0] = __int_as_float(op.z); break;
+        case FL_OP_OPACITY: {           // xform opacity -> plot probability (flam3's visibility curve 10^log2(p); include/flame_hip.h (5) word 15)
+            // The snap to 1: a constant-1 magnitude spline does not evaluate to exactly 1.0f (linlog / linexp above), and the
+            // iterate kernel spends a random number on every q strictly between 0 and 1.
+            const float p = fminf(fmaxf(ROW(op.z, true), 0.0f), 1.0f);
+            float q = exp2f(log2f(p) * 3.3219281f);
+            if (q < 2.3283064e-10f) q = 0.0f;                  // 2^-32: below the resolution of the draw
+            o[0] = p <= 0.0f ? 0.0f : p >= 1.0f - 1.0e-6f ? 1.0f : q;
+        } break;
         default: break;
         }
     }

@@ -63,12 +63,30 @@ __device__ __forceinline__ XfHead load_head(const float *__restrict__ xf) {
     return h;
 }
 
+// Xform opacity (include/flame_hip.h (5), words 14 / 15): the sample an xform has just produced is plotted with probability q and
+// hidden otherwise.  The decision is the SAMPLE's, and the sample leaves this lane in the swap before it is plotted (with MERGE it is
+// plotted inside the next round's xform block): the hidden bit rides in the sign of the colour, which is in [0, 1] — no LDS and no
+// swap traffic of its own; the receiving lane takes it off again behind the swap (iter_body).  q is wave-uniform (a scalar register),
+// so whether to draw at all is a scalar integer branch on its bit pattern: only 0 < q < 1 spends a random number, q == 0 hides every
+// sample and anything else (1; and whatever is not a probability) hides none.  Every arm of a kernel that has an opacity xform
+// leaves the colour's sign defined (records without opacity: cleared).
+__device__ __forceinline__ void opacity_mark(const bool has, const float q, float &c, mwc_t &r)
+{
+    const uint32_t qb = __float_as_uint(q);
+    uint32_t hid = 0u;
+    if (has) {
+        if (qb - 1u < 0x3f800000u - 1u) hid = mwc_next_01(r) <= q ? 0u : 0x80000000u;
+        else if (qb == 0u) hid = 0x80000000u;
+    }
+    c = __uint_as_float((__float_as_uint(c) & 0x7fffffffu) | hid);
+}
+
 // cuburn/code/iter.py:121-149: pre affine, sum of variations, optional post affine, colour
 // blend.  The record is wave-uniform; `h` was loaded a round ahead (its choice depends only on
 // the RNG), so the s_load latency of the record is off the critical path; only parameters of
 // parametric variations and variations beyond the first are loaded on demand.
 __device__ __forceinline__ void apply_xf(const XfHead &h, const float *__restrict__ xf, int var_stride,
-                                         float &x, float &y, float &c, mwc_t &r)
+                                         float &x, float &y, float &c, mwc_t &r, const bool any_opac = false)
 {
     const int word14 = __float_as_int(h.f[14]);
     const int nvar = word14 & 0xff;
@@ -87,6 +105,7 @@ __device__ __forceinline__ void apply_xf(const XfHead &h, const float *__restric
     }
     const float csp = h.f[13];
     c = fmaf(c, 1.0f - csp, h.f[12] * csp);
+    if (any_opac) opacity_mark((word14 & 0x200) != 0, h.f[15], c, r);      // (the walk's selectable xforms of programs with the flag; the final xform and the tap pass false)
     x = ox; y = oy;
 }
 
@@ -124,6 +143,16 @@ __device__ __forceinline__ void spec_variations(const float *__restrict__ xf, fl
     }
 }
 
+// does any selectable xform of this genome have an opacity?  (kernels of genomes without one: every trace of it is compiled out)
+__host__ __device__ constexpr bool spec_any_opac() { for (int i = 0; i < FL_SPEC_NXF; ++i) if (kSpecOpac[i] != 0) return true; return false; }
+constexpr bool kAnyOpac = spec_any_opac();
+// the opacity decision of record I's sample, behind its colour blend (q = word 15 of the head, in a scalar register)
+template <int I>
+__device__ __forceinline__ void spec_opacity(const XfHead &h, float &c, mwc_t &r)
+{
+    if constexpr (kAnyOpac && I < FL_SPEC_NXF) opacity_mark(kSpecOpac[I] != 0, h.f[15], c, r);
+}
+
 // apply_xf with the structure of record I known at compile time (same arithmetic, same order)
 template <int I>
 __device__ __forceinline__ void spec_apply_xf(const XfHead &h, const float *__restrict__ xf,
@@ -140,6 +169,7 @@ __device__ __forceinline__ void spec_apply_xf(const XfHead &h, const float *__re
     }
     const float csp = h.f[13];
     c = fmaf(c, 1.0f - csp, h.f[12] * csp);
+    spec_opacity<I>(h, c, r);
     x = ox; y = oy;
 }
 
@@ -191,6 +221,7 @@ __device__ __forceinline__ void spec_apply_xf_tab(const XfHead &h, const float4 
     }
     c = fmaf(c, t.z, t.w);
     asm volatile("" : "+v"(c));
+    spec_opacity<I>(h, c, r);
     x = ox; y = oy;
 }
 template <int LO, int HI, class Extra>
@@ -222,6 +253,7 @@ __device__ __forceinline__ void spec_apply_xf_res(const XfHead &h, const XfVec &
     // (the empty asm keeps the blend in its xform's arm: merged into one v_fmac behind the arms it needs a v_mov of the product in each)
     if constexpr (COL) { c = fmaf(c, h.f[13], v.cprod); asm volatile("" : "+v"(c)); }
     else { const float csp = h.f[13]; c = fmaf(c, 1.0f - csp, h.f[12] * csp); }
+    spec_opacity<I>(h, c, r);
     x = ox; y = oy;
 }
 template <int LO, int HI, class Extra>
@@ -386,6 +418,18 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     if constexpr (SPEC && FL_HOIST_BUDGET >= 2) asm volatile("" : "+v"(cam2), "+v"(cam5));      // the camera's offsets in vector registers (see kHoistCol)
 #endif
     const float *__restrict__ xf_final = P + xf_off + nxf * xf_stride;
+    // Does any selectable xform have an opacity (bit 9 of word 14)?  The per-genome kernel knows at compile time; the interpreter
+    // looks once per launch (wave-uniform).  Without one, nothing below touches the colour's sign or the plot.
+    // (OPAC: can this kernel meet one at all — what it does for hidden samples is compiled only then)
+#ifdef FL_RTC
+    constexpr bool OPAC = SPEC ? kAnyOpac : true;
+#else
+    constexpr bool OPAC = true;
+#endif
+    bool any_opac = false;
+    if constexpr (OPAC && SPEC) any_opac = true;
+    else if constexpr (OPAC) for (int i = 0; i < nxf; ++i) any_opac |= (__float_as_int(P[xf_off + i * xf_stride + 14]) & 0x200) != 0;
+    uint32_t hid_bits = 0u;                             // sign bit: the sample this lane holds is hidden (set behind the swap)
 
     // Cumulative xform densities of this slot's temporal sample (constant for the launch), one
     // per lane: the wave-uniform choice is then ONE vector compare + find-first-set instead
@@ -519,7 +563,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         else if constexpr (SPEC) spec_dispatch<0, FL_SPEC_NXF>(k_cur, hnext, xf_cur, x, y, color, rctx, extra);
         else
 #endif
-        { extra(); apply_xf(hnext, xf_cur, var_stride, x, y, color, rctx); }
+        { extra(); apply_xf(hnext, xf_cur, var_stride, x, y, color, rctx, any_opac); }
         if constexpr (!RESIDENT) hnext = load_head(xf_next);
 #ifdef FL_RTC
         if constexpr (SPEC && kTab) {
@@ -534,6 +578,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             swp[par][0][dst] = x; swp[par][1][dst] = y; swp[par][2][dst] = color;
             __syncthreads();
             x = swp[par][0][tid]; y = swp[par][1][tid]; color = swp[par][2][tid];
+            if constexpr (OPAC) if (any_opac) { hid_bits = __float_as_uint(color); color = fabsf(color); }      // the hidden bit came with the point (opacity_mark)
 #ifdef FL_RTC
             if constexpr (SPEC && kTab) tcur = xtab[half * 16u + k_next];          // the next round's operands: on their way while this round plots
 #endif
@@ -596,6 +641,8 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         cy = fmaf(cam3, fx, fmaf(cam4, fy, cam5));
         // iter.py:346-348; rint of a value in [0, 255] = the low mantissa bits of (value + 2^23): the float adder rounds to nearest even
         cf = fminf(fmaxf(fmaf(fc, 255.0f, color_dither), 0.0f), 255.0f) + 8388608.0f;
+        // a hidden sample: the sign of the scaled colour says so to the second part (its low byte, the palette column, is not touched)
+        if constexpr (OPAC) if (any_opac) cf = __uint_as_float((__float_as_uint(cf) & 0x7fffffffu) | (hid_bits & 0x80000000u));
         if constexpr (MERGE) asm volatile("" : "+v"(cx), "+v"(cy), "+v"(cf));      // (here, not sunk behind the reseed)
     };
     // ... and the cell and the record or the add (no random numbers in the binned back-end)
@@ -610,6 +657,15 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         bool ok = (ix < astride) & (iy < aheight);
         // (binned mode: a rejected sample only needs its tile number forced to "none" below, its
         // coordinate bits are never looked at)
+        if constexpr (OPAC) {
+            if (any_opac) {
+                // hidden by its xform's opacity: not plotted — the "no tile" bin, no add and no roulette draw — and counted as dropped,
+                // before the frame bounds are looked at
+                const bool hidden = (__float_as_uint(cf) >> 31) != 0u;
+                if (COUNT) { n_drop += hidden; n_oob += !hidden & !ok; }
+                ok &= !hidden;
+            } else if (COUNT) n_oob += !ok;
+        } else
         if (COUNT) n_oob += !ok;
         const uint32_t gi = ok ? iy * astride + ix : 0u;
 
@@ -646,7 +702,11 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             const uint32_t rec = __builtin_amdgcn_perm(t2, cbits, 0x06050400u);
             if (WIDE) skey[staged * NT + tid] = (uint16_t)bin;
             stage[staged * NT + tid] = rec;
-            __hip_atomic_fetch_add(my_cnt + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            // (opacity kernels: a sample without a tile is not counted and, in the sort, not scattered — nothing reads the "no tile" bin's
+            // count or its records, and where most samples are hidden the adds to that ONE address are applied a lane at a time.
+            // Kernels of genomes without opacity keep their code.)
+            if constexpr (OPAC) { if (!any_opac || ok) __hip_atomic_fetch_add(my_cnt + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+            else __hip_atomic_fetch_add(my_cnt + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         } else {
             // measurement mode: everything but the accumulate (ceiling of the walk itself)
             pend_old += ok ? val + gi : 0ull;
@@ -703,6 +763,11 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                 // tile counts), so that the scatter below can sort the batch IN PLACE: no second
                 // R*NT buffer, which is what limits the workgroups per CU.
                 uint32_t r2[FL_BIN_R_MAX], k2[FL_BIN_R_MAX];       // payload, tile (0xffffffff: no record)
+                // (opacity kernels: a sample without a tile was not counted, see plot_rest, and is not scattered)
+                auto has_record = [&](const uint32_t k) __attribute__((always_inline)) -> bool {
+                    if constexpr (OPAC) { if (any_opac && k == bg.nbins) return false; }
+                    return k != 0xffffffffu;
+                };
 #pragma unroll
                 for (int q = 0; q < FL_BIN_R_MAX; ++q) {
                     const bool have = (uint32_t)q < staged;
@@ -777,11 +842,11 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                     uint32_t pos[FL_SCATTER_DEPTH];
 #pragma unroll
                     for (int q = 0; q < FL_SCATTER_DEPTH; ++q)
-                        if (k2[q0 + q] != 0xffffffffu)
+                        if (has_record(k2[q0 + q]))
                             pos[q] = __hip_atomic_fetch_add(my_cnt + k2[q0 + q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
                     for (int q = 0; q < FL_SCATTER_DEPTH; ++q)
-                        if (k2[q0 + q] != 0xffffffffu) stage[pos[q]] = r2[q0 + q] & ((1u << PAY_BITS) - 1u);
+                        if (has_record(k2[q0 + q])) stage[pos[q]] = r2[q0 + q] & ((1u << PAY_BITS) - 1u);
                 }
                 __syncthreads();
                 const uint32_t nvalid = *s_nvalid;

@@ -37,7 +37,7 @@ void launch_apply_xf_tap(hipStream_t st, const int32_t *prog, const float *param
 #include <vector>
 struct IterSpec {
     int nxf = 0, has_final = 0, pstride = 0, cdf_off = 0, xf_off = 0, xf_stride = 0, var_stride = 0;
-    std::vector<int> nvar, post;                 // per record (selectable xforms, then the final xform)
+    std::vector<int> nvar, post, opac;           // per record (selectable xforms, then the final xform): variations, post affine, opacity
     std::vector<std::vector<int>> vids;          // flam3 variation numbers in application order
 };
 bool rtc_available();

@@ -82,6 +82,8 @@ std::string spec_header(const IterSpec &s, int nw, bool count, int acc, uint32_t
     for (int i = 0; i < nrec; ++i) h += std::to_string(s.nvar[i]) + ",";
     h += "0};\nconstexpr int kSpecPost[] = {";
     for (int i = 0; i < nrec; ++i) h += std::to_string(s.post[i]) + ",";
+    h += "0};\nconstexpr int kSpecOpac[] = {";
+    for (int i = 0; i < nrec; ++i) h += std::to_string(i < (int)s.opac.size() ? s.opac[i] : 0) + ",";
     snprintf(buf, sizeof buf, "0};\nconstexpr int kSpecVid[][%d] = {", maxv);
     h += buf;
     for (int i = 0; i < nrec; ++i) {

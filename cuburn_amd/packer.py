@@ -24,7 +24,8 @@ from .genome import variations as V
 
 KNOTS = 32          # 1 << DEFAULT_SEARCH_ROUNDS, cuburn/code/util.py:235
 PROG_MAGIC = 0x464c5032
-OP_SPLINE, OP_SPLINE_MAG, OP_CAMERA, OP_AFFINE, OP_CDF, OP_RATIO2, OP_INVSQ, OP_PERSP, OP_INVSQ_MAX, OP_CONST = range(10)
+OP_SPLINE, OP_SPLINE_MAG, OP_CAMERA, OP_AFFINE, OP_CDF, OP_RATIO2, OP_INVSQ, OP_PERSP, OP_INVSQ_MAX, OP_CONST, OP_OPACITY = range(11)
+XF_HAS_POST, XF_HAS_OPACITY = 1 << 8, 1 << 9      # flags of xform word 14, above the variation count
 MAX_PSTRIDE = 4096
 XF_HDR = 16
 
@@ -83,7 +84,7 @@ class GenomePacker(object):
         self.ops.append((OP_AFFINE, dst, first, 0))
         return first
 
-    def _xform(self, base, xf, rec):
+    def _xform(self, base, xf, rec, selectable=True):
         """Fill the fixed-stride record starting at block offset ``rec`` (include/flame_hip.h (5))."""
         pre_rows = self._affine(base + ('pre_affine',), rec)
         has_post = 1 if 'post_affine' in xf else 0
@@ -95,7 +96,13 @@ class GenomePacker(object):
         self._spline_op(rec + 13, base + ('color_speed',))
         names = sorted(xf.get('variations', {}))
         self.packed[rec + 14] = base + ('#nvar',)
-        self.ops.append((OP_CONST, rec + 14, len(names) | (has_post << 8), 0))
+        # The presence of the key `opacity` on a selectable xform is structure, like `post_affine`: word 15 then holds the
+        # plot probability of the xform's samples, per temporal sample.  (The final xform's opacity is ignored, like its weight.)
+        has_opacity = 1 if selectable and 'opacity' in xf else 0
+        self.ops.append((OP_CONST, rec + 14, len(names) | (has_post * XF_HAS_POST) | (has_opacity * XF_HAS_OPACITY), 0))
+        if has_opacity:
+            self.packed[rec + 15] = base + ('#plot_probability',)
+            self.ops.append((OP_OPACITY, rec + 15, self._row(base + ('opacity',)), 0))
         for j, vname in enumerate(names):
             vbase = base + ('variations', vname)
             voff = rec + XF_HDR + j * self.var_stride
@@ -155,7 +162,7 @@ class GenomePacker(object):
         first = self._new_rows((), [('xforms', k, 'weight') for k in keys])
         self.ops.append((OP_CDF, cdf, first, len(keys)))
         for i, (base, xf) in enumerate(allxf):
-            self._xform(base, xf, self.xf_off + i * self.xf_stride)
+            self._xform(base, xf, self.xf_off + i * self.xf_stride, selectable=i < len(keys))
         self._prog = [PROG_MAGIC, len(keys), has_final, 0, cdf, self.xf_off, self.xf_stride, self.var_stride]
 
     # ------------------------------------------------------------------ per-frame data

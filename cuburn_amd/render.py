@@ -8,6 +8,7 @@ in libflame_hip.so through the C ABI of include/flame_hip.h.
 """
 import ctypes as C
 import os
+import warnings
 import weakref
 from collections import namedtuple
 
@@ -272,6 +273,11 @@ class Renderer(object):
 
     def __init__(self, gnm, gprof, keep=False, arch=None):
         self.packer, self.lib, self.cubin = self.compile(gnm, keep=keep, arch=arch)
+        # (xform opacity is honoured for the selectable xforms; the final xform draws nothing of its own)
+        fop = gnm.get('final_xform', {}).get('opacity', 1)
+        if not (isinstance(fop, (int, float)) and fop == 1):
+            warnings.warn('final_xform.opacity is ignored (like its weight): the final xform is applied to every plotted sample',
+                          UserWarning, stacklevel=2)
         self.mod = None          # device handle, created on first use by a RenderManager
         self._mod_key = None
         self.filts = filters.create(gprof)

@@ -89,7 +89,12 @@ typedef struct fl_mwc {
  *         [0..5]  pre affine xx,xy,xo,yx,yy,yo (cuburn/code/iter.py:81-95)
  *         [6..11] post affine (same six; unused unless the flag below says so)
  *         [12] color   [13] color_speed
- *         [14] INT: nvar | (has_post << 8)      [15] reserved
+ *         [14] INT: nvar | (has_post << 8) | (has_opacity << 9)
+ *         [15] plot probability q of the xform's samples (FL_OP_OPACITY below); read only where bit 9 of [14] is
+ *              set, selectable xforms only.  A sample produced by the xform in a write-enabled round is plotted
+ *              with probability q and hidden otherwise; the walk goes on from it either way.  q == 1 and q == 0
+ *              draw no random number for the decision, 0 < q < 1 draws one (u = next uniform in [0, 1], plotted
+ *              iff u <= q) right after the xform.  Programs without bit 9 run exactly as before.
  *         variation j (sorted-name order, cuburn/code/iter.py:132) at 16 + j * var_stride:
  *           [0] INT flam3 variation number (cuburn/genome/variations.py:28-127)
  *           [1] weight   [2..] the variation's genome parameters in sorted-name order,
@@ -121,7 +126,10 @@ enum {
     FL_OP_PERSP = 7,      /* dst[0..2] <- mdist, sin, cos; row a = angle, row b = dist(mag)
                              (variations.py:267-273)                                     */
     FL_OP_INVSQ_MAX = 8,  /* dst <- 1/max(1e-20, v*v), v = row a (mag)  (curve, variations.py:630-634) */
-    FL_OP_CONST = 9       /* dst <- the 32 bits of a (structure words: variation numbers, counts) */
+    FL_OP_CONST = 9,      /* dst <- the 32 bits of a (structure words: variation numbers, counts) */
+    FL_OP_OPACITY = 10    /* dst <- q(p), p = clamp(row a (mag), 0, 1): q = 0 for p <= 0, 1 for p >= 1 - 1e-6, else
+                             10^(log2 p) = p^3.3219281 (flam3's visibility curve), flushed to 0 below 2^-32.
+                             dst must be word 15 of a selectable xform record whose word 14 has bit 9 */
 };
 
 /* ------------------------------------------------------------------------------------
@@ -318,7 +326,10 @@ int fl_debug_apply_xf(fl_ctx *ctx, fl_genome *g, uint32_t ts, int xfi, uint32_t 
  * count: bit 0 = the sample counters, bit 1 = a temporal sample per four waves (nw = 8 / 16: two / four per workgroup). */
 int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops, int nw, int count, int acc,
                          char *log, size_t log_bytes);
-/* Counters of the last iterate: accepted (written) samples, out-of-frame, roulette-dropped, spills. */
+/* Counters of the last iterate: accepted (written) samples, out-of-frame, dropped, spills.  "Dropped" are the samples thinned
+ * by the hot-pixel roulette (atomic accumulate) and the samples hidden by their xform's opacity; a hidden sample is counted
+ * there and nowhere else (it is tested before the frame bounds), so accepted + out-of-frame + dropped is the number of
+ * write-enabled samples run. */
 int fl_debug_counters(fl_ctx *ctx, uint64_t out4[4]);
 
 /* ---- run-time switches (environment; read when a context is created / a kernel is first launched) ----
