@@ -2,7 +2,8 @@
 GPU parity tests: the HIP path (through the C ABI of libflame_hip.so) against the CPU oracle.
 
 Bit-exact: RNG-driven integer work (shuffle permutation, packed palette, packed histogram of a
-flame without transcendentals, flush + hot flags, output dither).  Tolerance (stated per test):
+flame without transcendentals, flush + hot flags, output dither — at 200 x 120 here, below one pixel
+per dither state; tests/test_gpu_output.py has the sizes at which a state serves many).  Tolerance (stated per test):
 float parameter preparation and every filter.  Distributional: histograms of flames whose
 variations use hardware transcendentals.
 """
