@@ -469,8 +469,15 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     do {        // a failure anywhere frees what exists so far (fl_genome_destroy tolerates a partial genome)
         if ((e = hipMalloc(&g->d_prog, 4 * nprog))) break;
         if ((e = hipMalloc(&g->d_ops, 16 * nops))) break;
-        if ((e = hipMalloc(&g->d_times, 4 * (size_t)nrows * FL_KNOTS))) break;
-        if ((e = hipMalloc(&g->d_knots, 4 * (size_t)nrows * FL_KNOTS))) break;
+        // One spare row behind the table, padding (times 1e9, knots 0) written once here and never by fl_genome_upload: a row
+        // of FL_KNOTS real knots evaluated after its last-but-one reads word FL_KNOTS, the first of the following row
+        // (catmull_rom, times[idx + 2]; include/flame_hip.h (4)), and behind the LAST row that word must exist.
+        const size_t table = 4 * (size_t)nrows * FL_KNOTS;
+        const std::vector<float> pad_times(FL_KNOTS, 1e9f);
+        if ((e = hipMalloc(&g->d_times, table + 4 * FL_KNOTS))) break;
+        if ((e = hipMalloc(&g->d_knots, table + 4 * FL_KNOTS))) break;
+        if ((e = hipMemcpy((char *)g->d_times + table, pad_times.data(), 4 * FL_KNOTS, hipMemcpyHostToDevice))) break;
+        if ((e = hipMemset((char *)g->d_knots + table, 0, 4 * FL_KNOTS))) break;
         if ((e = hipMalloc(&g->d_ptimes, 4 * FL_KNOTS))) break;
         if ((e = hipMalloc(&g->d_pals, 16 * 256 * FL_KNOTS))) break;
         if ((e = hipMemcpy(g->d_prog, prog, 4 * nprog, hipMemcpyHostToDevice))) break;

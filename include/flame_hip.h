@@ -57,7 +57,11 @@ typedef struct fl_mwc {
  *
  * (4) Spline rows — cuburn/code/interp.py:207-232 (GenomePacker.pack): per genome
  *     parameter one row of FL_KNOTS (=32) knot times (padded 1e9) and FL_KNOTS knot
- *     values; normalisation per cuburn/genome/use.py:129-158.
+ *     values; normalisation per cuburn/genome/use.py:129-158.  The evaluation reads the two knots either side of the
+ *     sample (interp.py:326-334), so a row of all 32 real knots evaluated after its 31st takes its fourth support point
+ *     (time and value) from word 0 of the FOLLOWING row, as the reference does; behind the last row the library keeps one
+ *     row of padding (1e9 / 0) of its own, so the last row takes it from there.  Rows of up to 31 knots never leave
+ *     themselves.
  */
 #define FL_KNOTS 32
 #define FL_NTEMPORAL 1024   /* cuburn/render.py:207 ntemporal_samples = the minimum number of temporal samples here: one per
