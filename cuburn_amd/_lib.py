@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('FLAME_HIP_LIB', LIB_PATH)
 FILT = dict(yuv=0, bilateral=1, logscale=2, colorclip=3, smearclip=4, haloclip=5, plainclip=6, logencode=7, de=8)
 BUF = dict(front=0, back=1, params=2, palette=3, points=4, seeds=5, atom=6, hot=7, side=8)
 ACCUM_ATOMIC, ACCUM_BINNED = 0, 1
+FL_OP_CHAOS_CDF = 11                # include/flame_hip.h (6): dst[0..nxf-1] <- row of the chaos matrix (xaos)
 FL_OP_OPACITY = 10                  # include/flame_hip.h (6): dst <- plot probability of the xform's samples
 OUT = dict(rgba8=0, rgba16=1, yuv444p=2, yuv444p10=3, yuv420p10=4, yuv444p12=5)     # include/flame_hip.h FL_OUT_*
 

@@ -377,6 +377,11 @@ static int check_prog(const int32_t *p, uint32_t n)
     REQUIRE(cdf >= 6 && cdf + nxf <= xo, "bad cdf offset");
     REQUIRE(xs >= FL_XF_HDR + vs && (xs % 4) == 0 && vs >= 2 && vs <= 64, "bad record strides");
     REQUIRE(xo + (nxf + hf) * xs <= ps, "xform records exceed the block");
+    if (n > FL_PROG_HDR) {      // a chaos program: word 8 = block offset of the nxf x nxf matrix, behind the records
+        const int co = p[FL_PROG_HDR];
+        REQUIRE(nxf <= FL_CHAOS_MAX_XFORMS, "too many xforms for a genome with chaos");
+        REQUIRE(co >= xo + (nxf + hf) * xs && co <= ps && nxf * nxf <= ps - co, "bad chaos offset");
+    }
     return FL_OK;
 }
 
@@ -396,9 +401,11 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     uint32_t ps = prog[3];
     const int xo = prog[5], xs = prog[6], vs = prog[7], nrec = prog[1] + prog[2];
     std::vector<int> nvar_seen(nrec, -1), opac_seen(nrec, 0), opac_ops(nrec, 0);
+    const bool has_chaos = nprog > FL_PROG_HDR;
+    std::vector<int> chaos_ops(has_chaos ? prog[1] : 0, 0);
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;
-        REQUIRE(o[0] >= FL_OP_SPLINE && o[0] <= FL_OP_OPACITY, "bad op kind");
+        REQUIRE(o[0] >= FL_OP_SPLINE && o[0] <= FL_OP_CHAOS_CDF, "bad op kind");
         REQUIRE(o[1] >= 0 && (uint32_t)o[1] < ps, "op destination out of range");
         if (o[0] != FL_OP_CONST) {
             // every word an op writes and every spline row it reads must lie inside the block / row table
@@ -411,6 +418,15 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
                 ndst = nsrc = (uint32_t)o[3];
                 break;
             case FL_OP_PERSP: ndst = 3; break;
+            case FL_OP_CHAOS_CDF: {     // row p of the chaos matrix, from the nxf weight rows and nxf chaos rows
+                REQUIRE(has_chaos, "chaos op in a program without a chaos matrix");
+                const int nx = prog[1], rel = o[1] - prog[FL_PROG_HDR];
+                REQUIRE(o[3] >= 0 && (o[3] & 0xff) == nx, "bad chaos row length");
+                REQUIRE(rel >= 0 && rel < nx * nx && rel % nx == 0, "chaos op must write a row of the chaos matrix");
+                REQUIRE((uint32_t)(o[3] >> 8) + (uint32_t)nx <= nrows, "op row out of range");
+                ++chaos_ops[rel / nx];
+                ndst = nsrc = (uint32_t)nx;
+            } break;
             default: break;
             }
             REQUIRE((uint32_t)o[1] + ndst <= ps, "op destination out of range");
@@ -440,10 +456,12 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     }
     for (int i = 0; i < nrec; ++i) REQUIRE(nvar_seen[i] >= 0, "xform record without a variation count");
     for (int i = 0; i < nrec; ++i) REQUIRE(opac_ops[i] == opac_seen[i], "opacity flag and opacity op do not match");
+    for (int n : chaos_ops) REQUIRE(n == 1, "every row of the chaos matrix needs exactly one chaos op");
     // structure tables for the specialised kernel: counts / post flags / variation numbers per record
     IterSpec spec;
     spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
     spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
+    spec.chaos = has_chaos ? 1 : 0; spec.chaos_off = has_chaos ? prog[FL_PROG_HDR] : 0;
     spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>());
     for (int i = 0; i < nrec; ++i) spec.vids[i].assign(nvar_seen[i], -1);
     for (uint32_t i = 0; i < nops; ++i) {
@@ -661,12 +679,12 @@ static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nro
         launch_iter_fn(L(c).stream, fn, c->nw, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
                        L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
                        tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
-                       e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2);
+                       e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0);
     else
     launch_iter(L(c).stream, c->nw, count, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
                 L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
                 tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
-                e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2);
+                e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0);
     c->round_counter += nrounds;
     HIPCHK(hipGetLastError());
     if (acc == FL_ACCUM_BINNED) {
@@ -1248,6 +1266,7 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
     IterSpec spec;
     spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
     spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
+    spec.chaos = nprog > FL_PROG_HDR ? 1 : 0; spec.chaos_off = spec.chaos ? prog[FL_PROG_HDR] : 0;
     spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>(16, 0));
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;

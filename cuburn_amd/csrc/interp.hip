@@ -126,6 +126,21 @@ k_interp_params(float *__restrict__ params, const float *__restrict__ times, con
             if (q < 2.3283064e-10f) q = 0.0f;                  // 2^-32: below the resolution of the draw
             o[0] = p <= 0.0f ? 0.0f : p >= 1.0f - 1.0e-6f ? 1.0f : q;
         } break;
+        case FL_OP_CHAOS_CDF: {         // row p of the chaos matrix (cuburn/code/iter.py:32-54, precalc_chaos): FL_OP_CDF over w_n * max(c_pn, 0)
+            const int n = op.w & 0xff, crow = op.w >> 8;
+            float sum = 0.0f;
+            for (int k = 0; k < n; ++k) sum += ROW(op.z + k, false) * fmaxf(ROW(crow + k, false), 0.0f);
+            const bool plain = !(sum > 0.0f);      // no permitted successor: the plain weights
+            if (plain) { sum = 0.0f; for (int k = 0; k < n; ++k) sum += ROW(op.z + k, false); }
+            float rsum = 1.0f / sum;
+            sum = 0.0f;
+            for (int k = 0; k < n; ++k) {
+                const float wk = ROW(op.z + k, false);
+                sum += (plain ? wk : wk * fmaxf(ROW(crow + k, false), 0.0f)) * rsum;
+                o[k] = sum;
+            }
+            o[n - 1] = 2.0f;
+        } break;
         default: break;
         }
     }

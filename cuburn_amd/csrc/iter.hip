@@ -81,6 +81,18 @@ __device__ __forceinline__ void opacity_mark(const bool has, const float q, floa
     c = __uint_as_float((__float_as_uint(c) & 0x7fffffffu) | hid);
 }
 
+// Xaos (include/flame_hip.h (5), "chaos"): the lane's own choice of its next xform from a cumulative row — the plain densities after a
+// reseed, row p of the chaos matrix behind xform p.  One draw; the smallest n with u <= row[n], else n - 1 (the row's last word is 2).
+// The row is wave-uniform wherever this is called (inside the arm of xform p, p uniform): scalar loads, and nxf - 1 vector compares
+// against scalar operands — no LDS table and no per-lane gather.
+__device__ __forceinline__ uint32_t chaos_pick(const float *__restrict__ row, const int n, mwc_t &r)
+{
+    const float u = mwc_next_01(r);
+    uint32_t k = (uint32_t)(n - 1);
+    for (int i = n - 2; i >= 0; --i) if (u <= row[i]) k = (uint32_t)i;
+    return k;
+}
+
 // cuburn/code/iter.py:121-149: pre affine, sum of variations, optional post affine, colour
 // blend.  The record is wave-uniform; `h` was loaded a round ahead (its choice depends only on
 // the RNG), so the s_load latency of the record is off the critical path; only parameters of
@@ -204,7 +216,7 @@ struct XfVec { float xo, yo, cprod, pxo, pyo; };
 // them in a 16-byte-per-xform LDS table {x offset, y offset, 1 - colour speed, colour * speed}, filled once per launch, and read the entry of the
 // NEXT round's xform (chosen a round ahead) behind the swap: one address instruction and one ds_read_b128 per round instead of the two v_mov of
 // the affine and the v_sub + v_mov + v_mul of the colour blend.
-constexpr bool kTab = !kSpecResident && FL_HOIST_BUDGET >= 12 && FL_SPEC_NXF * 16 <= FL_XTAB_BYTES;
+constexpr bool kTab = !kSpecResident && FL_HOIST_BUDGET >= 12 && FL_SPEC_NXF * 16 <= FL_XTAB_BYTES && FL_SPEC_CHAOS == 0;      // (chaos kernels: no record is chosen a round ahead)
 template <int I, class Extra>
 __device__ __forceinline__ void spec_apply_xf_tab(const XfHead &h, const float4 &t, const float *__restrict__ xf,
                                                   float &x, float &y, float &c, mwc_t &r, const XfTail *tl, Extra &&extra)
@@ -266,6 +278,14 @@ __device__ __forceinline__ void spec_dispatch_res(int k, const XfHead (&heads)[F
         if (k < MID) spec_dispatch_res<LO, MID>(k, heads, hv, xf0, xf_stride, x, y, c, r, tails, extra);
         else spec_dispatch_res<MID, HI>(k, heads, hv, xf0, xf_stride, x, y, c, r, tails, extra);
     }
+}
+
+// chaos kernels: f(SpecIdx<I>) for every selectable xform in order (the arms of the divergent walk, see iter_body)
+template <int I> struct SpecIdx { static constexpr int v = I; };
+template <int I, class F>
+__device__ __forceinline__ void spec_each_xf(F &&f)
+{
+    if constexpr (I < FL_SPEC_NXF) { f(SpecIdx<I>{}); spec_each_xf<I + 1>(f); }
 }
 
 // wave-uniform dispatch over the selectable xforms [LO, HI): a binary tree of scalar compares
@@ -340,7 +360,9 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t) {
 // ACC: 0 = packed global atomics, 1 = binned (sample log, 128x64 tiles, tile number inside the staged
 // record), 2 = none (measurement of the walk), 3 = binned for images with more than 2047 tiles
 // (256x64 tiles, tile numbers staged in a separate 16-bit array)
-template <int NW, bool COUNT, int ACC, bool SPEC>
+// CHAOS: the second form of the walk (xaos) — every lane carries the index of its own next xform, and a wave runs the arm of every
+// xform present among its lanes under that xform's lane mask (contract: include/flame_hip.h (5); DESIGN.md §4.1 "Xaos")
+template <int NW, bool COUNT, int ACC, bool SPEC, bool CHAOS = false>
 __device__ __forceinline__ void
 iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__restrict__ params,
           const u64 *__restrict__ palette, fl_mwc *__restrict__ rng, float4 *__restrict__ points,
@@ -356,9 +378,10 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     constexpr uint32_t TWL = WIDE ? FL_TILE_W_WIDE_LOG2 : 7u;          // log2 of the tile width
     constexpr uint32_t PAY_BITS = TWL + FL_TILE_H_LOG2 + 8u;          // row | column | palette column
     // all LDS is carved from the dynamic region (16-byte aligned pieces)
-    float (*swp)[3][NT] = reinterpret_cast<float (*)[3][NT]>(smem);                    // [2][3][NT]
-    u64 *palrow = reinterpret_cast<u64 *>(smem + 2 * 3 * NT * 4);                      // [256]   (not binned)
-    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + 2 * 3 * NT * 4);             // [R*NT]  (binned)
+    constexpr int PL = CHAOS ? 4 : 3;                                                  // planes of the swap: x, y, colour (chaos kernels: + the next xform)
+    float (*swp)[PL][NT] = reinterpret_cast<float (*)[PL][NT]>(smem);                  // [2][PL][NT]
+    u64 *palrow = reinterpret_cast<u64 *>(smem + 2 * PL * NT * 4);                     // [256]   (not binned)
+    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + 2 * PL * NT * 4);            // [R*NT]  (binned)
     uint16_t *skey = reinterpret_cast<uint16_t *>(stage + bg.rounds * NT);             // [R*NT]  (wide only)
     uint32_t *cnt = stage + bg.rounds * NT + (WIDE ? bg.rounds * NT / 2 : 0);          // [B+1]
     // SETS sets of tile counters, lane l uses set l % SETS: the lanes of a wave hit few
@@ -397,6 +420,12 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     const int nxf = prog[1], has_final = prog[2], pstride = prog[3], cdf_off = prog[4];
     const int xf_off = prog[5], xf_stride = prog[6], var_stride = prog[7];
 #endif
+    int chaos_off = 0;                                  // (8-word programs have no word 8)
+#ifdef FL_RTC
+    if constexpr (CHAOS) chaos_off = SPEC ? FL_SPEC_CHAOS_OFF : prog[8];
+#else
+    if constexpr (CHAOS) chaos_off = prog[8];
+#endif
     const float *__restrict__ P = params + (size_t)ts * pstride;
 
     if (!BINNED) for (int i = tid; i < FL_PAL_W; i += NT) palrow[i] = palette[prow * FL_PAL_W + i];
@@ -408,8 +437,17 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     float4 pt = points[wi];
     float x = pt.x, y = pt.y, color = pt.z;
 
+    // chaos kernels: the walker's next xform persists in points[].w as a float.  The buffer may last have served a genome with
+    // more xforms, or a keyless one: clamped to [0, nxf - 1], not finite counts as 0 — an index past the records never reaches an address.
+    uint32_t nx = 0u;
+    if constexpr (CHAOS) { const float wf = isfinite(pt.w) ? fminf(fmaxf(pt.w, 0.0f), (float)(nxf - 1)) : 0.0f; nx = (uint32_t)wf; }
+    // (... and a reseeded walker has no previous xform: one more draw picks its next from the plain densities)
+
     const float color_dither = 0.49f * mwc_next_11(rctx);                   // iter.py:185
-    if (!isfinite(fabsf(x) + fabsf(y))) reseed(x, y, color, rctx);          // iter.py:209-216
+    if (!isfinite(fabsf(x) + fabsf(y))) {                                   // iter.py:209-216
+        reseed(x, y, color, rctx);
+        if constexpr (CHAOS) nx = chaos_pick(P + cdf_off, nxf, rctx);
+    }
     __syncthreads();
     // camera and final xform are constant for the slot
     const float cam0 = P[0], cam1 = P[1], cam3 = P[3], cam4 = P[4];
@@ -470,7 +508,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         const unsigned long long le = (__ballot(sel <= thr) & valid_lanes) | (1ull << 63);
         return min((int)__builtin_ctzll(le), nxf - 1);
     };
-    uint32_t sel_next = __builtin_amdgcn_readfirstlane(mwc_next(rctx));
+    uint32_t sel_next = CHAOS ? 0u : __builtin_amdgcn_readfirstlane(mwc_next(rctx));      // (chaos kernels draw no wave selector)
     int k_next = choose(sel_next);
     const float *__restrict__ xf_next = P + xf_off + k_next * xf_stride;
 #ifdef FL_RTC
@@ -543,8 +581,46 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         // raising it only for the swap, gains less: profiles/r03_wave_priority.txt).  In the two-lane frame loop the other
         // lane's kernels already fill those issue slots: the frame time does not move; a single frame gains the 6 %.
         __builtin_amdgcn_s_setprio(2);
-        if (!isfinite(fabsf(x) + fabsf(y))) reseed(x, y, color, rctx);      // iter.py:225-229
+        if (!isfinite(fabsf(x) + fabsf(y))) {                               // iter.py:225-229
+            reseed(x, y, color, rctx);
+            if constexpr (CHAOS) nx = chaos_pick(P + cdf_off, nxf, rctx);
+        }
 
+        if constexpr (CHAOS) {
+            // The divergent walk: the arm of every xform present among the wave's lanes, under that xform's lane mask; inside an arm
+            // the xform is uniform (its record and its chaos row are scalar operands).  The lane's draw for the step after this one
+            // sits inside the arm, behind the opacity decision.  Everything from the swap on is reached with all lanes active again.
+            uint32_t nx_out = nx;
+#ifdef FL_RTC
+            if constexpr (SPEC) {
+                spec_each_xf<0>([&](auto idx) __attribute__((always_inline)) {
+                    constexpr int I = decltype(idx)::v;
+                    if (nx == (uint32_t)I) {
+                        const float *__restrict__ rec = P + xf_off + I * xf_stride;
+                        if constexpr (RESIDENT) spec_apply_xf_res<I>(heads[I], hv[I], rec, x, y, color, rctx, &tails[I]);
+                        else { const XfHead h = load_head(rec); spec_apply_xf<I>(h, rec, x, y, color, rctx); }
+                        nx_out = chaos_pick(P + chaos_off + I * FL_SPEC_NXF, FL_SPEC_NXF, rctx);
+                    }
+                });
+            } else
+#endif
+            {
+                // the interpreter: a loop over the first remaining lane's xform (readfirstlane reads the first ACTIVE lane — the
+                // lanes that have run their arm have left the loop); at most nxf turns
+                bool pending = true;
+                do {
+                    const int p = __builtin_amdgcn_readfirstlane((int)nx);
+                    if ((int)nx == p) {
+                        const float *__restrict__ rec = P + xf_off + p * xf_stride;
+                        const XfHead h = load_head(rec);
+                        apply_xf(h, rec, var_stride, x, y, color, rctx, any_opac);
+                        nx_out = chaos_pick(P + chaos_off + p * nxf, nxf, rctx);
+                        pending = false;
+                    }
+                } while (pending);
+            }
+            nx = nx_out;
+        } else {
         const int k_cur = k_next;
         const float *__restrict__ xf_cur = xf_next;
 #ifdef FL_RTC
@@ -572,12 +648,15 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         }
 #endif
         (void)k_cur; (void)xf_cur;
+        }
 
         // rotate walkers between waves (iter.py:274-294), double-buffered by round parity
         {
             swp[par][0][dst] = x; swp[par][1][dst] = y; swp[par][2][dst] = color;
+            if constexpr (CHAOS) swp[par][PL - 1][dst] = __uint_as_float(nx);       // the sample carries its next xform
             __syncthreads();
             x = swp[par][0][tid]; y = swp[par][1][tid]; color = swp[par][2][tid];
+            if constexpr (CHAOS) nx = __float_as_uint(swp[par][PL - 1][tid]);
             if constexpr (OPAC) if (any_opac) { hid_bits = __float_as_uint(color); color = fabsf(color); }      // the hidden bit came with the point (opacity_mark)
 #ifdef FL_RTC
             if constexpr (SPEC && kTab) tcur = xtab[half * 16u + k_next];          // the next round's operands: on their way while this round plots
@@ -621,7 +700,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         }
     };
 #ifdef FL_RTC
-    constexpr bool MERGE = BINNED && SPEC && SPLIT_FUSE && FL_SPEC_NXF <= FL_ITER_MERGE_MAX_XF;
+    constexpr bool MERGE = BINNED && SPEC && SPLIT_FUSE && FL_SPEC_NXF <= FL_ITER_MERGE_MAX_XF && !CHAOS;      // (chaos: no single block to ride in)
 #else
     constexpr bool MERGE = false;
 #endif
@@ -891,7 +970,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         uint32_t tid_end = threadIdx.x;
         asm volatile("" : "+v"(tid_end));
         const size_t wj = (size_t)slot * NT + tid_end;
-        points[wj] = make_float4(x, y, color, 0.0f);                        // iter.py:414-416
+        points[wj] = make_float4(x, y, color, CHAOS ? (float)nx : 0.0f);    // iter.py:414-416 (chaos kernels: the walker's next xform)
         rng[wj].mul = rctx.mul; rng[wj].state = rctx.state; rng[wj].carry = rctx.carry;
     }
 
@@ -917,14 +996,14 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
 extern "C" __global__ void __launch_bounds__(FL_SPEC_NW * 64) k_iter_spec(FL_ITER_ARGS)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    iter_body<FL_SPEC_NW, FL_SPEC_COUNT != 0, FL_SPEC_ACC, true>(smem, FL_ITER_PASS);
+    iter_body<FL_SPEC_NW, FL_SPEC_COUNT != 0, FL_SPEC_ACC, true, FL_SPEC_CHAOS != 0>(smem, FL_ITER_PASS);
 }
 #else
-template <int NW, bool COUNT, int ACC>
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? 6 : NW == 8 ? 3 : 1) k_iter(FL_ITER_ARGS)
+template <int NW, bool COUNT, int ACC, bool CHAOS = false>
+__global__ void __launch_bounds__(NW * 64, NW == 4 ? (CHAOS ? 5 : 6) : NW == 8 ? 3 : 1) k_iter(FL_ITER_ARGS)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    iter_body<NW, COUNT, ACC, false>(smem, FL_ITER_PASS);
+    iter_body<NW, COUNT, ACC, false, CHAOS>(smem, FL_ITER_PASS);
 }
 
 // Xform tap: apply xform `xfi` of temporal sample `ts` once to n independent points (one per
@@ -994,9 +1073,9 @@ k_flush(u64 *__restrict__ atom, float4 *__restrict__ out, uint32_t *__restrict__
 }
 
 // ---- host-side launchers --------------------------------------------------------------------
-static size_t iter_lds_bytes(int nw, int acc, uint32_t rounds, uint32_t nbins, uint32_t sub_log2)
+static size_t iter_lds_bytes(int nw, int acc, uint32_t rounds, uint32_t nbins, uint32_t sub_log2, bool chaos)
 {
-    size_t nt = (size_t)nw * 64, b = 2 * 3 * nt * 4;
+    size_t nt = (size_t)nw * 64, b = 2 * (chaos ? 4 : 3) * nt * 4;      // (chaos kernels: a fourth plane of the swap, +2 KB per 256 walkers)
     if (acc == 1 || acc == 3) b += (size_t)rounds * nt * (acc == 3 ? 6 : 4) + (nw == 4 ? FL_CNT_SETS : FL_CNT_SETS_BIG) * (size_t)((nbins + 1 + 3) & ~3u) * 4 + 16
              + 128 * 4;      // chunk totals (only the all-waves scan uses them; the operand table sits behind them either way)
     else b += FL_PAL_W * 8;
@@ -1008,17 +1087,19 @@ void launch_iter(hipStream_t st, int nw, bool count, int acc, uint32_t nslots,
                  float4 *points, const uint32_t *hot, u64 *atom, float *out4, u64 *counters,
                  uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
                  uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
-                 uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2)
+                 uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2, bool chaos)
 {
     if (sub_log2 != 0u && (4 << sub_log2) != nw) abort();      // sub-blocks are four waves
     BinGeom bg = {tiles_x, nbins, rounds_per_batch, nbatch_total, sub_log2};
-    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2);
-#define LAUNCH(NW, C, A) do { \
+    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2, chaos);
+#define LAUNCH_X(NW, C, A, X) do { \
         static unsigned long long attr_done = 0; \
-        ensure_max_dynamic_lds((const void *)k_iter<NW, C, A>, attr_done); \
+        ensure_max_dynamic_lds((const void *)k_iter<NW, C, A, X>, attr_done); \
         /* the timing events bracket the kernel itself (recorded by the dispatch packet), not the launch call */ \
-        hipExtLaunchKernelGGL((k_iter<NW, C, A>), dim3(nslots), dim3(NW * 64), lds, st, ev_start, ev_stop, 0, prog, params, palette, \
+        hipExtLaunchKernelGGL((k_iter<NW, C, A, X>), dim3(nslots), dim3(NW * 64), lds, st, ev_start, ev_stop, 0, prog, params, palette, \
         rng, points, hot, atom, out4, counters, astride, aheight, round0, nrounds, fuse, bg, log, dir); } while (0)
+    /* (the chaos form of the walk is an instantiation of its own: programs of 9 words) */
+#define LAUNCH(NW, C, A) do { if (chaos) LAUNCH_X(NW, C, A, true); else LAUNCH_X(NW, C, A, false); } while (0)
 #define LAUNCH_NW(C, A) do { if (nw == 4) LAUNCH(4, C, A); else if (nw == 8) LAUNCH(8, C, A); else LAUNCH(16, C, A); } while (0)
     if (acc == 2) LAUNCH_NW(false, 2);
     else if (acc == 1) { if (count) LAUNCH_NW(true, 1); else LAUNCH_NW(false, 1); }
@@ -1026,6 +1107,7 @@ void launch_iter(hipStream_t st, int nw, bool count, int acc, uint32_t nslots,
     else { if (count) LAUNCH_NW(true, 0); else LAUNCH_NW(false, 0); }
 #undef LAUNCH_NW
 #undef LAUNCH
+#undef LAUNCH_X
 }
 
 void launch_iter_fn(hipStream_t st, hipFunction_t fn, int nw, int acc, uint32_t nslots,
@@ -1033,11 +1115,11 @@ void launch_iter_fn(hipStream_t st, hipFunction_t fn, int nw, int acc, uint32_t 
                     float4 *points, const uint32_t *hot, u64 *atom, float *out4, u64 *counters,
                     uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
                     uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
-                    uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2)
+                    uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2, bool chaos)
 {
     if (sub_log2 != 0u && (4 << sub_log2) != nw) abort();      // sub-blocks are four waves
     BinGeom bg = {tiles_x, nbins, rounds_per_batch, nbatch_total, sub_log2};
-    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2);
+    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2, chaos);
     void *args[] = {&prog, &params, &palette, &rng, &points, &hot, &atom, &out4, &counters, &astride, &aheight,
                     &round0, &nrounds, &fuse, &bg, &log, &dir};
     // (no hipFuncSetAttribute here: that API takes a host function pointer, not a module function; module launches

@@ -24,7 +24,7 @@ void launch_iter(hipStream_t st, int nw, bool count, int acc, uint32_t nslots,
                  uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
                  uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
                  uint32_t *log, uint32_t *dir,
-                 hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, uint32_t sub_log2 = 0);      // sub_log2: 8- / 16-wave workgroups of 2 / 4 temporal samples (iter_body)
+                 hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, uint32_t sub_log2 = 0, bool chaos = false);      // chaos: the program has 9 words (the CHAOS form of the walk); sub_log2: 8- / 16-wave workgroups of 2 / 4 temporal samples (iter_body)
 void launch_flush(hipStream_t st, u64 *atom, float4 *out, uint32_t *hot, uint32_t nbins, bool use_hot);
 void launch_clear_frame(hipStream_t st, float4 *front, u64 *atom, uint32_t *hot, u64 *counters, float4 *points,
                         uint32_t nbins, uint32_t npoints);      // npoints = 0: the walkers are left alone
@@ -37,6 +37,7 @@ void launch_apply_xf_tap(hipStream_t st, const int32_t *prog, const float *param
 #include <vector>
 struct IterSpec {
     int nxf = 0, has_final = 0, pstride = 0, cdf_off = 0, xf_off = 0, xf_stride = 0, var_stride = 0;
+    int chaos = 0, chaos_off = 0;                // a program of 9 words: the CHAOS form of the walk, and its matrix's block offset
     std::vector<int> nvar, post, opac;           // per record (selectable xforms, then the final xform): variations, post affine, opacity
     std::vector<std::vector<int>> vids;          // flam3 variation numbers in application order
 };
@@ -50,7 +51,7 @@ void launch_iter_fn(hipStream_t st, hipFunction_t fn, int nw, int acc, uint32_t 
                     float4 *points, const uint32_t *hot, u64 *atom, float *out4, u64 *counters,
                     uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
                     uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
-                    uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2 = 0);
+                    uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2 = 0, bool chaos = false);
 
 // binned.hip
 void launch_accum_tiles(hipStream_t st, const uint32_t *log, const uint32_t *dir, const u64 *palette,

@@ -77,6 +77,7 @@ std::string spec_header(const IterSpec &s, int nw, bool count, int acc, uint32_t
     DEF("FL_SPEC_CDF_OFF", s.cdf_off); DEF("FL_SPEC_XF_OFF", s.xf_off); DEF("FL_SPEC_XF_STRIDE", s.xf_stride);
     DEF("FL_SPEC_VAR_STRIDE", s.var_stride); DEF("FL_SPEC_NW", nw); DEF("FL_SPEC_COUNT", count ? 1 : 0); DEF("FL_SPEC_ACC", acc);
     DEF("FL_SPEC_SUB_LOG2", sub_log2 != 0u && (4 << sub_log2) == nw ? (int)sub_log2 : 0);
+    DEF("FL_SPEC_CHAOS", s.chaos ? 1 : 0); DEF("FL_SPEC_CHAOS_OFF", s.chaos ? s.chaos_off : 0);      // xaos: the divergent form of the walk (iter.hip CHAOS)
 #undef DEF
     h += "constexpr int kSpecNvar[] = {";
     for (int i = 0; i < nrec; ++i) h += std::to_string(s.nvar[i]) + ",";

@@ -87,7 +87,12 @@ base = {
 node = dict(base, type='node', blend=blend, author=author)
 edge = dict(base, type='edge', author=author, blend=blend, link=link,
             xforms=dict(src=map_(xform), dst=map_(xform)))
-anim = dict(base, type='animation', authors=list_(author), link=link)
+# Animations only: `chaos` (flam3 xaos), a map from target xform key to the factor on that xform's weight for the step that
+# follows this one.  A missing entry is 1, negative values count as 0.  Nodes and edges do not know the key: blending two
+# tables is not defined (genome/store.py moves a node's table onto its animation).
+anim_xform = dict(xform, chaos=map_(spline(1, 0)))
+anim = dict(base, type='animation', authors=list_(author), link=link,
+            xforms=map_(anim_xform), final_xform=anim_xform)
 
 default_filters = ['bilateral', 'logscale', 'smearclip']
 

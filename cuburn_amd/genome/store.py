@@ -6,6 +6,7 @@ One class; it offers the ``get(id)`` that edge blending uses to follow an edge's
 nodes (cuburn/genome/blend.py), plus ``animation(name)`` for callers that want something
 renderable whatever the stored type is.
 """
+import copy
 import json
 import os
 import warnings
@@ -55,12 +56,75 @@ class GenomeStore(object):
                 stem = os.path.basename(name)
         kind = genome.get('type')
         if kind == 'node':
-            genome = convert.node_to_anim(self, genome, half=half)
+            # `chaos` (flam3 xaos) is an animation-only key (genome/specs.py): it is taken off the node, and put onto the loop of
+            # the node against itself, whose xform `k` is `k_k` (natural sort)
+            genome, tables = _take_chaos(genome)
+            genome = convert.node_to_anim(_NoChaos(self), genome, half=half)
+            _put_chaos(genome, tables)
         elif kind == 'edge':
-            genome = convert.edge_to_anim(self, genome)
+            genome, tables = _take_chaos(genome)
+            if tables:
+                warnings.warn('chaos is dropped from edges: blending two xaos tables is not defined', UserWarning, stacklevel=2)
+            genome = convert.edge_to_anim(_NoChaos(self), genome)
         elif kind != 'animation':
             raise ValueError('unrecognised genome type %r' % kind)
         return genome, stem
+
+
+def _xform_dicts(genome):
+    """(path, xform dict) of every xform of a node or edge: 'xforms.<k>', 'xforms.src.<k>', 'final_xform'."""
+    xfs = genome.get('xforms', {})
+    if genome.get('type') == 'edge':
+        groups = [('xforms.' + side, xfs.get(side, {})) for side in ('src', 'dst')]
+    else:
+        groups = [('xforms', xfs)]
+    out = [(base + '.' + str(k), xf) for base, grp in groups if isinstance(grp, dict) for k, xf in grp.items()]
+    out.append(('final_xform', genome.get('final_xform')))
+    return [(p, xf) for p, xf in out if isinstance(xf, dict)]
+
+
+def _take_chaos(genome):
+    """A copy of a node or edge without its `chaos` tables, and the tables by xform path."""
+    tables = dict((p, xf['chaos']) for p, xf in _xform_dicts(genome) if 'chaos' in xf)
+    if not tables:
+        return genome, tables
+    genome = copy.deepcopy(genome)
+    for _, xf in _xform_dicts(genome):
+        xf.pop('chaos', None)
+    return genome, tables
+
+
+def _put_chaos(anim, tables):
+    """Tables of a node onto the animation of that node against itself: xform `k` -> `k_k`, target `n` -> `n_n`.  Only where
+    every xform of the node became `k_k` (what the natural sort of a node against itself gives); otherwise dropped, loudly."""
+    if not tables:
+        return
+    xfs = anim.get('xforms', {})
+    keys = set(str(n) for p, t in tables.items() if p != 'final_xform' for n in t) | set(
+        p.split('.', 1)[1] for p in tables if p != 'final_xform')
+    if not all('%s_%s' % (k, k) in xfs for k in keys):
+        warnings.warn('chaos is dropped: the xforms of the node did not pair with themselves', UserWarning, stacklevel=3)
+        return
+    for p, t in tables.items():
+        tab = dict(('%s_%s' % (n, n), v) for n, v in t.items())
+        if p == 'final_xform':
+            anim['final_xform']['chaos'] = tab
+        else:
+            k = p.split('.', 1)[1]
+            xfs['%s_%s' % (k, k)]['chaos'] = tab
+
+
+class _NoChaos(object):
+    """The store as the blender sees it: nodes it fetches (bases, an edge's ends) come without `chaos`."""
+
+    def __init__(self, store):
+        self.store = store
+
+    def get(self, ident):
+        genome, tables = _take_chaos(self.store.get(ident))
+        if tables:
+            warnings.warn('chaos of %r is dropped: blending xaos tables is not defined' % ident, UserWarning, stacklevel=2)
+        return genome
 
 
 def connect(path):

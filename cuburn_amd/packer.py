@@ -6,7 +6,7 @@ effect of rendering CUDA templates; here the genome's *structure* (which xforms,
 variations, post affines, final xform) is turned into three plain arrays handed to
 libflame_hip (formats: include/flame_hip.h (4)-(6)):
 
-  * ``prog``  int32 xform program interpreted by the iterate kernel,
+  * ``prog``  int32 xform program interpreted by the iterate kernel (8 words; 9 for a genome with chaos),
   * ``ops``   int32 x4 interpolation ops evaluated per temporal sample on device,
   * rows      one spline (32 knot times + 32 knot values) per genome parameter,
               filled per frame by ``pack`` exactly as GenomePacker.pack (interp.py:207-232).
@@ -24,9 +24,10 @@ from .genome import variations as V
 
 KNOTS = 32          # 1 << DEFAULT_SEARCH_ROUNDS, cuburn/code/util.py:235
 PROG_MAGIC = 0x464c5032
-OP_SPLINE, OP_SPLINE_MAG, OP_CAMERA, OP_AFFINE, OP_CDF, OP_RATIO2, OP_INVSQ, OP_PERSP, OP_INVSQ_MAX, OP_CONST, OP_OPACITY = range(11)
+OP_SPLINE, OP_SPLINE_MAG, OP_CAMERA, OP_AFFINE, OP_CDF, OP_RATIO2, OP_INVSQ, OP_PERSP, OP_INVSQ_MAX, OP_CONST, OP_OPACITY, OP_CHAOS_CDF = range(12)
 XF_HAS_POST, XF_HAS_OPACITY = 1 << 8, 1 << 9      # flags of xform word 14, above the variation count
 MAX_PSTRIDE = 4096
+CHAOS_MAX_XFORMS = 32      # FL_CHAOS_MAX_XFORMS: selectable xforms of a genome that has chaos
 XF_HDR = 16
 
 _AFFINE_ROWS = (('angle',), ('spread',), ('magnitude', 'x'), ('magnitude', 'y'), ('offset', 'x'), ('offset', 'y'))
@@ -128,6 +129,19 @@ class GenomePacker(object):
                 elif kind == 'persp':
                     self.ops.append((OP_PERSP, dst, self._row(vbase + (src[0],)), self._row(vbase + (src[1],)))); dst += 3
 
+    @staticmethod
+    def _chaos_tables(xforms, keys):
+        """``{prior key: {target key: spline}}`` of the entries that name an xform of the genome, or None when every one of
+        them is the constant 1 (or absent): such a genome packs exactly as it does without the key."""
+        tables, plain = {}, True
+        for p in keys:
+            tab = xforms[p].get('chaos') or {}
+            tables[p] = dict((str(n), v) for n, v in tab.items() if str(n) in keys)
+            for v in tables[p].values():
+                knots = SplineEval.normalize(list(v) if isinstance(v, (list, tuple)) else v, 1.0)[1]
+                plain = plain and bool(np.all(np.asarray(knots) == 1))
+        return None if plain else tables
+
     def _build(self, gnm):
         xforms = gnm.get('xforms', {})
         keys = sorted(xforms.keys())          # string sort, cuburn/genome/use.py:88-91
@@ -150,6 +164,14 @@ class GenomePacker(object):
         cdf = 6
         self.xf_off = (cdf + len(keys) + 3) // 4 * 4
         total = self.xf_off + len(allxf) * self.xf_stride
+        # chaos (flam3 xaos): an nxf x nxf matrix behind the last record — every other offset keeps its value
+        chaos = self._chaos_tables(xforms, keys)
+        self.chaos_off = None
+        if chaos is not None:
+            if len(keys) > CHAOS_MAX_XFORMS:
+                raise ValueError('a genome with chaos has at most %d selectable xforms (this one: %d)' % (CHAOS_MAX_XFORMS, len(keys)))
+            self.chaos_off = total
+            total += len(keys) * len(keys)
         self.packed = [('pad', str(i)) for i in range(total)]
         # camera
         for i, o in enumerate(_AFFINE_OUT):
@@ -161,9 +183,20 @@ class GenomePacker(object):
             self.packed[cdf + i] = ('den', k)
         first = self._new_rows((), [('xforms', k, 'weight') for k in keys])
         self.ops.append((OP_CDF, cdf, first, len(keys)))
+        weight_rows = first
         for i, (base, xf) in enumerate(allxf):
             self._xform(base, xf, self.xf_off + i * self.xf_stride, selectable=i < len(keys))
         self._prog = [PROG_MAGIC, len(keys), has_final, 0, cdf, self.xf_off, self.xf_stride, self.var_stride]
+        if chaos is not None:
+            # row p of the matrix: the cumulative densities of the step that follows xform p, from the weights and
+            # nxf consecutive rows xforms.p.chaos.n in key order (an absent entry: a default row of 1)
+            n = len(keys)
+            for pi, p in enumerate(keys):
+                for ni, k in enumerate(keys):
+                    self.packed[self.chaos_off + pi * n + ni] = ('chaos', p, k)
+                crow = self._new_rows(('xforms', p, 'chaos'), [(k,) for k in keys])
+                self.ops.append((OP_CHAOS_CDF, self.chaos_off + pi * n, weight_rows, n | (crow << 8)))
+            self._prog.append(self.chaos_off)
 
     # ------------------------------------------------------------------ per-frame data
     def signature(self, gnm):

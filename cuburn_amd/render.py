@@ -278,6 +278,16 @@ class Renderer(object):
         if not (isinstance(fop, (int, float)) and fop == 1):
             warnings.warn('final_xform.opacity is ignored (like its weight): the final xform is applied to every plotted sample',
                           UserWarning, stacklevel=2)
+        # (chaos: the final xform is not selected — its table is ignored; entries that name no xform of the genome are ignored)
+        if gnm.get('final_xform', {}).get('chaos'):
+            warnings.warn('final_xform.chaos is ignored (like its weight and opacity): the final xform is not selected',
+                          UserWarning, stacklevel=2)
+        keys = set(str(k) for k in gnm.get('xforms', {}))
+        for k, xf in gnm.get('xforms', {}).items():
+            unknown = sorted(str(n) for n in (xf.get('chaos') or {}) if str(n) not in keys)
+            if unknown:
+                warnings.warn('xforms.%s.chaos names no xform of the genome: %s (ignored)' % (k, ', '.join(unknown)),
+                              UserWarning, stacklevel=2)
         self.mod = None          # device handle, created on first use by a RenderManager
         self._mod_key = None
         self.filts = filters.create(gprof)

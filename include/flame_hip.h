@@ -87,6 +87,10 @@ typedef struct fl_mwc {
  *       prog[5]  xf_off     block offset of xform record 0
  *       prog[6]  xf_stride  floats per xform record (multiple of 4)
  *       prog[7]  var_stride floats per variation record (>= 2)
+ *     a genome with chaos (flam3 xaos) has a ninth word; programs of 8 words mean what they always meant:
+ *       prog[8]  chaos_off  block offset of an nxf x nxf matrix of floats behind the last xform record (every other
+ *                            offset keeps its value); row p = the cumulative densities of the step that FOLLOWS xform p
+ *                            (FL_OP_CHAOS_CDF below; same form as CDF[nxf], last word 2.0).  nxf <= FL_CHAOS_MAX_XFORMS.
  *     parameter block (32-bit words; floats unless noted):
  *       [0..5]   camera xx,xy,xo,yx,yy,yo (cuburn/code/iter.py:56-79)
  *       xform record i (i = nxf is the final xform) at xf_off + i * xf_stride:
@@ -103,10 +107,23 @@ typedef struct fl_mwc {
  *           [0] INT flam3 variation number (cuburn/genome/variations.py:28-127)
  *           [1] weight   [2..] the variation's genome parameters in sorted-name order,
  *                              then its precalculated values (cuburn_amd/genome/variations.py)
+ *
+ *     Contract of a chaos kernel (programs of 9 words; the CHAOS form of the walk, csrc/iter.hip).  The SAMPLE carries
+ *     the index of its next xform, `next` in [0, nxf): through the swap as a fourth plane of the swap buffer (+2 KB of
+ *     LDS per 256 walkers; kernels of 8-word programs keep their LDS), and between launches and frames in points[].w as
+ *     (float)next (other kernels keep writing 0).  On load it is clamped to nxf - 1 and a non-finite w counts as 0 — the
+ *     buffer may last have served another genome; an index past the records never reaches an address.
+ *     What a lane draws in one round, fuse rounds included, in order: (1) the reseed, three draws, only for a bad point;
+ *     (2) only after a reseed, one draw u that picks `next` from CDF[nxf]; (3) the variations of xform p = next; (4) the
+ *     opacity decision, as above; (5) the chaos draw, one u per lane every round: next = the smallest n with
+ *     u <= row p [n], else nxf - 1; (6) the swap; (7) the final xform; (8) the atomic back-end's roulette.  The wave's
+ *     selector (lane 0's draw of the other kernels) is NOT drawn.  A wave runs the arm of every xform present among its
+ *     lanes under that xform's lane mask; counters, the sort, both accumulate back-ends and the final xform are unchanged.
  */
 #define FL_PROG_MAGIC 0x464c5032 /* 'FLP2' */
 #define FL_PROG_HDR 8
 #define FL_MAX_XFORMS 64
+#define FL_CHAOS_MAX_XFORMS 32 /* selectable xforms of a program with chaos */
 #define FL_MAX_PSTRIDE 4096
 #define FL_XF_HDR 16      /* words of an xform record before its first variation */
 
@@ -131,9 +148,15 @@ enum {
                              (variations.py:267-273)                                     */
     FL_OP_INVSQ_MAX = 8,  /* dst <- 1/max(1e-20, v*v), v = row a (mag)  (curve, variations.py:630-634) */
     FL_OP_CONST = 9,      /* dst <- the 32 bits of a (structure words: variation numbers, counts) */
-    FL_OP_OPACITY = 10    /* dst <- q(p), p = clamp(row a (mag), 0, 1): q = 0 for p <= 0, 1 for p >= 1 - 1e-6, else
+    FL_OP_OPACITY = 10,   /* dst <- q(p), p = clamp(row a (mag), 0, 1): q = 0 for p <= 0, 1 for p >= 1 - 1e-6, else
                              10^(log2 p) = p^3.3219281 (flam3's visibility curve), flushed to 0 below 2^-32.
                              dst must be word 15 of a selectable xform record whose word 14 has bit 9 */
+    FL_OP_CHAOS_CDF = 11, /* dst[0..nxf-1] <- row p of the chaos matrix, dst = chaos_off + p * nxf (programs of 9 words only,
+                             one op per row).  a = the first of the nxf weight rows FL_OP_CDF reads; b = nxf | (r << 8),
+                             r = the first of nxf consecutive rows c_p0 .. c_p,nxf-1 (chaos entries, linear splines).
+                             d_n = w_n * max(c_pn, 0), s = sum d_n; if !(s > 0): d_n = w_n (an xform without a permitted
+                             successor falls back to the plain weights); dst[n] = running sum of d_n * (1 / s) in
+                             float32, FL_OP_CDF's order of operations; dst[nxf-1] = 2 (iter.py:32-54, precalc_chaos) */
 };
 
 /* ------------------------------------------------------------------------------------
