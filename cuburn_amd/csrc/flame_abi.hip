@@ -385,6 +385,34 @@ static int check_prog(const int32_t *p, uint32_t n)
     return FL_OK;
 }
 
+// Structure tables of the per-genome kernel (rtc.hip) from a program and its op list: per record the variation count, post and
+// opacity flags of its structure word (14) and its variation numbers in order (-1: no op names one).  The callers have checked
+// that every FL_OP_CONST writes inside the xform records.
+static IterSpec iter_spec(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops)
+{
+    const int xo = prog[5], xs = prog[6], vs = prog[7], nrec = prog[1] + prog[2];
+    const bool has_chaos = nprog > FL_PROG_HDR;
+    IterSpec spec;
+    spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
+    spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
+    spec.chaos = has_chaos ? 1 : 0; spec.chaos_off = has_chaos ? prog[FL_PROG_HDR] : 0;
+    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>());
+    for (int pass = 0; pass < 2; ++pass)          // the structure words first: they size the variation lists
+        for (uint32_t i = 0; i < nops; ++i) {
+            const int32_t *o = ops + 4 * i;
+            if (o[0] != FL_OP_CONST) continue;
+            const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
+            if (pass == 0 && w == 14) {
+                spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; spec.opac[rec] = (o[2] >> 9) & 1;
+                spec.vids[rec].assign(spec.nvar[rec], -1);
+            } else if (pass == 1 && w != 14) {
+                const int j = (w - FL_XF_HDR) / vs;
+                if (j >= 0 && j < spec.nvar[rec]) spec.vids[rec][j] = o[2];
+            }
+        }
+    return spec;
+}
+
 static bool known_var(int id)
 {
     for (int k : kKnownVars) if (k == id) return true;
@@ -457,25 +485,9 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     for (int i = 0; i < nrec; ++i) REQUIRE(nvar_seen[i] >= 0, "xform record without a variation count");
     for (int i = 0; i < nrec; ++i) REQUIRE(opac_ops[i] == opac_seen[i], "opacity flag and opacity op do not match");
     for (int n : chaos_ops) REQUIRE(n == 1, "every row of the chaos matrix needs exactly one chaos op");
-    // structure tables for the specialised kernel: counts / post flags / variation numbers per record
-    IterSpec spec;
-    spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
-    spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
-    spec.chaos = has_chaos ? 1 : 0; spec.chaos_off = has_chaos ? prog[FL_PROG_HDR] : 0;
-    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>());
-    for (int i = 0; i < nrec; ++i) spec.vids[i].assign(nvar_seen[i], -1);
-    for (uint32_t i = 0; i < nops; ++i) {
-        const int32_t *o = ops + 4 * i;
-        if (o[0] != FL_OP_CONST) continue;
-        const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
-        if (w == 14) { spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; spec.opac[rec] = (o[2] >> 9) & 1; }
-        else {
-            const int j = (w - FL_XF_HDR) / vs;
-            if (j < (int)spec.vids[rec].size()) spec.vids[rec][j] = o[2];
-        }
-    }
+    const IterSpec spec = iter_spec(prog, nprog, ops, nops);
     for (int i = 0; i < nrec; ++i)
-        for (int v : spec.vids[i]) REQUIRE(v >= 0, "variation record without a variation number");
+        for (int j = 0; j < spec.nvar[i]; ++j) REQUIRE(spec.vids[i][j] >= 0, "variation record without a variation number");
     HIPCHK(hipSetDevice(c->device));
     fl_genome *g = new fl_genome;
     { static std::atomic<uint64_t> next_serial{1}; g->serial = next_serial.fetch_add(1); }
@@ -609,23 +621,35 @@ static int do_clear(fl_ctx *c, const fl_dim &d, bool reset_points)
 #define FL_BIN_MAX_ROUNDS 1024u
 #define FL_BIN_MAX_ROUNDS_LONG 2304u
 
-static int ensure_binned(fl_ctx *c, const fl_dim &d, uint32_t write_rounds, int buf, uint32_t *tiles_x, uint32_t *nbins,
-                         uint32_t *nbatch_total, bool *wide)
+// Tile geometry of the binned accumulate for one image, and what a batch takes in the sample log.
+struct BinLayout {
+    bool wide;            // 256x64 tiles with separately staged tile numbers (else 128x64)
+    uint32_t tile_w, tiles_x, nbins;
+    size_t region;        // 32-bit words of the log per batch
+};
+static BinLayout bin_layout(const fl_ctx *c, const fl_dim &d)
 {
+    BinLayout b;
     const uint32_t nt = (uint32_t)c->nw * 64;
     // 128x64 tiles while their number fits the 11 bits left in a staged record (up to 4K);
     // larger images use 256x64 tiles with separately staged tile numbers
     const uint32_t rows = (d.ah + FL_TILE_H - 1) / FL_TILE_H;
-    *wide = ((d.astride + 127) / 128) * rows > FL_MAX_BINS || c->env_bin_wide;
-    const uint32_t tw = *wide ? (1u << FL_TILE_W_WIDE_LOG2) : 128u;
-    *tiles_x = (d.astride + tw - 1) / tw;
-    *nbins = *tiles_x * rows;
-    if (*nbins > FL_MAX_BINS_WIDE) return fail(FL_E_UNSUPPORTED, "image too large for the binned accumulate (> 8191 tiles of 256x64)", __FILE__, __LINE__);
+    b.wide = ((d.astride + 127) / 128) * rows > FL_MAX_BINS || c->env_bin_wide;
+    b.tile_w = b.wide ? (1u << FL_TILE_W_WIDE_LOG2) : 128u;
+    b.tiles_x = (d.astride + b.tile_w - 1) / b.tile_w;
+    b.nbins = b.tiles_x * rows;
+    // a region per batch — bin_rounds * nt records, one per word (256x64 tiles) or three per 64-bit word (flame_device.h)
+    b.region = !b.wide && FL_LOG_PACK3 ? 2 * (size_t)fl_pack3_words(c->bin_rounds * nt) : (size_t)c->bin_rounds * nt;
+    return b;
+}
+
+static int ensure_binned(fl_ctx *c, const fl_dim &d, uint32_t write_rounds, int buf, BinLayout *layout, uint32_t *nbatch_total)
+{
+    const BinLayout b = *layout = bin_layout(c, d);
+    if (b.nbins > FL_MAX_BINS_WIDE) return fail(FL_E_UNSUPPORTED, "image too large for the binned accumulate (> 8191 tiles of 256x64)", __FILE__, __LINE__);
     const uint32_t per_slot = (write_rounds + c->bin_rounds - 1) / c->bin_rounds;
     *nbatch_total = per_slot * c->nslots;
-    // 32-bit words of the log: a region per batch — bin_rounds * nt records, one per word (256x64 tiles) or three per 64-bit word (flame_device.h)
-    const size_t region = !*wide && FL_LOG_PACK3 ? 2 * (size_t)fl_pack3_words(c->bin_rounds * nt) : (size_t)c->bin_rounds * nt;
-    size_t lw = (size_t)*nbatch_total * region + 8, dw = (size_t)*nbins * *nbatch_total;
+    size_t lw = (size_t)*nbatch_total * b.region + 8, dw = (size_t)b.nbins * *nbatch_total;
     if (lw > L(c).log_words[buf]) {
         HIPCHK(hipStreamSynchronize(L(c).stream)); HIPCHK(hipStreamSynchronize(L(c).aux));
         hipFree(L(c).d_log[buf]); L(c).d_log[buf] = nullptr; L(c).log_words[buf] = 0;
@@ -648,13 +672,15 @@ static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nro
                           int buf = 0, hipStream_t drain = nullptr)
 {
     if (!drain) drain = L(c).stream;
-    uint32_t tiles_x = 0, nbins = 0, nbatch_total = 0;
-    bool wide = false;
+    BinLayout bl = {};
+    uint32_t nbatch_total = 0;
     if (acc == FL_ACCUM_BINNED) {
         if (nrounds <= fuse) return fail(FL_E_INVAL, "binned launch needs write-enabled rounds", __FILE__, __LINE__);
-        int rc = ensure_binned(c, d, nrounds - fuse, buf, &tiles_x, &nbins, &nbatch_total, &wide);
+        int rc = ensure_binned(c, d, nrounds - fuse, buf, &bl, &nbatch_total);
         if (rc) return rc;
     }
+    const uint32_t tiles_x = bl.tiles_x, nbins = bl.nbins;
+    const bool wide = bl.wide;
     EvPair *e = ev_pair(c, c->iter_ev);
     const int kacc = acc == FL_ACCUM_BINNED && wide ? 3 : acc;
     // the kernel specialised for this genome's structure (compiled on first use, rtc.hip); the
@@ -663,7 +689,9 @@ static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nro
     if (c->use_rtc && !g->rtc_failed && kacc != 2) {
         const unsigned ep = rtc_epoch();
         if (g->rtc_epoch != ep) { memset(g->rtc_fn, 0, sizeof g->rtc_fn); g->rtc_epoch = ep; }     // the module cache was flushed
-        hipFunction_t &slot = g->rtc_fn[c->sub_log2 ? 2 + c->sub_log2 : c->nw == 16 ? 2 : c->nw == 8][count ? 1 : 0][kacc];
+        // the walker geometry's row of rtc_fn: 4 / 8 / 16 waves, 8 in halves, 16 in quarters
+        const int geom = c->sub_log2 ? 2 + (int)c->sub_log2 : c->nw == 16 ? 2 : c->nw == 8 ? 1 : 0;
+        hipFunction_t &slot = g->rtc_fn[geom][count ? 1 : 0][kacc];
         if (!slot) {
             std::string err;
             if (rtc_iter_kernel(c->device, g->spec, c->nw, c->nslots, count, kacc, &slot, &err, c->sub_log2)) {
@@ -675,16 +703,11 @@ static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nro
         fn = slot;
     }
     (fn ? c->n_spec_launch : c->n_interp_launch) += 1;
-    if (fn)
-        launch_iter_fn(L(c).stream, fn, c->nw, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
-                       L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
-                       tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
-                       e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0);
-    else
-    launch_iter(L(c).stream, c->nw, count, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
-                L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
-                tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
-                e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0);
+    const IterLaunch il = {c->nw, count, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
+                           L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
+                           tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
+                           e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0};
+    launch_iter(L(c).stream, il, fn);
     c->round_counter += nrounds;
     HIPCHK(hipGetLastError());
     if (acc == FL_ACCUM_BINNED) {
@@ -756,13 +779,9 @@ int fl_iterate(fl_ctx *c, fl_genome *g, uint32_t w, uint32_t h, double nsamples,
     // would have to be allocated beyond the short cap's buffers fits the device's free memory with a margin — a frame that rendered
     // with 1024-round logs must not start failing on a shared or smaller device because a schedule saves it a flush.
     if (accum_mode == FL_ACCUM_BINNED && !c->launch_rounds && launches_with(cap_long) < launches_with(cap_short)) {
-        const uint32_t nt_ = (uint32_t)c->nw * 64;
-        const bool wide_ = ((d.astride + 127) / 128) * ((d.ah + FL_TILE_H - 1) / FL_TILE_H) > FL_MAX_BINS || c->env_bin_wide;
-        const uint32_t tw_ = wide_ ? (1u << FL_TILE_W_WIDE_LOG2) : 128u;
-        const size_t nbins_ = (size_t)((d.astride + tw_ - 1) / tw_) * ((d.ah + FL_TILE_H - 1) / FL_TILE_H);
-        const size_t region = !wide_ && FL_LOG_PACK3 ? 2 * (size_t)fl_pack3_words(c->bin_rounds * nt_) : (size_t)c->bin_rounds * nt_;
+        const BinLayout bl = bin_layout(c, d);
         const size_t nb_long = (size_t)((std::min(rounds, cap_long) + c->bin_rounds - 1) / c->bin_rounds) * c->nslots;
-        const size_t need = (nb_long * region + 8 + nbins_ * nb_long) * 4;      // one log + directory set, bytes
+        const size_t need = (nb_long * bl.region + 8 + (size_t)bl.nbins * nb_long) * 4;      // one log + directory set, bytes
         size_t have = 0, grow = 0;
         for (int b = 0; b < 2; ++b) {                                            // (two sets: launches of a frame are pipelined)
             have = (L(c).log_words[b] + L(c).dir_words[b]) * 4;
@@ -1262,12 +1281,7 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
     REQUIRE(prog && ops && nprog >= FL_PROG_HDR && (nw == 4 || nw == 8 || nw == 16) && acc >= 0 && acc <= 3, "bad argument");
     int rc = check_prog(prog, nprog);
     if (rc) return rc;
-    const int xo = prog[5], xs = prog[6], vs = prog[7], nrec = prog[1] + prog[2];
-    IterSpec spec;
-    spec.nxf = prog[1]; spec.has_final = prog[2]; spec.pstride = prog[3]; spec.cdf_off = prog[4];
-    spec.xf_off = xo; spec.xf_stride = xs; spec.var_stride = vs;
-    spec.chaos = nprog > FL_PROG_HDR ? 1 : 0; spec.chaos_off = spec.chaos ? prog[FL_PROG_HDR] : 0;
-    spec.nvar.assign(nrec, 0); spec.post.assign(nrec, 0); spec.opac.assign(nrec, 0); spec.vids.assign(nrec, std::vector<int>(16, 0));
+    const int xo = prog[5], xs = prog[6], nrec = prog[1] + prog[2];
     for (uint32_t i = 0; i < nops; ++i) {
         const int32_t *o = ops + 4 * i;
         if (o[0] == FL_OP_OPACITY) {
@@ -1277,12 +1291,10 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
         if (o[0] != FL_OP_CONST) continue;
         const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
         REQUIRE(rel >= 0 && rec < nrec, "structure word outside the xform records");
-        if (w == 14) {
-            REQUIRE((o[2] >> 10) == 0 && (((o[2] >> 9) & 1) == 0 || rec < prog[1]), "bad structure word");
-            spec.nvar[rec] = o[2] & 0xff; spec.post[rec] = (o[2] >> 8) & 1; spec.opac[rec] = (o[2] >> 9) & 1;
-        }
-        else { const int j = (w - FL_XF_HDR) / vs; if (j >= (int)spec.vids[rec].size()) spec.vids[rec].resize(j + 1, 0); spec.vids[rec][j] = o[2]; }
+        if (w == 14) { REQUIRE((o[2] >> 10) == 0 && (((o[2] >> 9) & 1) == 0 || rec < prog[1]), "bad structure word"); }
     }
+    IterSpec spec = iter_spec(prog, nprog, ops, nops);
+    for (std::vector<int> &v : spec.vids) for (int &id : v) if (id < 0) id = 0;      // (a variation without a number compiles as number 0 here; fl_genome_create refuses it)
     std::vector<char> code;
     std::string err;
     rc = rtc_compile(spec, nw, (count & 1) != 0, acc, &code, &err, nullptr, (count & 2) == 0 ? 0u : nw == 8 ? 1u : nw == 16 ? 2u : 0u);

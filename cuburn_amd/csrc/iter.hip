@@ -21,7 +21,10 @@
 // as compile-time tables — the native counterpart of the reference compiling a CUDA module per
 // genome (cuburn/render.py:232-236, cuburn/code/iter.py:559-575): the variation dispatch, the
 // variation loop, the post-affine test and the final-xform test disappear from the round loop.
-// Both builds execute the same arithmetic in the same order (bit-identical results).
+// Both builds execute the same arithmetic in the same order (bit-identical results): an xform is applied in ONE place, xf_apply, for the
+// interpreter, the three per-genome forms (record fetched per round, operand table, resident records), the final xform, the chaos
+// arms and the tap; the forms differ in the view that hands it its operands.  The ahead-of-time build sees a neutral structure (one
+// xform, no variations), so iter_body reads straight through: every choice in it is `if constexpr (SPEC && ...)`.
 #include "variations.h"
 #ifndef FL_RTC
 #include "kernels.h"
@@ -93,39 +96,86 @@ __device__ __forceinline__ uint32_t chaos_pick(const float *__restrict__ row, co
     return k;
 }
 
-// cuburn/code/iter.py:121-149: pre affine, sum of variations, optional post affine, colour
-// blend.  The record is wave-uniform; `h` was loaded a round ahead (its choice depends only on
-// the RNG), so the s_load latency of the record is off the critical path; only parameters of
-// parametric variations and variations beyond the first are loaded on demand.
-__device__ __forceinline__ void apply_xf(const XfHead &h, const float *__restrict__ xf, int var_stride,
-                                         float &x, float &y, float &c, mwc_t &r, const bool any_opac = false)
+// cuburn/code/iter.py:121-149: pre affine, sum of variations, optional post affine, colour blend, opacity decision — THE application
+// of an xform, for every kernel form: the interpreter, the three per-genome forms, the final xform, the chaos arms and the tap.  What
+// differs between them is where the operands come from and what is known at compile time; that is the view V (h: the record's head,
+// in scalar registers; xf: the record, for what lies behind the head):
+//     xo(h) yo(h) pxo(h) pyo(h)    the offsets of the pre and the post affine
+//     kInterp                      the variation run is read from the record at run time (nvar, var_stride), else variations(...)
+//     post(h)                      is there a post affine
+//     kBlend, cmul(h), cadd()      the colour blend's operands 1 - speed and colour * speed, where they are held ready
+//     opacity(h, c, r)             the opacity decision (opacity_mark)
+// The generated code is sensitive to the SHAPE of this: every function with a __restrict__ parameter that `xf` passes through is an
+// alias scope of its own (one level more or less reorders the loads of large kernels), a view member that is a constant at the
+// call site is pruned at inlining time only as a template parameter (TAIL, WALK), and the head's blend and the interpreter's
+// variation loop keep their order against the rest only when spelt here.  tools/iter_codegen_digest.py tells.
+template <class V>
+__device__ __forceinline__ void xf_apply(const XfHead &h, const float *__restrict__ xf, const V &v, float &x, float &y, float &c, mwc_t &r)
 {
-    const int word14 = __float_as_int(h.f[14]);
-    const int nvar = word14 & 0xff;
-    float tx = fmaf(h.f[0], x, fmaf(h.f[1], y, h.f[2]));
-    float ty = fmaf(h.f[3], x, fmaf(h.f[4], y, h.f[5]));
+    float tx = fmaf(h.f[0], x, fmaf(h.f[1], y, v.xo(h)));
+    float ty = fmaf(h.f[3], x, fmaf(h.f[4], y, v.yo(h)));
     float ox = -0.0f, oy = -0.0f;          // -0 + v = v for every v (IEEE): the first variation's add folds away (the CPU model of the tests starts at -0 as well)
-    if (nvar > 0) apply_variation(h.vid0, h.w0, xf + FL_XF_HDR + 2, xf, tx, ty, ox, oy, r);
-    for (int j = 1; j < nvar; ++j) {
-        const float *__restrict__ v = xf + FL_XF_HDR + j * var_stride;
-        apply_variation(__float_as_int(v[0]), v[1], v + 2, xf, tx, ty, ox, oy, r);
-    }
-    if (word14 & 0x100) {
-        const float qx = fmaf(h.f[6], ox, fmaf(h.f[7], oy, h.f[8]));
-        const float qy = fmaf(h.f[9], ox, fmaf(h.f[10], oy, h.f[11]));
+    if constexpr (V::kInterp) {
+        if (v.nvar > 0) apply_variation(h.vid0, h.w0, xf + FL_XF_HDR + 2, xf, tx, ty, ox, oy, r);
+        for (int j = 1; j < v.nvar; ++j) {
+            const float *__restrict__ vv = xf + FL_XF_HDR + j * v.var_stride;
+            apply_variation(__float_as_int(vv[0]), vv[1], vv + 2, xf, tx, ty, ox, oy, r);
+        }
+    } else v.variations(h, xf, tx, ty, ox, oy, r);
+    if (v.post(h)) {
+        const float qx = fmaf(h.f[6], ox, fmaf(h.f[7], oy, v.pxo(h)));
+        const float qy = fmaf(h.f[9], ox, fmaf(h.f[10], oy, v.pyo(h)));
         ox = qx; oy = qy;
     }
-    const float csp = h.f[13];
-    c = fmaf(c, 1.0f - csp, h.f[12] * csp);
-    if (any_opac) opacity_mark((word14 & 0x200) != 0, h.f[15], c, r);      // (the walk's selectable xforms of programs with the flag; the final xform and the tap pass false)
+    // (the empty asm keeps a blend with ready operands in its xform's arm: merged into one v_fmac behind the arms it needs a v_mov of the product in each)
+    if constexpr (V::kBlend) { c = fmaf(c, v.cmul(h), v.cadd()); asm volatile("" : "+v"(c)); }
+    else { const float csp = h.f[13]; c = fmaf(c, 1.0f - csp, h.f[12] * csp); }
+    v.opacity(h, c, r);
     x = ox; y = oy;
 }
 
-#ifdef FL_RTC
+// Every operand from the head: the record is wave-uniform; `h` was loaded a round ahead (its choice depends only on
+// the RNG), so the s_load latency of the record is off the critical path.
+struct XfFromHead {
+    __device__ __forceinline__ float xo(const XfHead &h) const { return h.f[2]; }
+    __device__ __forceinline__ float yo(const XfHead &h) const { return h.f[5]; }
+    __device__ __forceinline__ float pxo(const XfHead &h) const { return h.f[8]; }
+    __device__ __forceinline__ float pyo(const XfHead &h) const { return h.f[11]; }
+    static constexpr bool kBlend = false;          // (no blend of its own: colour and speed from the head)
+};
+// The interpreter: the structure word (14) is read at run time; only parameters of parametric variations and variations
+// beyond the first are loaded on demand.  WALK: a selectable xform of the walk, which has an opacity decision where the program has the
+// flag at all (any_opac); the final xform and the tap have none.
+template <bool WALK>
+struct XfInterp : XfFromHead {
+    static constexpr bool kInterp = true;
+    int word14, nvar, var_stride; bool any_opac;
+    __device__ __forceinline__ XfInterp(const XfHead &h, int var_stride_, bool any_opac_)
+        : word14(__float_as_int(h.f[14])), nvar(word14 & 0xff), var_stride(var_stride_), any_opac(any_opac_) {}
+    __device__ __forceinline__ bool post(const XfHead &) const { return (word14 & 0x100) != 0; }
+    __device__ __forceinline__ void opacity(const XfHead &h, float &c, mwc_t &r) const { if constexpr (WALK) if (any_opac) opacity_mark((word14 & 0x200) != 0, h.f[15], c, r); }
+};
+
 // Structure tables of the genome this translation unit is compiled for (generated header
 // "flame_spec.h": rtc.hip): FL_SPEC_NXF selectable xforms + FL_SPEC_FINAL, per record its number of
 // variations, whether it has a post affine, and its variation numbers in order.
+#ifdef FL_RTC
 #include "flame_spec.h"
+#else
+// the ahead-of-time build: a neutral structure, so that the per-genome templates below are declared in both builds (iter_body
+// instantiates none of them with SPEC == false)
+#define FL_SPEC_NXF 1
+#define FL_SPEC_FINAL 0
+#define FL_SPEC_PSTRIDE 0
+#define FL_SPEC_CDF_OFF 0
+#define FL_SPEC_XF_OFF 0
+#define FL_SPEC_XF_STRIDE 0
+#define FL_SPEC_VAR_STRIDE 0
+#define FL_SPEC_SUB_LOG2 0
+#define FL_SPEC_CHAOS 0
+#define FL_SPEC_CHAOS_OFF 0
+constexpr int kSpecNvar[] = {0, 0}, kSpecPost[] = {0, 0}, kSpecOpac[] = {0, 0}, kSpecVid[][1] = {{0}, {0}};
+#endif
 
 // The early tail (round 5): kernels whose records are fetched per round ask for the ten words behind the record's head — the first
 // variation's parameters and the second one's number and weight — a round ahead, together with the head, instead of at the top of the
@@ -143,47 +193,30 @@ struct VTail {
         return (t && wd >= kTailFirst && wd < kTailFirst + kTailWords) ? t->w[wd - kTailFirst] : p[wd];
     }
 };
-template <int I, int J>
-__device__ __forceinline__ void spec_variations(const float *__restrict__ xf, float w0, float &tx, float &ty,
-                                                float &ox, float &oy, mwc_t &r, const XfTail *tl = nullptr)
-{
-    if constexpr (J < kSpecNvar[I]) {
-        constexpr int B = FL_XF_HDR + J * FL_SPEC_VAR_STRIDE;
-        const VTail v = {xf, tl, B + 2}, vh = {xf, tl, B};
-        apply_variation_body(kSpecVid[I][J], J == 0 ? w0 : vh[1], v, xf, tx, ty, ox, oy, r);
-        spec_variations<I, J + 1>(xf, w0, tx, ty, ox, oy, r, tl);
-    }
-}
-
 // does any selectable xform of this genome have an opacity?  (kernels of genomes without one: every trace of it is compiled out)
 __host__ __device__ constexpr bool spec_any_opac() { for (int i = 0; i < FL_SPEC_NXF; ++i) if (kSpecOpac[i] != 0) return true; return false; }
 constexpr bool kAnyOpac = spec_any_opac();
-// the opacity decision of record I's sample, behind its colour blend (q = word 15 of the head, in a scalar register)
-template <int I>
-__device__ __forceinline__ void spec_opacity(const XfHead &h, float &c, mwc_t &r)
-{
-    if constexpr (kAnyOpac && I < FL_SPEC_NXF) opacity_mark(kSpecOpac[I] != 0, h.f[15], c, r);
-}
 
-// apply_xf with the structure of record I known at compile time (same arithmetic, same order)
-template <int I>
-__device__ __forceinline__ void spec_apply_xf(const XfHead &h, const float *__restrict__ xf,
-                                              float &x, float &y, float &c, mwc_t &r)
-{
-    float tx = fmaf(h.f[0], x, fmaf(h.f[1], y, h.f[2]));
-    float ty = fmaf(h.f[3], x, fmaf(h.f[4], y, h.f[5]));
-    float ox = -0.0f, oy = -0.0f;          // -0 + v = v for every v (IEEE): the first variation's add folds away (the CPU model of the tests starts at -0 as well)
-    spec_variations<I, 0>(xf, h.w0, tx, ty, ox, oy, r);
-    if constexpr (kSpecPost[I] != 0) {
-        const float qx = fmaf(h.f[6], ox, fmaf(h.f[7], oy, h.f[8]));
-        const float qy = fmaf(h.f[9], ox, fmaf(h.f[10], oy, h.f[11]));
-        ox = qx; oy = qy;
+// Record I of the per-genome kernel, its structure known at compile time (same arithmetic, same order), its operands in the head:
+// SpecXf<I, false> is the record fetched per round, and the final xform without hoisted operands.
+template <int I, bool TAIL = true>
+struct SpecXf : XfFromHead {
+    static constexpr bool kInterp = false;
+    const XfTail *tl;
+    // the variation run, variation J onwards (TAIL: the words behind the head come from tl's registers where it holds them)
+    template <int J = 0>
+    __device__ __forceinline__ void variations(const XfHead &h, const float *__restrict__ xf, float &tx, float &ty, float &ox, float &oy, mwc_t &r) const {
+        if constexpr (J < kSpecNvar[I]) {
+            constexpr int B = FL_XF_HDR + J * FL_SPEC_VAR_STRIDE;
+            const VTail v = {xf, TAIL ? tl : nullptr, B + 2}, vh = {xf, TAIL ? tl : nullptr, B};
+            apply_variation_body(kSpecVid[I][J], J == 0 ? h.w0 : vh[1], v, xf, tx, ty, ox, oy, r);
+            variations<J + 1>(h, xf, tx, ty, ox, oy, r);
+        }
     }
-    const float csp = h.f[13];
-    c = fmaf(c, 1.0f - csp, h.f[12] * csp);
-    spec_opacity<I>(h, c, r);
-    x = ox; y = oy;
-}
+    static __device__ __forceinline__ constexpr bool post(const XfHead &) { return kSpecPost[I] != 0; }
+    // the opacity decision of record I's sample, behind its colour blend (q = word 15 of the head, in a scalar register)
+    __device__ __forceinline__ void opacity(const XfHead &h, float &c, mwc_t &r) const { if constexpr (kAnyOpac && I < FL_SPEC_NXF) opacity_mark(kSpecOpac[I] != 0, h.f[15], c, r); }
+};
 
 // Kernels of few xforms keep EVERY xform's record in scalar registers for the whole launch (a slot's parameter block
 // does not change during a launch): the round then neither computes the next record's address nor loads it (three
@@ -211,76 +244,36 @@ constexpr bool kHoistCol = kSpecResident && FL_SPEC_NXF + 2 <= FL_HOIST_BUDGET;
 constexpr bool kHoistAff = kHoistCol && 3 * FL_SPEC_NXF + 2 <= FL_HOIST_BUDGET;
 constexpr bool kHoistPost = kHoistAff && 3 * FL_SPEC_NXF + 2 + 2 * spec_npost() <= FL_HOIST_BUDGET;
 struct XfVec { float xo, yo, cprod, pxo, pyo; };
-// spec_apply_xf for a resident record: h.f[13] holds 1 - colour speed, v the vector-register copies
+// A resident record: h.f[13] holds 1 - colour speed, v the vector-register copies.
+// The final xform's record is constant for the slot as well: its operands are held the same way (three registers, five with a post affine).
+constexpr bool kHoistFinal = FL_SPEC_FINAL != 0 && FL_HOIST_BUDGET >= 7;
+template <int I, bool COL = kHoistCol, bool AFF = kHoistAff, bool POST = kHoistPost>
+struct SpecXfRes : SpecXf<I> {
+    const XfVec &v;
+    __device__ __forceinline__ float xo(const XfHead &h) const { return AFF ? v.xo : h.f[2]; }
+    __device__ __forceinline__ float yo(const XfHead &h) const { return AFF ? v.yo : h.f[5]; }
+    __device__ __forceinline__ float pxo(const XfHead &h) const { return POST ? v.pxo : h.f[8]; }
+    __device__ __forceinline__ float pyo(const XfHead &h) const { return POST ? v.pyo : h.f[11]; }
+    static constexpr bool kBlend = COL;
+    __device__ __forceinline__ float cmul(const XfHead &h) const { return h.f[13]; }
+    __device__ __forceinline__ float cadd() const { return v.cprod; }
+};
 // Kernels whose records are fetched per round (more than four xforms, see kSpecResident) cannot keep every xform's operands in registers; they keep
 // them in a 16-byte-per-xform LDS table {x offset, y offset, 1 - colour speed, colour * speed}, filled once per launch, and read the entry of the
 // NEXT round's xform (chosen a round ahead) behind the swap: one address instruction and one ds_read_b128 per round instead of the two v_mov of
 // the affine and the v_sub + v_mov + v_mul of the colour blend.
 constexpr bool kTab = !kSpecResident && FL_HOIST_BUDGET >= 12 && FL_SPEC_NXF * 16 <= FL_XTAB_BYTES && FL_SPEC_CHAOS == 0;      // (chaos kernels: no record is chosen a round ahead)
-template <int I, class Extra>
-__device__ __forceinline__ void spec_apply_xf_tab(const XfHead &h, const float4 &t, const float *__restrict__ xf,
-                                                  float &x, float &y, float &c, mwc_t &r, const XfTail *tl, Extra &&extra)
-{
-    extra();          // (the previous round's plot, in the xform's own block: two independent chains for the scheduler; see iter_body)
-    float tx = fmaf(h.f[0], x, fmaf(h.f[1], y, t.x));
-    float ty = fmaf(h.f[3], x, fmaf(h.f[4], y, t.y));
-    float ox = -0.0f, oy = -0.0f;
-    spec_variations<I, 0>(xf, h.w0, tx, ty, ox, oy, r, tl);
-    if constexpr (kSpecPost[I] != 0) {
-        const float qx = fmaf(h.f[6], ox, fmaf(h.f[7], oy, h.f[8]));
-        const float qy = fmaf(h.f[9], ox, fmaf(h.f[10], oy, h.f[11]));
-        ox = qx; oy = qy;
-    }
-    c = fmaf(c, t.z, t.w);
-    asm volatile("" : "+v"(c));
-    spec_opacity<I>(h, c, r);
-    x = ox; y = oy;
-}
-template <int LO, int HI, class Extra>
-__device__ __forceinline__ void spec_dispatch_tab(int k, const XfHead &h, const float4 &t, const float *__restrict__ xf,
-                                                  float &x, float &y, float &c, mwc_t &r, const XfTail *tl, Extra &&extra)
-{
-    if constexpr (HI - LO == 1) spec_apply_xf_tab<LO>(h, t, xf, x, y, c, r, tl, extra);
-    else {
-        constexpr int MID = (LO + HI) / 2;
-        if (k < MID) spec_dispatch_tab<LO, MID>(k, h, t, xf, x, y, c, r, tl, extra);
-        else spec_dispatch_tab<MID, HI>(k, h, t, xf, x, y, c, r, tl, extra);
-    }
-}
-// The final xform's record is constant for the slot as well: its operands are held the same way (three registers, five with a post affine).
-constexpr bool kHoistFinal = FL_SPEC_FINAL != 0 && FL_HOIST_BUDGET >= 7;
-template <int I, bool COL = kHoistCol, bool AFF = kHoistAff, bool POST = kHoistPost>
-__device__ __forceinline__ void spec_apply_xf_res(const XfHead &h, const XfVec &v, const float *__restrict__ xf,
-                                                  float &x, float &y, float &c, mwc_t &r, const XfTail *tl = nullptr)
-{
-    float tx = fmaf(h.f[0], x, fmaf(h.f[1], y, AFF ? v.xo : h.f[2]));
-    float ty = fmaf(h.f[3], x, fmaf(h.f[4], y, AFF ? v.yo : h.f[5]));
-    float ox = -0.0f, oy = -0.0f;
-    spec_variations<I, 0>(xf, h.w0, tx, ty, ox, oy, r, tl);
-    if constexpr (kSpecPost[I] != 0) {
-        const float qx = fmaf(h.f[6], ox, fmaf(h.f[7], oy, POST ? v.pxo : h.f[8]));
-        const float qy = fmaf(h.f[9], ox, fmaf(h.f[10], oy, POST ? v.pyo : h.f[11]));
-        ox = qx; oy = qy;
-    }
-    // (the empty asm keeps the blend in its xform's arm: merged into one v_fmac behind the arms it needs a v_mov of the product in each)
-    if constexpr (COL) { c = fmaf(c, h.f[13], v.cprod); asm volatile("" : "+v"(c)); }
-    else { const float csp = h.f[13]; c = fmaf(c, 1.0f - csp, h.f[12] * csp); }
-    spec_opacity<I>(h, c, r);
-    x = ox; y = oy;
-}
-template <int LO, int HI, class Extra>
-__device__ __forceinline__ void spec_dispatch_res(int k, const XfHead (&heads)[FL_SPEC_NXF], const XfVec (&hv)[FL_SPEC_NXF], const float *__restrict__ xf0, int xf_stride,
-                                                  float &x, float &y, float &c, mwc_t &r, const XfTail (&tails)[FL_SPEC_NXF], Extra &&extra)
-{
-    if constexpr (HI - LO == 1) { extra(); spec_apply_xf_res<LO>(heads[LO], hv[LO], xf0 + LO * xf_stride, x, y, c, r, &tails[LO]); }
-    else {
-        constexpr int MID = (LO + HI) / 2;
-        if (k < MID) spec_dispatch_res<LO, MID>(k, heads, hv, xf0, xf_stride, x, y, c, r, tails, extra);
-        else spec_dispatch_res<MID, HI>(k, heads, hv, xf0, xf_stride, x, y, c, r, tails, extra);
-    }
-}
+template <int I>
+struct SpecXfTab : SpecXf<I> {
+    const float4 &t;
+    __device__ __forceinline__ float xo(const XfHead &) const { return t.x; }
+    __device__ __forceinline__ float yo(const XfHead &) const { return t.y; }
+    static constexpr bool kBlend = true;
+    __device__ __forceinline__ float cmul(const XfHead &) const { return t.z; }
+    __device__ __forceinline__ float cadd() const { return t.w; }
+};
 
-// chaos kernels: f(SpecIdx<I>) for every selectable xform in order (the arms of the divergent walk, see iter_body)
+// f(SpecIdx<I>) for every selectable xform in order (chaos kernels: the arms of the divergent walk, see iter_body)
 template <int I> struct SpecIdx { static constexpr int v = I; };
 template <int I, class F>
 __device__ __forceinline__ void spec_each_xf(F &&f)
@@ -288,19 +281,17 @@ __device__ __forceinline__ void spec_each_xf(F &&f)
     if constexpr (I < FL_SPEC_NXF) { f(SpecIdx<I>{}); spec_each_xf<I + 1>(f); }
 }
 
-// wave-uniform dispatch over the selectable xforms [LO, HI): a binary tree of scalar compares
-template <int LO, int HI, class Extra>
-__device__ __forceinline__ void spec_dispatch(int k, const XfHead &h, const float *__restrict__ xf,
-                                              float &x, float &y, float &c, mwc_t &r, Extra &&extra)
+// wave-uniform dispatch over the selectable xforms [LO, HI): a binary tree of scalar compares with leaf(SpecIdx<k>) at its leaves
+template <int LO, int HI, class Leaf, class... A>
+__device__ __forceinline__ void spec_dispatch(int k, const float *__restrict__ xf, Leaf &&leaf, A &&...a)
 {
-    if constexpr (HI - LO == 1) { extra(); spec_apply_xf<LO>(h, xf, x, y, c, r); }
+    if constexpr (HI - LO == 1) leaf(SpecIdx<LO>{}, xf, a...);
     else {
         constexpr int MID = (LO + HI) / 2;
-        if (k < MID) spec_dispatch<LO, MID>(k, h, xf, x, y, c, r, extra);
-        else spec_dispatch<MID, HI>(k, h, xf, x, y, c, r, extra);
+        if (k < MID) spec_dispatch<LO, MID>(k, xf, leaf, a...);
+        else spec_dispatch<MID, HI>(k, xf, leaf, a...);
     }
 }
-#endif
 
 // cuburn/code/iter.py:366-406: if the cell had reached 512 hits, swap it with zero and add its
 // unpacked contents (weighted by the hot-pixel multiplier) to the float accumulator.
@@ -403,29 +394,15 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     // (NW / 4) * slot + q — walkers, RNG streams, point swap and parameter blocks exactly those of 1024 four-wave slots (same
     // results, bit for bit) — and the whole workgroup shares one sort batch, which is what the large workgroups are for.
     // (The wave number on the scalar side: the parameter block must stay a scalar base.)
-#ifdef FL_RTC
-    constexpr uint32_t kSubSpec = FL_SPEC_SUB_LOG2;
-#else
-    constexpr uint32_t kSubSpec = 0;
-#endif
-    const uint32_t sub_log2 = NW == 4 ? 0u : SPEC ? kSubSpec : bg.sub_log2;      // 0, or log2(NW / 4)
+    const uint32_t sub_log2 = NW == 4 ? 0u : SPEC ? (uint32_t)FL_SPEC_SUB_LOG2 : bg.sub_log2;      // 0, or log2(NW / 4)
     const bool pair = sub_log2 != 0u;
     const uint32_t half = pair ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(w >> 2)) : 0u;      // which sub-block
     const uint32_t slot = blockIdx.x, ts = pair ? (slot << sub_log2) + half : slot, prow = slot * FL_PAL_H / gridDim.x;
-#ifdef FL_RTC
     const int nxf = SPEC ? FL_SPEC_NXF : prog[1], has_final = SPEC ? FL_SPEC_FINAL : prog[2], pstride = SPEC ? FL_SPEC_PSTRIDE : prog[3];
     const int cdf_off = SPEC ? FL_SPEC_CDF_OFF : prog[4], xf_off = SPEC ? FL_SPEC_XF_OFF : prog[5];
     const int xf_stride = SPEC ? FL_SPEC_XF_STRIDE : prog[6], var_stride = SPEC ? FL_SPEC_VAR_STRIDE : prog[7];
-#else
-    const int nxf = prog[1], has_final = prog[2], pstride = prog[3], cdf_off = prog[4];
-    const int xf_off = prog[5], xf_stride = prog[6], var_stride = prog[7];
-#endif
     int chaos_off = 0;                                  // (8-word programs have no word 8)
-#ifdef FL_RTC
     if constexpr (CHAOS) chaos_off = SPEC ? FL_SPEC_CHAOS_OFF : prog[8];
-#else
-    if constexpr (CHAOS) chaos_off = prog[8];
-#endif
     const float *__restrict__ P = params + (size_t)ts * pstride;
 
     if (!BINNED) for (int i = tid; i < FL_PAL_W; i += NT) palrow[i] = palette[prow * FL_PAL_W + i];
@@ -452,18 +429,12 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     // camera and final xform are constant for the slot
     const float cam0 = P[0], cam1 = P[1], cam3 = P[3], cam4 = P[4];
     float cam2 = P[2], cam5 = P[5];
-#ifdef FL_RTC
     if constexpr (SPEC && FL_HOIST_BUDGET >= 2) asm volatile("" : "+v"(cam2), "+v"(cam5));      // the camera's offsets in vector registers (see kHoistCol)
-#endif
     const float *__restrict__ xf_final = P + xf_off + nxf * xf_stride;
     // Does any selectable xform have an opacity (bit 9 of word 14)?  The per-genome kernel knows at compile time; the interpreter
     // looks once per launch (wave-uniform).  Without one, nothing below touches the colour's sign or the plot.
     // (OPAC: can this kernel meet one at all — what it does for hidden samples is compiled only then)
-#ifdef FL_RTC
     constexpr bool OPAC = SPEC ? kAnyOpac : true;
-#else
-    constexpr bool OPAC = true;
-#endif
     bool any_opac = false;
     if constexpr (OPAC && SPEC) any_opac = true;
     else if constexpr (OPAC) for (int i = 0; i < nxf; ++i) any_opac |= (__float_as_int(P[xf_off + i * xf_stride + 14]) & 0x200) != 0;
@@ -511,7 +482,6 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     uint32_t sel_next = CHAOS ? 0u : __builtin_amdgcn_readfirstlane(mwc_next(rctx));      // (chaos kernels draw no wave selector)
     int k_next = choose(sel_next);
     const float *__restrict__ xf_next = P + xf_off + k_next * xf_stride;
-#ifdef FL_RTC
     constexpr bool RESIDENT = SPEC && kSpecResident;
     XfHead heads[FL_SPEC_NXF];
     XfVec hv[FL_SPEC_NXF] = {};
@@ -546,19 +516,13 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         hfin_res.f[13] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f - csp)));
         if constexpr (kSpecPost[FL_SPEC_NXF] != 0) { vfin.pxo = hfin_res.f[8]; vfin.pyo = hfin_res.f[11]; asm volatile("" : "+v"(vfin.pxo), "+v"(vfin.pyo)); }
     }
-#else
-    constexpr bool RESIDENT = false;
-#endif
     XfHead hnext = RESIDENT ? XfHead{} : load_head(xf_next);
-#ifdef FL_RTC
     XfTail tail_next = {};
     if constexpr (SPEC && kTab) {
 #pragma unroll
         for (int i = 0; i < kTailWords; ++i) tail_next.w[i] = xf_next[kTailFirst + i];
     }
-#endif
     float4 tcur = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#ifdef FL_RTC
     if constexpr (SPEC && kTab) {
         const uint32_t th = pair ? tid & 255u : tid;           // (paired: a table per half, filled from the half's own block)
         if ((int)th < FL_SPEC_NXF) {
@@ -569,7 +533,6 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         __syncthreads();
         tcur = xtab[half * 16u + k_next];
     }
-#endif
 
     // One round of the walk: reseed bad points, apply the chosen xform, swap walkers between waves.
     uint32_t par = 0;                                   // parity of the round: which of the two swap buffers
@@ -591,20 +554,17 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             // the xform is uniform (its record and its chaos row are scalar operands).  The lane's draw for the step after this one
             // sits inside the arm, behind the opacity decision.  Everything from the swap on is reached with all lanes active again.
             uint32_t nx_out = nx;
-#ifdef FL_RTC
             if constexpr (SPEC) {
                 spec_each_xf<0>([&](auto idx) __attribute__((always_inline)) {
                     constexpr int I = decltype(idx)::v;
                     if (nx == (uint32_t)I) {
                         const float *__restrict__ rec = P + xf_off + I * xf_stride;
-                        if constexpr (RESIDENT) spec_apply_xf_res<I>(heads[I], hv[I], rec, x, y, color, rctx, &tails[I]);
-                        else { const XfHead h = load_head(rec); spec_apply_xf<I>(h, rec, x, y, color, rctx); }
+                        if constexpr (RESIDENT) xf_apply(heads[I], rec, SpecXfRes<I>{{{}, &tails[I]}, hv[I]}, x, y, color, rctx);
+                        else { const XfHead h = load_head(rec); xf_apply(h, rec, SpecXf<I, false>{{}, nullptr}, x, y, color, rctx); }
                         nx_out = chaos_pick(P + chaos_off + I * FL_SPEC_NXF, FL_SPEC_NXF, rctx);
                     }
                 });
-            } else
-#endif
-            {
+            } else {
                 // the interpreter: a loop over the first remaining lane's xform (readfirstlane reads the first ACTIVE lane — the
                 // lanes that have run their arm have left the loop); at most nxf turns
                 bool pending = true;
@@ -613,7 +573,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
                     if ((int)nx == p) {
                         const float *__restrict__ rec = P + xf_off + p * xf_stride;
                         const XfHead h = load_head(rec);
-                        apply_xf(h, rec, var_stride, x, y, color, rctx, any_opac);
+                        xf_apply(h, rec, XfInterp<true>(h, var_stride, any_opac), x, y, color, rctx);
                         nx_out = chaos_pick(P + chaos_off + p * nxf, nxf, rctx);
                         pending = false;
                     }
@@ -623,9 +583,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         } else {
         const int k_cur = k_next;
         const float *__restrict__ xf_cur = xf_next;
-#ifdef FL_RTC
-        XfTail tail = tail_next;          // (the early tail: requested a round ahead, with the head)
-#endif
+        const XfTail tail = tail_next;    // (the early tail: requested a round ahead, with the head)
         sel_next = __builtin_amdgcn_readfirstlane(mwc_next(rctx));
         k_next = choose(sel_next);
         xf_next = P + xf_off + k_next * xf_stride;
@@ -633,20 +591,30 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
         // same scalar registers (no second set and no nine register copies every round — the scalar unit is
         // on this kernel's critical path) and still has the swap, the barrier and the rest of the round to
         // arrive: k_iter 0.717 -> 0.70 ms, the interpreter kernel -15 %.
-#ifdef FL_RTC
-        if constexpr (RESIDENT) spec_dispatch_res<0, FL_SPEC_NXF>(k_cur, heads, hv, P + xf_off, xf_stride, x, y, color, rctx, tails, extra);
-        else if constexpr (SPEC && kTab) spec_dispatch_tab<0, FL_SPEC_NXF>(k_cur, hnext, tcur, xf_cur, x, y, color, rctx, &tail, extra);
-        else if constexpr (SPEC) spec_dispatch<0, FL_SPEC_NXF>(k_cur, hnext, xf_cur, x, y, color, rctx, extra);
-        else
-#endif
-        { extra(); apply_xf(hnext, xf_cur, var_stride, x, y, color, rctx, any_opac); }
+        // (extra(): the previous round's plot, in the xform's own block — two independent chains for the scheduler, see MERGE)
+        if constexpr (SPEC) {
+            if constexpr (RESIDENT) spec_dispatch<0, FL_SPEC_NXF>(k_cur, P + xf_off, [&](auto idx, const float *xf0) __attribute__((always_inline)) {
+                constexpr int I = decltype(idx)::v;
+                extra();
+                xf_apply(heads[I], xf0 + I * xf_stride, SpecXfRes<I>{{{}, &tails[I]}, hv[I]}, x, y, color, rctx);
+            });
+            // (the operands ride down the tree as arguments, each form only its own: captured, or with the table's beside it, the per-round form's code moves)
+            else if constexpr (kTab) spec_dispatch<0, FL_SPEC_NXF>(k_cur, xf_cur, [](auto idx, const float *xf, const XfHead &h, const float4 &t, float &x, float &y, float &c, mwc_t &r, const XfTail *tl, auto &ex) __attribute__((always_inline)) {
+                constexpr int I = decltype(idx)::v;
+                ex();
+                xf_apply(h, xf, SpecXfTab<I>{{{}, tl}, t}, x, y, c, r);
+            }, hnext, tcur, x, y, color, rctx, &tail, extra);
+            else spec_dispatch<0, FL_SPEC_NXF>(k_cur, xf_cur, [](auto idx, const float *xf, const XfHead &h, float &x, float &y, float &c, mwc_t &r, auto &ex) __attribute__((always_inline)) {
+                constexpr int I = decltype(idx)::v;
+                ex();
+                xf_apply(h, xf, SpecXf<I, false>{{}, nullptr}, x, y, c, r);
+            }, hnext, x, y, color, rctx, extra);
+        } else { extra(); xf_apply(hnext, xf_cur, XfInterp<true>(hnext, var_stride, any_opac), x, y, color, rctx); }
         if constexpr (!RESIDENT) hnext = load_head(xf_next);
-#ifdef FL_RTC
         if constexpr (SPEC && kTab) {
 #pragma unroll
             for (int i = 0; i < kTailWords; ++i) tail_next.w[i] = xf_next[kTailFirst + i];
         }
-#endif
         (void)k_cur; (void)xf_cur;
         }
 
@@ -658,9 +626,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             x = swp[par][0][tid]; y = swp[par][1][tid]; color = swp[par][2][tid];
             if constexpr (CHAOS) nx = __float_as_uint(swp[par][PL - 1][tid]);
             if constexpr (OPAC) if (any_opac) { hid_bits = __float_as_uint(color); color = fabsf(color); }      // the hidden bit came with the point (opacity_mark)
-#ifdef FL_RTC
             if constexpr (SPEC && kTab) tcur = xtab[half * 16u + k_next];          // the next round's operands: on their way while this round plots
-#endif
             __builtin_amdgcn_s_setprio(0);
             par ^= 1u;
         }
@@ -669,11 +635,7 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
     // or plotting, in batches of bg.rounds rounds that end with the tile sort — so that a round's loop
     // bookkeeping is ONE counter: the scalar unit is on this kernel's critical path.
     const uint32_t nfuse = min(fuse, nrounds);
-#ifdef FL_RTC
     constexpr bool SPLIT_FUSE = !SPEC || FL_SPEC_NXF <= 9;      // per-genome kernels with more xforms keep a single copy of the walk
-#else
-    constexpr bool SPLIT_FUSE = true;
-#endif
     // (a kernel with many heavy xforms keeps ONE copy of the walk: there the fuse rounds run through the
     // plotting loop with the plot skipped — a second copy of twelve inlined xforms cost cfg5 7 %)
     // The swap destination cycles through three values (phase = round % 3).  Rotating three registers costs three
@@ -699,21 +661,14 @@ iter_body(unsigned char *smem, const int32_t *__restrict__ prog, const float *__
             for (uint32_t i = from; i < to; ++i) body(next_dst(), i);
         }
     };
-#ifdef FL_RTC
     constexpr bool MERGE = BINNED && SPEC && SPLIT_FUSE && FL_SPEC_NXF <= FL_ITER_MERGE_MAX_XF && !CHAOS;      // (chaos: no single block to ride in)
-#else
-    constexpr bool MERGE = false;
-#endif
     // The plot of a round, in two parts: the final xform (which may draw random numbers) ...
     auto plot_head = [&](float &cx, float &cy, float &cf) __attribute__((always_inline)) {
         float fx = x, fy = y, fc = color;
-#ifdef FL_RTC
         if constexpr (SPEC) {
-            if constexpr (kHoistFinal) spec_apply_xf_res<FL_SPEC_NXF, true, true, true>(hfin_res, vfin, xf_final, fx, fy, fc, rctx, &tfin);
-            else if constexpr (FL_SPEC_FINAL != 0) { const XfHead hfin = load_head(xf_final); spec_apply_xf<FL_SPEC_NXF>(hfin, xf_final, fx, fy, fc, rctx); }
-        } else
-#endif
-        if (has_final) { const XfHead hfin = load_head(xf_final); apply_xf(hfin, xf_final, var_stride, fx, fy, fc, rctx); }   // iter.py:302-307
+            if constexpr (kHoistFinal) xf_apply(hfin_res, xf_final, SpecXfRes<FL_SPEC_NXF, true, true, true>{{{}, &tfin}, vfin}, fx, fy, fc, rctx);
+            else if constexpr (FL_SPEC_FINAL != 0) { const XfHead hfin = load_head(xf_final); xf_apply(hfin, xf_final, SpecXf<FL_SPEC_NXF, false>{{}, nullptr}, fx, fy, fc, rctx); }
+        } else if (has_final) { const XfHead hfin = load_head(xf_final); xf_apply(hfin, xf_final, XfInterp<false>(hfin, var_stride, false), fx, fy, fc, rctx); }   // iter.py:302-307
         // the camera and the colour's scale here too: the point's registers are free before the next round's reseed can
         // write them (kept for the second part, the MERGE loop below paid three register copies per round)
         cx = fmaf(cam0, fx, fmaf(cam1, fy, cam2));                          // iter.py:306-309
@@ -1019,7 +974,7 @@ k_apply_xf_tap(const int32_t *__restrict__ prog, const float *__restrict__ param
     float4 p = pts[i];
     const float *__restrict__ xf = P + prog[5] + xfi * prog[6];
     const XfHead h = load_head(xf);
-    apply_xf(h, xf, prog[7], p.x, p.y, p.z, r);
+    xf_apply(h, xf, XfInterp<false>(h, prog[7], false), p.x, p.y, p.z, r);
     pts[i] = p;
     rng[i].mul = r.mul; rng[i].state = r.state; rng[i].carry = r.carry;
 }
@@ -1082,50 +1037,39 @@ static size_t iter_lds_bytes(int nw, int acc, uint32_t rounds, uint32_t nbins, u
     return b + ((size_t)FL_XTAB_BYTES << sub_log2);      // (sub-blocks: an operand table each)
 }
 
-void launch_iter(hipStream_t st, int nw, bool count, int acc, uint32_t nslots,
-                 const int32_t *prog, const float *params, const u64 *palette, fl_mwc *rng,
-                 float4 *points, const uint32_t *hot, u64 *atom, float *out4, u64 *counters,
-                 uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
-                 uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
-                 uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2, bool chaos)
+void launch_iter(hipStream_t st, const IterLaunch &L, hipFunction_t fn)
 {
-    if (sub_log2 != 0u && (4 << sub_log2) != nw) abort();      // sub-blocks are four waves
-    BinGeom bg = {tiles_x, nbins, rounds_per_batch, nbatch_total, sub_log2};
-    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2, chaos);
+    const int nw = L.nw;
+    if (L.sub_log2 != 0u && (4 << L.sub_log2) != nw) abort();      // sub-blocks are four waves
+    BinGeom bg = {L.tiles_x, L.nbins, L.rounds_per_batch, L.nbatch_total, L.sub_log2};
+    const size_t lds = iter_lds_bytes(nw, L.acc, L.rounds_per_batch, L.nbins, L.sub_log2, L.chaos);
+    if (fn) {
+        // the kernel's parameters in FL_ITER_ARGS order
+        IterLaunch a = L;
+        void *args[] = {&a.prog, &a.params, &a.palette, &a.rng, &a.points, &a.hot, &a.atom, &a.out4, &a.counters, &a.astride, &a.aheight,
+                        &a.round0, &a.nrounds, &a.fuse, &bg, &a.log, &a.dir};
+        // (no hipFuncSetAttribute here: that API takes a host function pointer, not a module function; module launches
+        // accept up to the device's 160 KB of dynamic LDS as they are — the 137 KB workgroups of the 8K geometry run
+        // through this path in tests/test_gpu_fullsize.py::test_cfg5_full_size)
+        (void)hipExtModuleLaunchKernel(fn, L.nslots * (uint32_t)nw * 64, 1, 1, (uint32_t)nw * 64, 1, 1, lds, st, args, nullptr, L.ev_start, L.ev_stop, 0);
+        return;
+    }
 #define LAUNCH_X(NW, C, A, X) do { \
         static unsigned long long attr_done = 0; \
         ensure_max_dynamic_lds((const void *)k_iter<NW, C, A, X>, attr_done); \
         /* the timing events bracket the kernel itself (recorded by the dispatch packet), not the launch call */ \
-        hipExtLaunchKernelGGL((k_iter<NW, C, A, X>), dim3(nslots), dim3(NW * 64), lds, st, ev_start, ev_stop, 0, prog, params, palette, \
-        rng, points, hot, atom, out4, counters, astride, aheight, round0, nrounds, fuse, bg, log, dir); } while (0)
+        hipExtLaunchKernelGGL((k_iter<NW, C, A, X>), dim3(L.nslots), dim3(NW * 64), lds, st, L.ev_start, L.ev_stop, 0, L.prog, L.params, L.palette, \
+        L.rng, L.points, L.hot, L.atom, L.out4, L.counters, L.astride, L.aheight, L.round0, L.nrounds, L.fuse, bg, L.log, L.dir); } while (0)
     /* (the chaos form of the walk is an instantiation of its own: programs of 9 words) */
-#define LAUNCH(NW, C, A) do { if (chaos) LAUNCH_X(NW, C, A, true); else LAUNCH_X(NW, C, A, false); } while (0)
+#define LAUNCH(NW, C, A) do { if (L.chaos) LAUNCH_X(NW, C, A, true); else LAUNCH_X(NW, C, A, false); } while (0)
 #define LAUNCH_NW(C, A) do { if (nw == 4) LAUNCH(4, C, A); else if (nw == 8) LAUNCH(8, C, A); else LAUNCH(16, C, A); } while (0)
-    if (acc == 2) LAUNCH_NW(false, 2);
-    else if (acc == 1) { if (count) LAUNCH_NW(true, 1); else LAUNCH_NW(false, 1); }
-    else if (acc == 3) { if (count) LAUNCH_NW(true, 3); else LAUNCH_NW(false, 3); }
-    else { if (count) LAUNCH_NW(true, 0); else LAUNCH_NW(false, 0); }
+    if (L.acc == 2) LAUNCH_NW(false, 2);
+    else if (L.acc == 1) { if (L.count) LAUNCH_NW(true, 1); else LAUNCH_NW(false, 1); }
+    else if (L.acc == 3) { if (L.count) LAUNCH_NW(true, 3); else LAUNCH_NW(false, 3); }
+    else { if (L.count) LAUNCH_NW(true, 0); else LAUNCH_NW(false, 0); }
 #undef LAUNCH_NW
 #undef LAUNCH
 #undef LAUNCH_X
-}
-
-void launch_iter_fn(hipStream_t st, hipFunction_t fn, int nw, int acc, uint32_t nslots,
-                    const int32_t *prog, const float *params, const u64 *palette, fl_mwc *rng,
-                    float4 *points, const uint32_t *hot, u64 *atom, float *out4, u64 *counters,
-                    uint32_t astride, uint32_t aheight, uint32_t round0, uint32_t nrounds, uint32_t fuse,
-                    uint32_t tiles_x, uint32_t nbins, uint32_t rounds_per_batch, uint32_t nbatch_total,
-                    uint32_t *log, uint32_t *dir, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t sub_log2, bool chaos)
-{
-    if (sub_log2 != 0u && (4 << sub_log2) != nw) abort();      // sub-blocks are four waves
-    BinGeom bg = {tiles_x, nbins, rounds_per_batch, nbatch_total, sub_log2};
-    const size_t lds = iter_lds_bytes(nw, acc, rounds_per_batch, nbins, sub_log2, chaos);
-    void *args[] = {&prog, &params, &palette, &rng, &points, &hot, &atom, &out4, &counters, &astride, &aheight,
-                    &round0, &nrounds, &fuse, &bg, &log, &dir};
-    // (no hipFuncSetAttribute here: that API takes a host function pointer, not a module function; module launches
-    // accept up to the device's 160 KB of dynamic LDS as they are — the 137 KB workgroups of the 8K geometry run
-    // through this path in tests/test_gpu_fullsize.py::test_cfg5_full_size)
-    (void)hipExtModuleLaunchKernel(fn, nslots * (uint32_t)nw * 64, 1, 1, (uint32_t)nw * 64, 1, 1, lds, st, args, nullptr, ev_start, ev_stop, 0);
 }
 
 void launch_flush(hipStream_t st, u64 *atom, float4 *out, uint32_t *hot, uint32_t nbins, bool use_hot)
