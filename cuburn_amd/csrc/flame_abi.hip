@@ -959,6 +959,28 @@ int fl_filter(fl_ctx *c, int id, uint32_t w, uint32_t h, const float *p, uint32_
     return FL_OK;
 }
 
+int fl_resample(fl_ctx *c, uint32_t w, uint32_t h, uint32_t ss, const float *taps, uint32_t ntaps)
+{
+    REQUIRE(c && taps && w && h, "null argument");
+    REQUIRE(ss >= 1 && ss <= FL_RESAMPLE_MAX_SS, "resample: ss must be 1..4");
+    REQUIRE(ntaps >= ss && ntaps <= ss + 2 * FL_GUTTER && (ntaps - ss) % 2 == 0,
+            "resample: ntaps must lie in [ss, ss + 24] and have the parity of ss");
+    REQUIRE(w <= 0x7fffffffu / ss && h <= 0x7fffffffu / ss, "resample: source size overflows");
+    for (uint32_t i = 0; i < ntaps; ++i) REQUIRE(std::isfinite(taps[i]), "resample: non-finite tap");
+    HIPCHK(hipSetDevice(c->device));
+    fl_dim din, dout;
+    fl_calc_dim(ss * w, ss * h, &din); fl_calc_dim(w, h, &dout);
+    int rc = ensure_fb(c, din);
+    if (rc) return rc;
+    EvPair *e = ev_begin(c, c->filt_ev);
+    flush_pending(c);                                       // a deferred yuv / DE belongs to the source size
+    launch_resample(L(c).stream, din, dout, (int)ss, L(c).d_back, L(c).d_front, taps, (int)ntaps);
+    std::swap(L(c).d_front, L(c).d_back);
+    ev_end(c, e);
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
 size_t fl_output_bytes(uint32_t w, uint32_t h, int fmt)
 {
     const size_t n = (size_t)w * h;

@@ -95,6 +95,10 @@ void launch_de_adaptive(hipStream_t st, fl_dim d, float4 *buf, float4 *stage_c, 
 size_t de_adaptive_tiles(fl_dim d);
 void de_adaptive_norms(float *out);
 
+// resample.hip: flam3's spatial filter + supersample decimation, src laid out as din (the ss-fold frame) -> dst laid out as dout;
+// ntaps in [ss, ss + 2 * FL_GUTTER] of the same parity as ss (fl_resample checks)
+void launch_resample(hipStream_t st, fl_dim din, fl_dim dout, int ss, float4 *dst, const float4 *src, const float *taps, int ntaps);
+
 // output.hip
 void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng, uint32_t nrng, int fmt, void *dst);
 

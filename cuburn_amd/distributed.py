@@ -515,6 +515,10 @@ def sharded_frame_steps(mgr, rdr, gnm, gprof, tc, rank, world, device=None, copy
     lane and torch's stream are ordered by events (order_streams), so that with two frames queued ahead the next
     frame's iterate kernels run under this frame's exchange and filters.
     """
+    if gprof.supersample != 1 or any(f.name == 'spatial' for f in rdr.filts):
+        raise ValueError('sharded rendering does not resample yet (supersample %r, filters %s): band halos are not defined '
+                         'across a change of resolution; distribute whole frames instead (jobs.py)'
+                         % (gprof.supersample, [f.name for f in rdr.filts]))
     from . import _lib
     from .render import DurationEvent
     lib = _lib.load()

@@ -82,6 +82,11 @@ class Logscale(_Simple):
         k1 = f32(params.brightness(tc) * 268 / 256)
         area = dim.h / (params.scale(tc) ** 2 * dim.w)       # cuburn/filters.py:103-106
         k2 = f32(1.0 / (area * gprof.spp(tc)))
+        # a bin of the supersampled accumulator has 1 / ss^2 of an output pixel's area, and the spatial filter averages:
+        # the same factor on either side of `spatial`
+        ss = supersample_of(gprof)
+        if ss != 1:
+            k2 = f32(k2 * f32(ss * ss))
         return [k1, k2]
 
 
@@ -128,6 +133,67 @@ class LogEncode(_Simple):
         return [f32(params.degamma(tc))]
 
 
+SPATIAL_SUPPORT = 1.5               # flam3's Gaussian: the filter is cut at 1.5 widths
+MAX_SUPERSAMPLE = 4
+MAX_OVERHANG = 12                   # source bins the footprint may overhang an output bin per side: the gutter
+
+
+def check_supersample(ss):
+    if isinstance(ss, bool) or ss != int(ss) or not 1 <= ss <= MAX_SUPERSAMPLE:
+        raise ValueError('supersample must be an integer in 1..%d (got %r)' % (MAX_SUPERSAMPLE, ss))
+    return int(ss)
+
+
+def supersample_of(gprof):
+    return check_supersample(gprof.supersample)
+
+
+def spatial_taps(radius, ss):
+    """
+    The taps per axis of flam3's spatial filter (flam3_create_spatial_filter, Gaussian shape) of ``radius`` output pixels at
+    supersample ``ss``, float32, normalised to sum 1 in float64.  Their number has the parity of ``ss``, so
+    that the footprint is centred on the ss x ss source bins of an output pixel; radius 0 reaches those bins and no further.
+    """
+    ss, radius = check_supersample(ss), float(radius)
+    if not (radius >= 0 and np.isfinite(radius)):
+        raise ValueError('spatial: radius must be finite and >= 0 (got %g)' % radius)
+    fw = 2.0 * SPATIAL_SUPPORT * ss * radius
+    n = int(fw) + 1
+    if (n ^ ss) & 1:
+        n += 1
+    n = max(n, ss)
+    if n > ss + 2 * MAX_OVERHANG:
+        raise ValueError('spatial: radius %g at supersample %d needs %d taps per axis, above the limit of %d (ss + %d: the '
+                         'footprint may overhang an output pixel by the %d-bin gutter per side)'
+                         % (radius, ss, n, ss + 2 * MAX_OVERHANG, 2 * MAX_OVERHANG, MAX_OVERHANG))
+    adjust = SPATIAL_SUPPORT * n / fw if fw > 0 else 1.0
+    x = ((2.0 * np.arange(n) + 1.0) / n - 1.0) * adjust
+    t = np.exp(-2.0 * x * x) * np.sqrt(2.0 / np.pi)
+    return (t / t.sum()).astype(np.float32)
+
+
+@Filter.register('spatial')
+class Spatial(Filter):
+    """flam3's spatial filter and the supersample decimation, one kernel: takes the buffer of the ss-fold frame
+    and leaves that of the output frame, whose Dimensions ``apply`` returns."""
+
+    def apply(self, fb, gprof, params, dim, tc, stream=None):
+        ss = supersample_of(gprof)
+        taps = spatial_taps(params.radius(tc), ss)
+        w, h = dim.w // ss, dim.h // ss
+        if (w * ss, h * ss) != (dim.w, dim.h):
+            raise ValueError('spatial: a %d x %d buffer is not %d times an output frame' % (dim.w, dim.h, ss))
+        _lib.check(_lib.load().fl_resample(fb.ctx, w, h, ss, taps.ctypes.data, len(taps)))
+        return fb.calc_dim(w, h)
+
+
 def create(gprof):
+    """The profile's chain.  `spatial` runs where the profile lists it (["de", "logscale", "spatial", "colorclip"] is flam3's
+    late clip); a supersampled profile that does not list it gets it last (tone-map at full resolution, then filter: flam3's
+    early clip).  Listed at supersample 1 it is flam3's plain spatial filter."""
     order = ['yuv'] + list(gprof.filter_order)
+    if order.count('spatial') > 1:
+        raise ValueError("filter_order lists 'spatial' %d times: the frame is brought down to the output size once" % order.count('spatial'))
+    if supersample_of(gprof) > 1 and 'spatial' not in order:
+        order.append('spatial')
     return [Filter.filter_map[f]() for f in order]

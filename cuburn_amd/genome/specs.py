@@ -50,6 +50,7 @@ filters = {
         'radius': scalespline(11), 'minimum': scalespline(0, max=1), 'curve': scalespline(0.6),
     },
     'haloclip': {},
+    'spatial': {},
     'smearclip': {'width': scalespline(0.7, d='Spatial stdev of filter')},
     'plainclip': {'brightness': scalespline(1.0, d='Linear brightness')},
     'logscale': {'brightness': scalespline(4, d='Log-scale brightness')},
@@ -101,6 +102,8 @@ default_filters = ['bilateral', 'logscale', 'smearclip']
 prof_filters = dict((fk, dict((k, refscalar(1, '.'.join(['filters', fk, k]))) for k in fv))
                     for fk, fv in filters.items())
 prof_filters['logscale']['scale'] = refscalar(1, 'camera.scale')
+# flam3's spatial filter radius in output pixels: the profile's factor times the genome's camera.dither_width (flam3's `filter`)
+prof_filters['spatial']['radius'] = refscalar(1, 'camera.dither_width')
 
 profile = {
     'duration': RefScalar(30, 'time.duration', 'Base duration in seconds'),
@@ -113,6 +116,7 @@ profile = {
     'height': Scalar(720, 'Output height in pixels'),
     'width': Scalar(1280, 'Output width in pixels'),
     'spp': RefScalar(2000, 'camera.spp', 'Base samples per pixel'),
+    'supersample': Scalar(1, 'Accumulate at this many times the output size per axis (1..4) and filter down (flam3 supersample)'),
     'filter_order': list_(enum(list(filters.keys())), default_filters),
     'filters': prof_filters,
     'output': {'type': enum('jpeg png tiff x264', 'jpeg')},

@@ -19,7 +19,7 @@ BUILTIN = {
     'preview': dict(width=640, height=360, spp=1200, skip=1),
 }
 
-_OVERRIDES = 'duration fps frame_width start end skip shard spp width height'.split()
+_OVERRIDES = 'duration fps frame_width start end skip shard spp width height supersample'.split()
 
 
 def add_args(parser=None):
@@ -47,6 +47,8 @@ def add_args(parser=None):
     spa.add_argument('--spp', type=int, metavar='SPP', help='Set base samples per pixel')
     spa.add_argument('--width', type=int, metavar='PX')
     spa.add_argument('--height', type=int, metavar='PX')
+    spa.add_argument('--supersample', type=int, metavar='N',
+                     help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
     out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'x264', 'vp8', 'vp9', 'prores', 'raw'])

@@ -368,7 +368,11 @@ class RenderManager(object):
         ``dev_out`` / ``host``: see Output.copy (frame straight into a device buffer of the caller).
         """
         lib = _lib.load()
-        dim = self.fb.set_dim(gprof.width, gprof.height, nsamples=gprof.spp(tc) * gprof.width * gprof.height)
+        # the accumulator, and every filter in front of `spatial`, have supersample times the output's size per axis; the sample
+        # count stays a density per OUTPUT pixel, as in flam3
+        ss = filters.supersample_of(gprof)
+        nsamps = gprof.spp(tc) * gprof.width * gprof.height
+        acc = self.fb.set_dim(ss * gprof.width, ss * gprof.height, nsamples=nsamps)
         td = gprof.frame_width(tc) / round(gprof.fps * gprof.duration)
         ts = tc - 0.5 * td
         g = rdr._handle(self.fb)
@@ -376,15 +380,16 @@ class RenderManager(object):
         _lib.check(lib.fl_frame_begin(self.fb.ctx, C.byref(fid)))
         if copy:
             self._copy(rdr, gnm)
-        _lib.check(lib.fl_interp(self.fb.ctx, g, dim.w, dim.h, ts, td))
-        nsamps = gprof.spp(tc) * dim.w * dim.h
+        _lib.check(lib.fl_interp(self.fb.ctx, g, acc.w, acc.h, ts, td))
         run = C.c_uint64()
-        _lib.check(lib.fl_iterate(self.fb.ctx, g, dim.w, dim.h, float(nsamps), self.fuse,
-                                  self.resolve_accum_mode(dim), C.byref(run)))
+        _lib.check(lib.fl_iterate(self.fb.ctx, g, acc.w, acc.h, float(nsamps), self.fuse,
+                                  self.resolve_accum_mode(acc), C.byref(run)))
         self.last_nsamples = run.value
+        dim = acc
         for filt in rdr.filts:
             params = getattr(gprof.filters, filt.name)
-            filt.apply(self.fb, gprof, params, dim, tc)
+            dim = filt.apply(self.fb, gprof, params, dim, tc) or dim      # `spatial` returns the output's Dimensions
+        assert dim == self.fb.calc_dim(gprof.width, gprof.height), 'the filter chain did not end at the output size'
         rdr.out.convert(self.fb, gprof, dim)
         h_out = rdr.out.copy(self.fb, dim, dev_out=dev_out, host=host)
         return DurationEvent(self.fb, fid.value), h_out

@@ -237,6 +237,21 @@ enum {
 #define FL_DE_MAX_RADIUS 96    /* FL_FILT_DE: the largest R in px, and so the filter's reach */
 int fl_filter(fl_ctx *ctx, int filter_id, uint32_t w, uint32_t h, const float *params, uint32_t nparams);
 
+/* flam3's spatial filter + supersample decimation: front (laid out for ss*w x ss*h) -> front (laid out for w x h).
+ * The reference has no such step (its accumulator has the output's size; cuburn/genome/convert.py:196 carries flam3's
+ * `filter` radius as camera.dither_width and nothing reads it).  After flam3_create_spatial_filter, Gaussian shape only:
+ * `taps` = ntaps weights t[0..ntaps-1] of a separable filter, ntaps in [ss, ss + 2 * FL_GUTTER] with ntaps - ss even,
+ * g = (ntaps - ss) / 2 the source bins the footprint overhangs on either side.  For EVERY bin of the result's padded buffer,
+ * 0 <= X < astride(w), 0 <= Y < ah(h):
+ *     out[Y][X] = sum_j sum_i t[j] * t[i] * src[12 + ss*(Y-12) - g + j][12 + ss*(X-12) - g + i]
+ * with source coordinates outside [0, astride(ss*w)) x [0, ah(ss*h)) contributing exactly zero (they are not read; the weights
+ * are not renormalised), all four channels alike.  Inside the picture every tap is in range; the result's gutter fades to zero.
+ * ss in 1..4; ss = 1 is the plain spatial filter.  Deferred filter steps (a `yuv`, the DE's end) run first, at the source's
+ * size.  Recorded with the filters in fl_timings / fl_timings_detail[3].  FL_E_INVAL for anything else, non-finite taps included. */
+#define FL_RESAMPLE_MAX_SS 4
+#define FL_RESAMPLE_MAX_TAPS (FL_RESAMPLE_MAX_SS + 2 * FL_GUTTER)
+int fl_resample(fl_ctx *ctx, uint32_t w, uint32_t h, uint32_t ss, const float *taps, uint32_t ntaps);
+
 /* cuburn/output.py:83-88,120-125,150-158,212-219,323-338 (convert + copy of every Output class):
  * f32 -> pixel format with dither (cuburn/code/output.py:7-236), gutter cropped; async D2H into
  * host_out (or device copy when dev_out != 0).  fl_output_bytes gives the frame's size. */
