@@ -12,8 +12,10 @@
 #include <atomic>
 #include <vector>
 #include <algorithm>
+#include <array>
 #include "kernels.h"
 #include "flame_device.h"
+#include "launch_plan.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *what, const char *file, int line, hipError_t e = hipSuccess)
@@ -24,11 +26,71 @@ static int fail(int code, const char *what, const char *file, int line, hipError
     g_err = buf;
     return code;
 }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return fail(e_ == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, #x, __FILE__, __LINE__, e_); } while (0)
+static int fail_hip(hipError_t e, const char *what, const char *file, int line)
+{
+    return fail(e == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, what, file, line, e);
+}
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail_hip(e_, #x, __FILE__, __LINE__); } while (0)
 #define REQUIRE(c, msg) do { if (!(c)) return fail(FL_E_INVAL, msg, __FILE__, __LINE__); } while (0)
 
+// A grow-only device buffer and its one owner.  reserve(n) keeps memory that is large enough; otherwise it frees it (after `quiesce`
+// has waited for whatever may still use it) and allocates n elements anew: contents are not kept.
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;                   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    size_t bytes() const { return cap * sizeof(T); }
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    template <class Quiesce> int reserve(size_t n, const char *what, Quiesce quiesce)
+    {
+        if (n <= cap) return FL_OK;
+        if (int rc = quiesce()) return rc;
+        release();
+        const hipError_t e = hipMalloc(&p, n * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return fail_hip(e, what, __FILE__, __LINE__); }
+        cap = n;
+        return FL_OK;
+    }
+    int reserve(size_t n, const char *what) { return reserve(n, what, [] { return (int)FL_OK; }); }
+    friend void swap(DevBuf &a, DevBuf &b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+};
+
 struct EvPair { hipEvent_t a, b; };
+
+// The bilateral DE's scalars (cuburn/filters.py:62-95) and the 7 coefficients of its blur, as fl_filter received them.
+struct Bilateral { float sstd, cstd, dstd, dpow, gspeed, k7[7]; };
+
+// Deferred ends of the filter chain.  fl_filter defers two cheap per-pixel steps so that the NEXT call can take them
+// along in one pass (cuburn's default chains are yuv -> bilateral -> logscale -> colorclip /
+// smearclip): `yuv` directly in front of `bilateral` becomes part of the DE's first direction,
+// and the DE's last, un-normalising direction takes a following `logscale` and `colorclip` with it.
+// Anything else that looks at the buffers (another filter, output, the debug taps, the next
+// frame) first runs what is pending (flush_pending), so the observable behaviour is that of the separate kernels
+// (the fused kernels run the same per-pixel device functions in the same order).
+struct Pending {
+    bool yuv = false, de = false;     // a `yuv` that has not run yet / the DE, all eight directions
+    int in_mode = 0;                  // what the DE's first direction normalises: 1 the raw accumulator, 2 the raw YUV one
+    Bilateral bl = {};
+    DeTail tail = {};                 // what its last direction applies on the way
+    fl_dim dim = {0, 0, 0, 0, 0};
+    void clear() { yuv = de = false; }
+    void defer_yuv(const fl_dim &d) { yuv = true; dim = d; }
+    // (a pending `yuv` becomes the first direction's input form)
+    void defer_bilateral(const fl_dim &d, const Bilateral &b) { in_mode = yuv ? 2 : 1; yuv = false; de = true; bl = b; tail = {}; dim = d; }
+    // A logscale (once) or a colorclip directly behind the deferred DE rides along with its last direction.  A colorclip ends
+    // the tail: the caller flushes at once.
+    bool try_take(int id, const float *p)
+    {
+        if (!de || yuv || (id == FL_FILT_LOGSCALE && tail.do_log)) return false;
+        if (id == FL_FILT_LOGSCALE) { tail.do_log = 1; tail.k1 = p[0]; tail.k2 = p[1]; }
+        else { tail.do_clip = 1; tail.vib = p[0]; tail.highpow = p[1]; tail.gam = p[2]; tail.lin = p[3]; tail.lingam = p[4]; }
+        return true;
+    }
+};
 
 // One "lane" = a stream with its own framebuffers, sample log and per-frame parameter buffers.
 // Consecutive frames alternate between two lanes so that the drain + filter + output kernels of
@@ -36,40 +98,56 @@ struct EvPair { hipEvent_t a, b; };
 // the role of stream_a / stream_b in the reference (cuburn/render.py:253-262,432-433).
 struct Lane {
     hipStream_t stream = nullptr;
-    size_t nbins = 0;
-    float4 *d_front = nullptr, *d_back = nullptr, *d_side = nullptr;
-    float *d_blur = nullptr;          // 1-channel scratch [nbins]
-    u64 *d_atom = nullptr;
-    uint32_t *d_hot = nullptr;
-    void *d_outpix = nullptr;         // w*h*8 bytes
-    uint32_t *d_de_tmax = nullptr;    // FL_FILT_DE: largest 16h per 64 x 16 tile [nbins / 256 + 64]
-    float *d_de_sinv = nullptr;       // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
-    size_t outpix_bytes = 0;
+    // the framebuffers: allocated together, for one image size (ensure_fb)
+    DevBuf<float4> d_front, d_back, d_side;         // [nbins]
+    DevBuf<float> d_blur;                           // 1-channel scratch [nbins]
+    DevBuf<u64> d_atom;
+    DevBuf<uint32_t> d_hot;
+    DevBuf<unsigned char> d_outpix;                 // w*h*8 bytes
+    DevBuf<uint32_t> d_de_tmax;                     // FL_FILT_DE: largest 16h per 64 x 16 tile [nbins / 256 + 64]
+    DevBuf<float> d_de_sinv;                        // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
+    size_t nbins() const { return d_front.cap; }
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
     // accumulate + flush of launch k run on `aux` while launch k+1 iterates on `stream` into the other set
     // (the role of the reference's alternating streams inside a frame, cuburn/render.py:340-369)
-    uint32_t *d_log[2] = {nullptr, nullptr}, *d_dir[2] = {nullptr, nullptr};
-    size_t log_words[2] = {0, 0}, dir_words[2] = {0, 0};
+    DevBuf<uint32_t> d_log[2], d_dir[2];
     hipStream_t aux = nullptr;
     hipEvent_t ev_it[2] = {nullptr, nullptr}, ev_ac[2] = {nullptr, nullptr};   // iterate k queued / drains of launch k done
-    float *d_params = nullptr;        // [nslots * pstride] one block per temporal sample = per walker slot (grow-only)
+    DevBuf<float> d_params;           // [nslots * pstride] one block per temporal sample = per walker slot
     uint64_t params_serial = 0;       // serial of the genome whose parameters the blocks hold (0: none / just allocated)
-    size_t params_floats = 0;
-    u64 *d_palette = nullptr;         // [FL_PAL_H * FL_PAL_W]
+    DevBuf<u64> d_palette;            // [FL_PAL_H * FL_PAL_W]
     // cross-lane ordering of the state both lanes share
     hipEvent_t ev_interp_done = nullptr;   // genome staging buffers + palette RNG states
     hipEvent_t ev_iter_done = nullptr;     // walkers + their RNG states
     hipEvent_t ev_out_done = nullptr;      // output-dither RNG states
     bool interp_rec = false, iter_rec = false, out_rec = false;
-    // deferred ends of the filter chain (see flush_pending): a `yuv` that has not run yet, and the DE — all eight directions,
-    // the first normalising the accumulator (pend_in_mode: 1 raw, 2 raw YUV), the last un-normalising (+ a logscale to apply
-    // on the way, + a colorclip if that is the call that flushes it): run_de_finish
-    bool pend_yuv = false, pend_finish = false, pend_log = false;
-    float pend_k1 = 0.0f, pend_k2 = 0.0f;
-    int pend_in_mode = 0;
-    float pend_dp[5] = {0, 0, 0, 0, 0}, pend_k7[7] = {0, 0, 0, 0, 0, 0, 0};
-    fl_dim pend_dim = {0, 0, 0, 0, 0};
+    Pending pend;
+
+    std::array<hipEvent_t *, 7> events() { return {&ev_interp_done, &ev_iter_done, &ev_out_done, &ev_it[0], &ev_ac[0], &ev_it[1], &ev_ac[1]}; }
+    int quiesce(bool with_aux)
+    {
+        HIPCHK(hipStreamSynchronize(stream));
+        if (with_aux) HIPCHK(hipStreamSynchronize(aux));
+        return FL_OK;
+    }
+    void release_fb()
+    {
+        d_front.release(); d_back.release(); d_side.release(); d_blur.release(); d_atom.release();
+        d_hot.release(); d_outpix.release(); d_de_tmax.release(); d_de_sinv.release();
+        pend.clear();                 // whatever was deferred dies with the buffers
+    }
+    // everything but `stream`, which may be the caller's (fl_ctx::own_stream)
+    void release()
+    {
+        release_fb();
+        d_params.release(); d_palette.release();
+        for (int k = 0; k < 2; ++k) { d_log[k].release(); d_dir[k].release(); }
+        if (aux) hipStreamDestroy(aux);
+        for (hipEvent_t *ev : events()) if (*ev) hipEventDestroy(*ev);
+    }
 };
+
+#define FL_NOUT 65536u                // RNG states reserved for the output dither kernel
 
 struct fl_ctx {
     int device = 0;
@@ -77,15 +155,21 @@ struct fl_ctx {
     static const int kMaxLanes = 4;
     int nlanes = 2, cur = 0;          // FLAME_LANES (1..4; default 2): consecutive frames go round the lanes
     Lane lanes[kMaxLanes];
-    uint32_t nslots = 0, nwalkers = 0;
+    Lane &lane() { return lanes[cur]; }
+    Lane &prev_lane() { return lanes[(cur + nlanes - 1) % nlanes]; }      // the previous frame's lane: it touched the shared state last
+    uint32_t nslots = 0;
     uint32_t sub_log2 = 0;                        // 512 slots of 8 waves / 256 of 16: 2 / 4 temporal samples per workgroup (iter.hip "Sub-blocks of four waves")
     uint32_t ntemporal() const { return nslots << sub_log2; }      // temporal samples = parameter blocks per frame (>= FL_NTEMPORAL)
     int nw = 4;                       // waves per iterate workgroup
-    fl_mwc *d_rng = nullptr;          // [nwalkers]: walkers | palette rows (64*256) | output dither (FL_NOUT)
-    float4 *d_points = nullptr;       // [nslots*NT]
-    u64 *d_counters = nullptr;
-    uint32_t *d_sort = nullptr; size_t sort_words = 0;     // radix sort scratch (grow-only): digit counts + chunk totals
-    uint32_t bin_rounds = 16, bin_parts = 0;      // bin_parts 0: chosen per image (see do_iter_launch)
+    uint32_t npoints() const { return nslots * (uint32_t)nw * 64u; }      // walkers
+    DevBuf<fl_mwc> d_rng;             // three tables: walkers [npoints] | palette rows [FL_PAL_H * 256] | output dither [FL_NOUT]
+    fl_mwc *rng_walk() const { return d_rng.p; }
+    fl_mwc *rng_pal() const { return d_rng.p + npoints(); }
+    fl_mwc *rng_out() const { return rng_pal() + FL_PAL_H * 256; }
+    DevBuf<float4> d_points;          // [npoints]
+    DevBuf<u64> d_counters;
+    DevBuf<uint32_t> d_sort;          // radix sort scratch: digit counts + chunk totals
+    uint32_t bin_rounds = 16, bin_parts = 0;      // bin_parts 0: chosen per image (accum_parts)
     uint32_t launch_rounds = 0;                   // FLAME_LAUNCH_ROUNDS: write-enabled rounds per binned launch (0: FL_BIN_MAX_ROUNDS) — the sample log of a launch is nslots x 256 x rounds x 4 bytes
     uint32_t round_counter = 0;
     static const uint32_t kFrames = 8;            // frames that may be in flight (reference: 2)
@@ -102,10 +186,8 @@ struct fl_ctx {
     bool env_bin_wide = false, env_no_intra = false;
     bool use_rtc = true;                    // FLAME_RTC=0: always the interpreter kernel
     uint32_t n_spec_launch = 0, n_interp_launch = 0;      // iterate launches by kernel since fl_timings_reset (fl_launch_stats)
+    BinLayout layout(const fl_dim &d) const { return bin_layout(d, nw, bin_rounds, env_bin_wide); }
 };
-#define L(c) ((c)->lanes[(c)->cur])
-#define OTHER(c) ((c)->lanes[((c)->cur + (c)->nlanes - 1) % (c)->nlanes])      /* the previous frame's lane: it touched the shared state last */
-#define FL_NOUT 65536u                // RNG states reserved for the output dither kernel
 
 struct fl_genome {
     uint64_t serial = 0;                    // unique per created genome (a lane remembers whose parameters its blocks hold)
@@ -136,7 +218,8 @@ static const int kKnownVars[] = {0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,
 // that never asks for timings stops recording after kMaxTimed launches instead of growing forever.
 static const size_t kMaxTimed = 8192;
 
-static EvPair *ev_begin(fl_ctx *c, std::vector<EvPair> &list)
+// A pair from the pool, entered in `list`; nothing recorded yet (null: timing is off, or the pool is spent).
+static EvPair *ev_acquire(fl_ctx *c, std::vector<EvPair> &list)
 {
     if (!c->timing || c->pool_used >= kMaxTimed) return nullptr;
     if (c->pool.capacity() < kMaxTimed) c->pool.reserve(kMaxTimed);      // pointers into the pool are held across nested pairs: never reallocate
@@ -145,32 +228,18 @@ static EvPair *ev_begin(fl_ctx *c, std::vector<EvPair> &list)
         if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
         c->pool.push_back(p);
     }
-    EvPair p = c->pool[c->pool_used++];
-    list.push_back(p);
-    hipEventRecord(p.a, L(c).stream);
-    return &c->pool[c->pool_used - 1];
-}
-// a pair whose events are recorded by the kernel launch itself (hipExtLaunchKernelGGL)
-static EvPair *ev_pair(fl_ctx *c, std::vector<EvPair> &list)
-{
-    if (!c->timing || c->pool_used >= kMaxTimed) return nullptr;
-    if (c->pool.capacity() < kMaxTimed) c->pool.reserve(kMaxTimed);
-    if (c->pool_used == c->pool.size()) {
-        EvPair p;
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
-        c->pool.push_back(p);
-    }
     list.push_back(c->pool[c->pool_used++]);
     return &c->pool[c->pool_used - 1];
 }
-static void ev_end(fl_ctx *c, EvPair *p) { if (p) hipEventRecord(p->b, L(c).stream); }
 static EvPair *ev_begin_on(fl_ctx *c, std::vector<EvPair> &list, hipStream_t st)
 {
-    EvPair *p = ev_pair(c, list);
+    EvPair *p = ev_acquire(c, list);
     if (p) hipEventRecord(p->a, st);
     return p;
 }
 static void ev_end_on(EvPair *p, hipStream_t st) { if (p) hipEventRecord(p->b, st); }
+static EvPair *ev_begin(fl_ctx *c, std::vector<EvPair> &list) { return ev_begin_on(c, list, c->lane().stream); }
+static void ev_end(fl_ctx *c, EvPair *p) { ev_end_on(p, c->lane().stream); }
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -178,15 +247,7 @@ extern "C" {
 int fl_abi_version(void) { return FL_ABI_VERSION; }
 const char *fl_last_error(void) { return g_err.c_str(); }
 
-void fl_calc_dim(uint32_t w, uint32_t h, fl_dim *o)
-{
-    o->w = w; o->h = h;
-    o->aw = w + 2 * FL_GUTTER;
-    o->ah = 16 * ((h + 2 * FL_GUTTER + 15) / 16);
-    o->astride = 32 * ((o->aw + 31) / 32);
-}
-
-static void flush_pending(fl_ctx *c);
+void fl_calc_dim(uint32_t w, uint32_t h, fl_dim *o) { *o = calc_dim(w, h); }
 
 // the normalisers of the `de` filter depend on nothing but the quantised radius: computed once per process
 static const float *de_norms()
@@ -195,38 +256,25 @@ static const float *de_norms()
     return t.data();
 }
 
-static void free_fb(fl_ctx *c)
-{
-    hipFree(L(c).d_front); hipFree(L(c).d_back); hipFree(L(c).d_side); hipFree(L(c).d_blur);
-    hipFree(L(c).d_atom); hipFree(L(c).d_hot); hipFree(L(c).d_outpix); hipFree(L(c).d_de_tmax); hipFree(L(c).d_de_sinv);
-    L(c).d_front = L(c).d_back = L(c).d_side = nullptr; L(c).d_blur = nullptr; L(c).d_atom = nullptr;
-    L(c).d_hot = nullptr; L(c).d_outpix = nullptr; L(c).d_de_tmax = nullptr; L(c).d_de_sinv = nullptr;
-    L(c).nbins = 0; L(c).outpix_bytes = 0;
-    L(c).pend_yuv = L(c).pend_finish = L(c).pend_log = false;      // whatever was deferred dies with the buffers
-}
-
 // cuburn/render.py:121-161 Framebuffers.alloc / set_dim: grow-only; on OOM free everything
 // and report FL_E_NOMEM so the caller survives an oversize frame.
-static int ensure_fb(fl_ctx *c, const fl_dim &d)
+static int ensure_fb(Lane &ln, uint32_t w, uint32_t h, fl_dim *dim)
 {
-    size_t nbins = (size_t)d.ah * d.astride, ob = (size_t)d.w * d.h * 8;
-    if (L(c).nbins >= nbins && L(c).outpix_bytes >= ob) return FL_OK;
-    hipStreamSynchronize(L(c).stream);
-    free_fb(c);
-    hipError_t e;
-    if ((e = hipMalloc(&L(c).d_front, 16 * nbins)) || (e = hipMalloc(&L(c).d_back, 16 * nbins)) ||
-        (e = hipMalloc(&L(c).d_side, 16 * nbins)) || (e = hipMalloc(&L(c).d_blur, 4 * nbins)) ||
-        (e = hipMalloc(&L(c).d_atom, 8 * nbins)) || (e = hipMalloc(&L(c).d_hot, 4 * (nbins / 16))) ||
-        (e = hipMalloc(&L(c).d_outpix, ob)) ||
-        (e = hipMalloc(&L(c).d_de_tmax, 4 * (nbins / 256 + 64))) ||
-        (e = hipMalloc(&L(c).d_de_sinv, 4 * (16 * FL_DE_MAX_RADIUS + 1))) ||
-        (e = hipMemcpyAsync(L(c).d_de_sinv, de_norms(), 4 * (16 * FL_DE_MAX_RADIUS + 1), hipMemcpyHostToDevice, L(c).stream))) {
-        free_fb(c);
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, "framebuffer allocation", __FILE__, __LINE__, e);
+    const fl_dim d = *dim = calc_dim(w, h);
+    const size_t nbins = (size_t)d.ah * d.astride, ob = (size_t)d.w * d.h * 8, nsinv = 16 * FL_DE_MAX_RADIUS + 1;
+    if (ln.nbins() >= nbins && ln.d_outpix.cap >= ob) return FL_OK;
+    hipStreamSynchronize(ln.stream);
+    ln.release_fb();
+    const char *what = "framebuffer allocation";
+    int rc;
+    if (!(rc = ln.d_front.reserve(nbins, what)) && !(rc = ln.d_back.reserve(nbins, what)) && !(rc = ln.d_side.reserve(nbins, what)) &&
+        !(rc = ln.d_blur.reserve(nbins, what)) && !(rc = ln.d_atom.reserve(nbins, what)) && !(rc = ln.d_hot.reserve(nbins / 16, what)) &&
+        !(rc = ln.d_outpix.reserve(ob, what)) && !(rc = ln.d_de_tmax.reserve(nbins / 256 + 64, what)) && !(rc = ln.d_de_sinv.reserve(nsinv, what))) {
+        const hipError_t e = hipMemcpyAsync(ln.d_de_sinv, de_norms(), 4 * nsinv, hipMemcpyHostToDevice, ln.stream);
+        if (e != hipSuccess) { (void)hipGetLastError(); rc = fail_hip(e, what, __FILE__, __LINE__); }
     }
-    L(c).nbins = nbins; L(c).outpix_bytes = ob;
-    return FL_OK;
+    if (rc) ln.release_fb();
+    return rc;
 }
 
 static bool env_on(const char *name) { const char *e = getenv(name); return e && *e && strcmp(e, "0") != 0; }
@@ -254,14 +302,13 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
         else if (nseeds == fixed + 4u * per_wave) nw = 4;
         else return fail(FL_E_INVAL, "nseeds must be nslots*64*NW + 64*256 + 65536 with NW = 4, 8 or 16", __FILE__, __LINE__);
     }
+    if (nslots < FL_NTEMPORAL && (uint32_t)nw * nslots != 4u * FL_NTEMPORAL)
+        return fail(FL_E_INVAL, "512 slots need 8-wave workgroups, 256 slots 16-wave ones (a temporal sample per four waves: 1024 in all)", __FILE__, __LINE__);
     fl_ctx *c = new fl_ctx;
     c->device = device;
     c->nw = nw;
-    if (nslots < FL_NTEMPORAL && (uint32_t)nw * nslots != 4u * FL_NTEMPORAL)
-        return fail(FL_E_INVAL, "512 slots need 8-wave workgroups, 256 slots 16-wave ones (a temporal sample per four waves: 1024 in all)", __FILE__, __LINE__);
     c->nslots = nslots;
     c->sub_log2 = nslots >= FL_NTEMPORAL ? 0u : nw == 8 ? 1u : 2u;
-    c->nwalkers = nslots * (uint32_t)nw * 64 + FL_PAL_H * 256 + FL_NOUT;
     if (const char *e = getenv("FLAME_LANES")) { const int v = atoi(e); c->nlanes = v >= 1 && v <= fl_ctx::kMaxLanes ? v : 2; }
     if (const char *e = getenv("FLAME_BIN_ROUNDS")) { int v = atoi(e); if (v >= 1 && v <= FL_BIN_R_MAX) c->bin_rounds = (uint32_t)v; }
     if (const char *e = getenv("FLAME_BIN_PARTS")) { int v = atoi(e); if (v >= 1 && v <= 64) c->bin_parts = (uint32_t)v; }
@@ -272,41 +319,25 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
     if (stream) { c->lanes[0].stream = (hipStream_t)stream; c->own_stream = false; c->nlanes = 1; }   // caller's stream: one lane
     else c->own_stream = true;
     // every failure below leaves through fl_ctx_destroy, which frees whatever exists so far
-    hipError_t e = hipSuccess;
+    const size_t nrng = (size_t)c->npoints() + FL_PAL_H * 256 + FL_NOUT;
     const char *what = "context allocation";
-    do {
-        if (c->own_stream)
-            for (int i = 0; i < c->nlanes && e == hipSuccess; ++i) e = hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking);
-        if (e) break;
-        if ((e = hipMalloc(&c->d_rng, sizeof(fl_mwc) * (size_t)c->nwalkers))) break;
-        if ((e = hipMalloc(&c->d_points, sizeof(float4) * (size_t)nslots * nw * 64))) break;
-        if ((e = hipMalloc(&c->d_counters, 8 * 4))) break;
-        for (int i = 0; i < c->nlanes && e == hipSuccess; ++i) {
-            Lane &ln = c->lanes[i];
-            if ((e = hipMalloc(&ln.d_palette, sizeof(u64) * FL_PAL_H * FL_PAL_W))) break;
-            if ((e = hipEventCreateWithFlags(&ln.ev_interp_done, hipEventDisableTiming))) break;
-            if ((e = hipEventCreateWithFlags(&ln.ev_iter_done, hipEventDisableTiming))) break;
-            if ((e = hipEventCreateWithFlags(&ln.ev_out_done, hipEventDisableTiming))) break;
-            if ((e = hipStreamCreateWithFlags(&ln.aux, hipStreamNonBlocking))) break;
-            for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-                if ((e = hipEventCreateWithFlags(&ln.ev_it[k], hipEventDisableTiming))) break;
-                e = hipEventCreateWithFlags(&ln.ev_ac[k], hipEventDisableTiming);
-            }
-            if (e) break;
-        }
-        if (e) break;
-        if ((e = hipMemcpy(c->d_rng, seeds, sizeof(fl_mwc) * (size_t)c->nwalkers, hipMemcpyHostToDevice))) break;
-        if ((e = hipMemsetD32(c->d_points, 0x7fc00000, (size_t)nslots * nw * 64 * 4))) break;
-        if ((e = hipMemset(c->d_counters, 0, 32))) break;
-        for (uint32_t i = 0; i < fl_ctx::kFrames && e == hipSuccess; ++i) {
-            if ((e = hipEventCreate(&c->ev_begin_[i]))) break;
-            e = hipEventCreate(&c->ev_end_[i]);
-        }
-    } while (0);
-    if (e != hipSuccess) {
+    const auto hip = [what](hipError_t e) { return e == hipSuccess ? (int)FL_OK : fail_hip(e, what, __FILE__, __LINE__); };
+    int rc = FL_OK;
+    for (int i = 0; i < c->nlanes && c->own_stream && !rc; ++i) rc = hip(hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking));
+    if (!rc && !(rc = c->d_rng.reserve(nrng, what)) && !(rc = c->d_points.reserve(c->npoints(), what))) rc = c->d_counters.reserve(4, what);
+    for (int i = 0; i < c->nlanes && !rc; ++i) {
+        Lane &ln = c->lanes[i];
+        if ((rc = ln.d_palette.reserve(FL_PAL_H * FL_PAL_W, what)) || (rc = hip(hipStreamCreateWithFlags(&ln.aux, hipStreamNonBlocking)))) break;
+        for (hipEvent_t *ev : ln.events()) if ((rc = hip(hipEventCreateWithFlags(ev, hipEventDisableTiming)))) break;
+    }
+    if (!rc && !(rc = hip(hipMemcpy(c->d_rng, seeds, c->d_rng.bytes(), hipMemcpyHostToDevice))) &&
+        !(rc = hip(hipMemsetD32(c->d_points, 0x7fc00000, (size_t)c->npoints() * 4)))) rc = hip(hipMemset(c->d_counters, 0, 32));
+    for (uint32_t i = 0; i < fl_ctx::kFrames && !rc; ++i)
+        if (!(rc = hip(hipEventCreate(&c->ev_begin_[i])))) rc = hip(hipEventCreate(&c->ev_end_[i]));
+    if (rc) {
         fl_ctx_destroy(c);
         (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, what, __FILE__, __LINE__, e);
+        return rc;
     }
     *out = c;
     return FL_OK;
@@ -322,46 +353,33 @@ void fl_ctx_destroy(fl_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     for (uint32_t i = 0; i < fl_ctx::kDepEvents; ++i) if (c->dep_ev[i]) hipEventDestroy(c->dep_ev[i]);
-    for (int i = 0; i < fl_ctx::kMaxLanes; ++i) {
-        if (c->lanes[i].stream) hipStreamSynchronize(c->lanes[i].stream);
-        if (c->lanes[i].aux) hipStreamSynchronize(c->lanes[i].aux);
+    for (Lane &ln : c->lanes) {
+        if (ln.stream) hipStreamSynchronize(ln.stream);
+        if (ln.aux) hipStreamSynchronize(ln.aux);
     }
-    for (int i = 0; i < fl_ctx::kMaxLanes; ++i) {
-        c->cur = i;
-        free_fb(c);
-        Lane &ln = c->lanes[i];
-        hipFree(ln.d_params); hipFree(ln.d_palette);
-        for (int k = 0; k < 2; ++k) {
-            hipFree(ln.d_log[k]); hipFree(ln.d_dir[k]);
-            if (ln.ev_it[k]) hipEventDestroy(ln.ev_it[k]);
-            if (ln.ev_ac[k]) hipEventDestroy(ln.ev_ac[k]);
-        }
-        if (ln.aux) hipStreamDestroy(ln.aux);
-        if (ln.ev_interp_done) hipEventDestroy(ln.ev_interp_done);
-        if (ln.ev_iter_done) hipEventDestroy(ln.ev_iter_done);
-        if (ln.ev_out_done) hipEventDestroy(ln.ev_out_done);
+    for (Lane &ln : c->lanes) {
+        ln.release();
         if (c->own_stream && ln.stream) hipStreamDestroy(ln.stream);
     }
-    hipFree(c->d_rng); hipFree(c->d_points); hipFree(c->d_counters); hipFree(c->d_sort);
     for (auto &p : c->pool) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (uint32_t i = 0; i < fl_ctx::kFrames; ++i) {
         if (c->ev_begin_[i]) hipEventDestroy(c->ev_begin_[i]);
         if (c->ev_end_[i]) hipEventDestroy(c->ev_end_[i]);
     }
+    delete c;                          // (with the context's own buffers)
     (void)hipGetLastError();
-    delete c;
 }
 
 int fl_ctx_sync(fl_ctx *c) { REQUIRE(c, "null ctx"); sync_all(c); return FL_OK; }
 
-// Make the current lane's stream wait for what the OTHER lane last did to state both share.
+// Make the current lane's stream wait for what the previous frame's lane last did to state both share.
 static int wait_other(fl_ctx *c, int what)
 {
     if (c->nlanes < 2) return FL_OK;
-    Lane &o = OTHER(c);
-    if (what == 0 && o.interp_rec) HIPCHK(hipStreamWaitEvent(L(c).stream, o.ev_interp_done, 0));
-    if (what == 1 && o.iter_rec) HIPCHK(hipStreamWaitEvent(L(c).stream, o.ev_iter_done, 0));
-    if (what == 2 && o.out_rec) HIPCHK(hipStreamWaitEvent(L(c).stream, o.ev_out_done, 0));
+    Lane &ln = c->lane(), &o = c->prev_lane();
+    if (what == 0 && o.interp_rec) HIPCHK(hipStreamWaitEvent(ln.stream, o.ev_interp_done, 0));
+    if (what == 1 && o.iter_rec) HIPCHK(hipStreamWaitEvent(ln.stream, o.ev_iter_done, 0));
+    if (what == 2 && o.out_rec) HIPCHK(hipStreamWaitEvent(ln.stream, o.ev_out_done, 0));
     return FL_OK;
 }
 
@@ -385,9 +403,26 @@ static int check_prog(const int32_t *p, uint32_t n)
     return FL_OK;
 }
 
+// What an op may do to the structure of the xform records (prog passed check_prog): an opacity op writes word 15 of a selectable
+// record (the final xform has no opacity); a structure word — FL_OP_CONST: xform word 14 (nvar | post << 8 | opacity << 9) or a
+// variation number — lies inside the records, and word 14 carries nothing above bit 9 and no opacity flag on the final xform.
+// iter_spec() relies on this.
+static int check_structure_op(const int32_t *prog, const int32_t *o)
+{
+    const int xs = prog[6], nxf = prog[1], nrec = nxf + prog[2], rel = o[1] - prog[5];
+    if (o[0] == FL_OP_OPACITY) REQUIRE(rel >= 0 && rel / xs < nxf && rel % xs == 15, "opacity op must write word 15 of a selectable xform record");
+    if (o[0] != FL_OP_CONST) return FL_OK;
+    REQUIRE(rel >= 0 && rel / xs < nrec, "structure word outside the xform records");
+    if (rel % xs == 14) {
+        REQUIRE((o[2] >> 10) == 0, "bad structure word");
+        REQUIRE(((o[2] >> 9) & 1) == 0 || rel / xs < nxf, "the final xform has no opacity");
+    }
+    return FL_OK;
+}
+
 // Structure tables of the per-genome kernel (rtc.hip) from a program and its op list: per record the variation count, post and
 // opacity flags of its structure word (14) and its variation numbers in order (-1: no op names one).  The callers have checked
-// that every FL_OP_CONST writes inside the xform records.
+// every op with check_structure_op.
 static IterSpec iter_spec(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops)
 {
     const int xo = prog[5], xs = prog[6], vs = prog[7], nrec = prog[1] + prog[2];
@@ -435,6 +470,8 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
         const int32_t *o = ops + 4 * i;
         REQUIRE(o[0] >= FL_OP_SPLINE && o[0] <= FL_OP_CHAOS_CDF, "bad op kind");
         REQUIRE(o[1] >= 0 && (uint32_t)o[1] < ps, "op destination out of range");
+        if ((rc = check_structure_op(prog, o))) return rc;
+        const int rel = o[1] - xo;
         if (o[0] != FL_OP_CONST) {
             // every word an op writes and every spline row it reads must lie inside the block / row table
             uint32_t ndst = 1, nsrc = 1;
@@ -448,11 +485,11 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
             case FL_OP_PERSP: ndst = 3; break;
             case FL_OP_CHAOS_CDF: {     // row p of the chaos matrix, from the nxf weight rows and nxf chaos rows
                 REQUIRE(has_chaos, "chaos op in a program without a chaos matrix");
-                const int nx = prog[1], rel = o[1] - prog[FL_PROG_HDR];
+                const int nx = prog[1], crel = o[1] - prog[FL_PROG_HDR];
                 REQUIRE(o[3] >= 0 && (o[3] & 0xff) == nx, "bad chaos row length");
-                REQUIRE(rel >= 0 && rel < nx * nx && rel % nx == 0, "chaos op must write a row of the chaos matrix");
+                REQUIRE(crel >= 0 && crel < nx * nx && crel % nx == 0, "chaos op must write a row of the chaos matrix");
                 REQUIRE((uint32_t)(o[3] >> 8) + (uint32_t)nx <= nrows, "op row out of range");
-                ++chaos_ops[rel / nx];
+                ++chaos_ops[crel / nx];
                 ndst = nsrc = (uint32_t)nx;
             } break;
             default: break;
@@ -460,21 +497,14 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
             REQUIRE((uint32_t)o[1] + ndst <= ps, "op destination out of range");
             REQUIRE(o[2] >= 0 && (uint32_t)o[2] + nsrc <= nrows, "op row out of range");
             if (o[0] == FL_OP_RATIO2 || o[0] == FL_OP_PERSP) REQUIRE(o[3] >= 0 && (uint32_t)o[3] < nrows, "op row out of range");
-            if (o[0] == FL_OP_OPACITY) {        // word 15 of a selectable record (the final xform has no opacity)
-                const int rel = o[1] - xo;
-                REQUIRE(rel >= 0 && rel / xs < prog[1] && rel % xs == 15, "opacity op must write word 15 of a selectable xform record");
-                ++opac_ops[rel / xs];
-            }
+            if (o[0] == FL_OP_OPACITY) ++opac_ops[rel / xs];
             continue;
         }
-        // structure words: xform word 14 (nvar | post << 8 | opacity << 9) or a variation number
-        const int rel = o[1] - xo;
-        REQUIRE(rel >= 0 && rel / xs < nrec, "structure word outside the xform records");
+        // structure words, beyond check_structure_op: the variations fit the record, every variation is a known one
         const int w = rel % xs;
         if (w == 14) {
             const int nv = o[2] & 0xff;
-            REQUIRE(FL_XF_HDR + nv * vs <= xs && (o[2] >> 10) == 0, "bad variation count");
-            REQUIRE(((o[2] >> 9) & 1) == 0 || rel / xs < prog[1], "the final xform has no opacity");
+            REQUIRE(FL_XF_HDR + nv * vs <= xs, "bad variation count");
             nvar_seen[rel / xs] = nv;
             opac_seen[rel / xs] = (o[2] >> 9) & 1;
         } else {
@@ -521,7 +551,7 @@ int fl_genome_create(fl_ctx *c, const int32_t *prog, uint32_t nprog, const int32
     if (e != hipSuccess) {
         fl_genome_destroy(g);
         (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FL_E_NOMEM : FL_E_HIP, "genome allocation", __FILE__, __LINE__, e);
+        return fail_hip(e, "genome allocation", __FILE__, __LINE__);
     }
     *out = g;
     return FL_OK;
@@ -552,11 +582,12 @@ int fl_genome_upload(fl_ctx *c, fl_genome *g, const float *times, const float *k
     memcpy(h + 2 * nb, pal_rgba, pb);
     memcpy(h + 2 * nb + pb, pal_times, tb);
     { int rc = wait_other(c, 0); if (rc) return rc; }     // the other lane's interp still reads these buffers
-    HIPCHK(hipMemcpyAsync(g->d_times, h, nb, hipMemcpyHostToDevice, L(c).stream));
-    HIPCHK(hipMemcpyAsync(g->d_knots, h + nb, nb, hipMemcpyHostToDevice, L(c).stream));
-    HIPCHK(hipMemcpyAsync(g->d_pals, h + 2 * nb, pb, hipMemcpyHostToDevice, L(c).stream));
-    HIPCHK(hipMemcpyAsync(g->d_ptimes, h + 2 * nb + pb, tb, hipMemcpyHostToDevice, L(c).stream));
-    HIPCHK(hipEventRecord(g->ev_stage[slot], L(c).stream));
+    hipStream_t st = c->lane().stream;
+    HIPCHK(hipMemcpyAsync(g->d_times, h, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g->d_knots, h + nb, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g->d_pals, h + 2 * nb, pb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g->d_ptimes, h + 2 * nb + pb, tb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(g->ev_stage[slot], st));
     g->npal = npal;
     return FL_OK;
 }
@@ -569,8 +600,8 @@ int fl_frame_begin(fl_ctx *c, uint32_t *frame_id)
     const uint32_t k = id % fl_ctx::kFrames;
     c->cur = (int)(id % (uint32_t)c->nlanes);             // consecutive frames go round the lanes
     c->frame_lane[k] = (uint32_t)c->cur;
-    HIPCHK(hipEventRecord(c->ev_begin_[k], L(c).stream));
-    HIPCHK(hipEventRecord(c->ev_end_[k], L(c).stream));       // moved forward by fl_output
+    HIPCHK(hipEventRecord(c->ev_begin_[k], c->lane().stream));
+    HIPCHK(hipEventRecord(c->ev_end_[k], c->lane().stream));       // moved forward by fl_output
     *frame_id = id;
     return FL_OK;
 }
@@ -579,110 +610,65 @@ int fl_interp(fl_ctx *c, fl_genome *g, uint32_t w, uint32_t h, float ts, float t
 {
     REQUIRE(c && g && g->npal, "genome not uploaded");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
+    Lane &ln = c->lane();
+    const fl_dim d = calc_dim(w, h);
     // One parameter block per walker slot: slot s iterates temporal sample s of nslots, evaluated
     // at ts + s*td/nslots, so that every temporal sample receives the same number of iterations
     // whatever the slot count (the reference: one block column per each of its 1024 temporal
     // samples, cuburn/render.py:303-307,343-346; cuburn/code/iter.py:165,184).
     const size_t need = (size_t)c->ntemporal() * g->pstride;     // (workgroups in sub-blocks: two or four blocks per slot)
-    if (need > L(c).params_floats) {
-        HIPCHK(hipStreamSynchronize(L(c).stream));
-        hipFree(L(c).d_params); L(c).d_params = nullptr; L(c).params_floats = 0;
-        HIPCHK(hipMalloc(&L(c).d_params, sizeof(float) * need));
-        L(c).params_floats = need; L(c).params_serial = 0;
-    }
-    fl_mwc *rng_pal = c->d_rng + (size_t)c->nslots * c->nw * 64;
-    { int rc = wait_other(c, 0); if (rc) return rc; }     // palette RNG states are shared
-    launch_interp_palette(L(c).stream, rng_pal, g->d_ptimes, g->d_pals, ts, td / FL_PAL_H, L(c).d_palette);
-    launch_interp_params(L(c).stream, L(c).d_params, g->d_times, g->d_knots, g->d_ops, g->nops, g->pstride,
-                         c->ntemporal(), ts, td / (float)c->ntemporal(), d, L(c).params_serial != g->serial);
-    L(c).params_serial = g->serial;
+    if (need > ln.d_params.cap) ln.params_serial = 0;
+    int rc = ln.d_params.reserve(need, "parameter blocks", [&ln] { return ln.quiesce(false); });
+    if (rc) return rc;
+    if ((rc = wait_other(c, 0))) return rc;                 // palette RNG states are shared
+    launch_interp_palette(ln.stream, c->rng_pal(), g->d_ptimes, g->d_pals, ts, td / FL_PAL_H, ln.d_palette);
+    launch_interp_params(ln.stream, ln.d_params, g->d_times, g->d_knots, g->d_ops, g->nops, g->pstride,
+                         c->ntemporal(), ts, td / (float)c->ntemporal(), d, ln.params_serial != g->serial);
+    ln.params_serial = g->serial;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(L(c).ev_interp_done, L(c).stream));
-    L(c).interp_rec = true;
+    HIPCHK(hipEventRecord(ln.ev_interp_done, ln.stream));
+    ln.interp_rec = true;
     return FL_OK;
 }
 
-static int do_clear(fl_ctx *c, const fl_dim &d, bool reset_points)
+static int do_clear(fl_ctx *c, Lane &ln, const fl_dim &d, bool reset_points)
 {
     size_t nbins = (size_t)d.ah * d.astride;
     // cuburn/render.py:321-328
-    launch_clear_frame(L(c).stream, L(c).d_front, L(c).d_atom, L(c).d_hot, c->d_counters, c->d_points, (uint32_t)nbins,
-                       reset_points ? c->nslots * (uint32_t)c->nw * 64u : 0u);
+    launch_clear_frame(ln.stream, ln.d_front, ln.d_atom, ln.d_hot, c->d_counters, c->d_points, (uint32_t)nbins,
+                       reset_points ? c->npoints() : 0u);
     HIPCHK(hipGetLastError());
     return FL_OK;
 }
 
-// Maximum write-enabled rounds of one binned launch (bounds the sample log: nslots*NT*4 B per round).  The reference's batches grow
-// 1024, 1536, 2304, ... rounds (cuburn/render.py:338-369); here they stop growing at 1024 — equal launches overlap best in the
-// lane's two-stream pipeline (cfg3, 2731 rounds: 1024 + 1024 + 683 is 1.7 % faster than 1024 + 1536 + 171) — unless following the
-// reference's schedule up to 2304 rounds saves a launch, i.e. a flush and a zeroed + added tile per workgroup (cfg5, 4096 rounds:
-// 1024 + 1536 + 1536 instead of 4 x 1024, frame 37.0 -> 36.1 ms; profiles/r05_launch_cap.txt).
-#define FL_BIN_MAX_ROUNDS 1024u
-#define FL_BIN_MAX_ROUNDS_LONG 2304u
-
-// Tile geometry of the binned accumulate for one image, and what a batch takes in the sample log.
-struct BinLayout {
-    bool wide;            // 256x64 tiles with separately staged tile numbers (else 128x64)
-    uint32_t tile_w, tiles_x, nbins;
-    size_t region;        // 32-bit words of the log per batch
-};
-static BinLayout bin_layout(const fl_ctx *c, const fl_dim &d)
+// The log + directory set `buf` of the lane, large enough for a launch of `write_rounds` write-enabled rounds.
+static int ensure_binned(fl_ctx *c, Lane &ln, const fl_dim &d, uint32_t write_rounds, int buf, BinLayout *layout, uint32_t *nbatch_total)
 {
-    BinLayout b;
-    const uint32_t nt = (uint32_t)c->nw * 64;
-    // 128x64 tiles while their number fits the 11 bits left in a staged record (up to 4K);
-    // larger images use 256x64 tiles with separately staged tile numbers
-    const uint32_t rows = (d.ah + FL_TILE_H - 1) / FL_TILE_H;
-    b.wide = ((d.astride + 127) / 128) * rows > FL_MAX_BINS || c->env_bin_wide;
-    b.tile_w = b.wide ? (1u << FL_TILE_W_WIDE_LOG2) : 128u;
-    b.tiles_x = (d.astride + b.tile_w - 1) / b.tile_w;
-    b.nbins = b.tiles_x * rows;
-    // a region per batch — bin_rounds * nt records, one per word (256x64 tiles) or three per 64-bit word (flame_device.h)
-    b.region = !b.wide && FL_LOG_PACK3 ? 2 * (size_t)fl_pack3_words(c->bin_rounds * nt) : (size_t)c->bin_rounds * nt;
-    return b;
-}
-
-static int ensure_binned(fl_ctx *c, const fl_dim &d, uint32_t write_rounds, int buf, BinLayout *layout, uint32_t *nbatch_total)
-{
-    const BinLayout b = *layout = bin_layout(c, d);
+    const BinLayout b = *layout = c->layout(d);
     if (b.nbins > FL_MAX_BINS_WIDE) return fail(FL_E_UNSUPPORTED, "image too large for the binned accumulate (> 8191 tiles of 256x64)", __FILE__, __LINE__);
-    const uint32_t per_slot = (write_rounds + c->bin_rounds - 1) / c->bin_rounds;
-    *nbatch_total = per_slot * c->nslots;
-    size_t lw = (size_t)*nbatch_total * b.region + 8, dw = (size_t)b.nbins * *nbatch_total;
-    if (lw > L(c).log_words[buf]) {
-        HIPCHK(hipStreamSynchronize(L(c).stream)); HIPCHK(hipStreamSynchronize(L(c).aux));
-        hipFree(L(c).d_log[buf]); L(c).d_log[buf] = nullptr; L(c).log_words[buf] = 0;
-        HIPCHK(hipMalloc(&L(c).d_log[buf], lw * 4));
-        L(c).log_words[buf] = lw;
-    }
-    if (dw > L(c).dir_words[buf]) {
-        HIPCHK(hipStreamSynchronize(L(c).stream)); HIPCHK(hipStreamSynchronize(L(c).aux));
-        hipFree(L(c).d_dir[buf]); L(c).d_dir[buf] = nullptr; L(c).dir_words[buf] = 0;
-        HIPCHK(hipMalloc(&L(c).d_dir[buf], dw * 4));
-        L(c).dir_words[buf] = dw;
-    }
-    return FL_OK;
+    const BinSet s = bin_set(b, write_rounds, c->bin_rounds, c->nslots);
+    *nbatch_total = s.nbatch;
+    const auto quiesce = [&ln] { return ln.quiesce(true); };
+    if (int rc = ln.d_log[buf].reserve(s.log_words, "sample log", quiesce)) return rc;
+    return ln.d_dir[buf].reserve(s.dir_words, "sample log directory", quiesce);
 }
 
 // One iterate launch and (binned mode) its tile accumulate.  `buf` selects the log / directory set;
 // `drain` is the stream the accumulate runs on: the lane's own stream, or its aux stream when the
 // launches of a frame are pipelined (then the accumulate waits for this iterate through ev_it[buf]).
-static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nrounds, uint32_t fuse, bool count, int acc = 0,
+static int do_iter_launch(fl_ctx *c, Lane &ln, fl_genome *g, const fl_dim &d, uint32_t nrounds, uint32_t fuse, bool count, int acc = 0,
                           int buf = 0, hipStream_t drain = nullptr)
 {
-    if (!drain) drain = L(c).stream;
+    if (!drain) drain = ln.stream;
     BinLayout bl = {};
     uint32_t nbatch_total = 0;
     if (acc == FL_ACCUM_BINNED) {
         if (nrounds <= fuse) return fail(FL_E_INVAL, "binned launch needs write-enabled rounds", __FILE__, __LINE__);
-        int rc = ensure_binned(c, d, nrounds - fuse, buf, &bl, &nbatch_total);
+        int rc = ensure_binned(c, ln, d, nrounds - fuse, buf, &bl, &nbatch_total);
         if (rc) return rc;
     }
-    const uint32_t tiles_x = bl.tiles_x, nbins = bl.nbins;
-    const bool wide = bl.wide;
-    EvPair *e = ev_pair(c, c->iter_ev);
-    const int kacc = acc == FL_ACCUM_BINNED && wide ? 3 : acc;
+    EvPair *e = ev_acquire(c, c->iter_ev);      // recorded by the kernel launch itself (hipExtLaunchKernelGGL)
+    const int kacc = acc == FL_ACCUM_BINNED && bl.wide ? 3 : acc;
     // the kernel specialised for this genome's structure (compiled on first use, rtc.hip); the
     // interpreter kernel if hipRTC is unavailable, switched off, or the compile failed
     hipFunction_t fn = nullptr;
@@ -703,41 +689,62 @@ static int do_iter_launch(fl_ctx *c, fl_genome *g, const fl_dim &d, uint32_t nro
         fn = slot;
     }
     (fn ? c->n_spec_launch : c->n_interp_launch) += 1;
-    const IterLaunch il = {c->nw, count, kacc, c->nslots, g->d_prog, L(c).d_params, L(c).d_palette, c->d_rng, c->d_points,
-                           L(c).d_hot, L(c).d_atom, (float *)L(c).d_front, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
-                           tiles_x, nbins, c->bin_rounds, nbatch_total, L(c).d_log[buf], L(c).d_dir[buf],
+    const IterLaunch il = {c->nw, count, kacc, c->nslots, g->d_prog, ln.d_params, ln.d_palette, c->rng_walk(), c->d_points,
+                           ln.d_hot, ln.d_atom, (float *)ln.d_front.p, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
+                           bl.tiles_x, bl.nbins, c->bin_rounds, nbatch_total, ln.d_log[buf], ln.d_dir[buf],
                            e ? e->a : nullptr, e ? e->b : nullptr, c->sub_log2, g->spec.chaos != 0};
-    launch_iter(L(c).stream, il, fn);
+    launch_iter(ln.stream, il, fn);
     c->round_counter += nrounds;
     HIPCHK(hipGetLastError());
     if (acc == FL_ACCUM_BINNED) {
-        if (drain != L(c).stream) {
-            HIPCHK(hipEventRecord(L(c).ev_it[buf], L(c).stream));
-            HIPCHK(hipStreamWaitEvent(drain, L(c).ev_it[buf], 0));
+        if (drain != ln.stream) {
+            HIPCHK(hipEventRecord(ln.ev_it[buf], ln.stream));
+            HIPCHK(hipStreamWaitEvent(drain, ln.ev_it[buf], 0));
         }
         EvPair *e2 = ev_begin_on(c, c->accum_ev, drain);
-        // workgroups per tile: enough of them to fill the chip several times over (~8192 in all),
-        // no more — every workgroup zeroes and drains a whole LDS tile whatever its share of records
-        // (256x64 tiles, one workgroup per CU: twice as many — a dense region then spreads over more
-        // workgroups; cfg5 8K: 3 per tile 20.7 ms of accumulate per frame, 8 per tile 16.2, 12: 18.2)
-        // (round 5: with the ganged tile order of images of more than 512 tiles — launch_accum_tiles — six per tile at 4K and 8K:
-        // 507 / 531 / 619 us per 4K launch with 6 / 8 / 12, 2187 / 2410 / 2677 at 8K; profiles/r05_bin_parts.txt)
-        uint32_t parts = c->bin_parts ? c->bin_parts : nbins > 512u ? ((wide ? 12800u : 6400u) + nbins / 2u) / nbins : (wide ? 16384u : 8192u) / nbins;
-        parts = parts < 1u ? 1u : parts > (c->bin_parts ? 64u : 16u) ? (c->bin_parts ? 64u : 16u) : parts;
-        launch_accum_tiles(drain, L(c).d_log[buf], L(c).d_dir[buf], L(c).d_palette, L(c).d_atom, (float *)L(c).d_front, tiles_x, nbins,
-                           parts, nbatch_total, c->bin_rounds * (uint32_t)c->nw * 64, c->nslots, d.astride, d.ah, wide);
+        launch_accum_tiles(drain, ln.d_log[buf], ln.d_dir[buf], ln.d_palette, ln.d_atom, (float *)ln.d_front.p, bl.tiles_x, bl.nbins,
+                           accum_parts(bl.nbins, bl.wide, c->bin_parts), nbatch_total, c->bin_rounds * (uint32_t)c->nw * 64, c->nslots,
+                           d.astride, d.ah, bl.wide);
         ev_end_on(e2, drain);
         HIPCHK(hipGetLastError());
     }
     return FL_OK;
 }
 
-static int do_flush(fl_ctx *c, const fl_dim &d, bool use_hot = true, hipStream_t st = nullptr)
+static int do_flush(fl_ctx *c, Lane &ln, const fl_dim &d, bool use_hot = true, hipStream_t st = nullptr)
 {
-    if (!st) st = L(c).stream;
+    if (!st) st = ln.stream;
     EvPair *e = ev_begin_on(c, c->flush_ev, st);
-    launch_flush(st, L(c).d_atom, L(c).d_front, L(c).d_hot, d.ah * d.astride, use_hot);
+    launch_flush(st, ln.d_atom, ln.d_front, ln.d_hot, d.ah * d.astride, use_hot);
     ev_end_on(e, st);
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+// Run what the filter chain deferred: the `yuv`, or the DE — its eight per-direction kernels (de.hip) are all queued here, now
+// that the tail is known: the first normalises the accumulator in d_front as it stages it, the result goes through d_back and
+// ends in d_front, un-normalised (+ the tail's tone filters) by the last.
+static int flush_pending(fl_ctx *c, Lane &ln)
+{
+    Pending &pd = ln.pend;
+    if (!pd.yuv && !pd.de) return FL_OK;
+    if (pd.yuv) {
+        launch_yuv_to_rgb(ln.stream, pd.dim, ln.d_back, ln.d_front);
+        swap(ln.d_front, ln.d_back);
+    }
+    if (pd.de) {
+        const Bilateral &b = pd.bl;
+        const auto dir = [&](int pat, float4 *dst, const float4 *src, const DeTail *tail) {
+            launch_de_dir(ln.stream, pd.dim, pat, dst, src, b.k7, b.sstd, b.cstd, b.dstd, b.dpow, b.gspeed, pd.in_mode, tail);
+        };
+        EvPair *e = ev_begin_on(c, c->de_ev, ln.stream);            // the DE proper: fl_timings_detail[4], whoever flushes it
+        float4 *Na = ln.d_back, *Nb = ln.d_front;
+        dir(0, Na, Nb, nullptr);
+        for (int pat = 1; pat < 7; ++pat) { dir(pat, Nb, Na, nullptr); std::swap(Na, Nb); }
+        dir(7, ln.d_front, Na, &pd.tail);
+        ev_end_on(e, ln.stream);
+    }
+    pd.clear();
     HIPCHK(hipGetLastError());
     return FL_OK;
 }
@@ -747,76 +754,60 @@ int fl_iterate(fl_ctx *c, fl_genome *g, uint32_t w, uint32_t h, double nsamples,
 {
     REQUIRE(c && g, "null argument");
     REQUIRE(accum_mode == FL_ACCUM_ATOMIC || accum_mode == FL_ACCUM_BINNED || accum_mode == 2, "bad accumulation mode");
-    REQUIRE(L(c).params_floats >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
+    Lane &ln = c->lane();
+    REQUIRE(ln.d_params.cap >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
     if (rc) return rc;
-    flush_pending(c);
+    if ((rc = flush_pending(c, ln))) return rc;
     if ((rc = wait_other(c, 1))) return rc;                 // walkers / RNG states are shared between lanes
-    if ((rc = do_clear(c, d, true))) return rc;
-    const uint32_t nt = (uint32_t)c->nw * 64;
-    const double per_round = (double)c->nslots * nt;
+    if ((rc = do_clear(c, ln, d, true))) return rc;
+    const double per_round = (double)c->npoints();
     uint64_t rounds = (uint64_t)ceil(nsamples / per_round);
     if (rounds == 0) rounds = 1;
     if (nsamples_run) *nsamples_run = (uint64_t)(rounds * per_round);
-    // cuburn/render.py:338-369: launch batches grow 4, 6, 9, 13, ... (x 256 rounds), each
-    // followed by a flush; the first batch also carries the fuse rounds.  The reference alternates
-    // two streams so that flush k overlaps iter k+1 (render.py:358-369).  Here, when a binned frame
+    // The launches of the frame (launch_plan.h), each followed by a flush; the first also carries the fuse rounds.  The long cap
+    // saves a launch but sizes the (grow-only) sample log and directory for the longest launch: it is taken only if what
+    // would have to be allocated beyond the short cap's buffers fits the device's free memory with a margin — a frame that rendered
+    // with 1024-round logs must not start failing on a shared or smaller device because a schedule saves it a flush.
+    const bool binned = accum_mode == FL_ACCUM_BINNED;
+    LaunchPlan plan = binned ? launch_schedule(rounds, c->sub_log2, c->nw, c->launch_rounds) : launch_schedule_under(rounds, c->sub_log2, FL_NO_CAP);
+    if (binned && !c->launch_rounds && plan.cap > launch_cap(false, c->sub_log2, c->nw)) {
+        const size_t need = bin_set(c->layout(d), std::min(rounds, plan.cap), c->bin_rounds, c->nslots).bytes();
+        size_t grow = 0, mfree = 0, mtotal = 0;
+        for (int b = 0; b < 2; ++b) {                                            // (two sets: launches of a frame are pipelined)
+            const size_t have = ln.d_log[b].bytes() + ln.d_dir[b].bytes();
+            if (need > have) grow += need - have;
+        }
+        if (grow && (hipMemGetInfo(&mfree, &mtotal) != hipSuccess || grow + (size_t(1) << 30) > mfree))
+            plan = launch_schedule_under(rounds, c->sub_log2, launch_cap(false, c->sub_log2, c->nw));
+    }
+    // The reference alternates two streams so that flush k overlaps iter k+1 (render.py:358-369).  Here, when a binned frame
     // needs several launches, the iterate kernels stay on the lane's stream and the tile accumulate
     // + flush of each launch go to the lane's aux stream, with two log / directory sets: launch k+1
     // iterates while launch k drains.  (Both kernels want the whole chip, so this buys little —
     // DESIGN.md §4.1 — but it costs nothing and hides the drains' launch gaps.)
-    // (workgroups in sub-blocks have a half or a quarter of the walkers of their plain geometry: their rounds count double / fourfold
-    // for the same samples per launch, i.e. the same log, flush schedule and number of launches)
-    const uint64_t unit = 256ull << c->sub_log2;
-    auto launches_with = [rounds, unit](uint64_t cap_) { uint32_t nl = 0; for (uint64_t r = rounds, b = 4; r; b += b / 2) { r -= std::min(std::min(r, b * unit), cap_); ++nl; } return nl; };
-    // (16-wave workgroups: the long cap stops at the 1536 rounds that tests/test_gpu_parity.py::test_long_launch_log_beyond_4gb... pins —
-    // a 2304-round launch of the 8K geometry is a 14.5 GB log whose record indices pass 2^31)
-    const uint64_t cap_short = (uint64_t)FL_BIN_MAX_ROUNDS << c->sub_log2;
-    uint64_t cap_long = (uint64_t)(c->nw == 16 ? 1536u : FL_BIN_MAX_ROUNDS_LONG) << c->sub_log2;
-    // The long cap saves a launch but sizes the (grow-only) sample log and directory for the longest launch: it is taken only if what
-    // would have to be allocated beyond the short cap's buffers fits the device's free memory with a margin — a frame that rendered
-    // with 1024-round logs must not start failing on a shared or smaller device because a schedule saves it a flush.
-    if (accum_mode == FL_ACCUM_BINNED && !c->launch_rounds && launches_with(cap_long) < launches_with(cap_short)) {
-        const BinLayout bl = bin_layout(c, d);
-        const size_t nb_long = (size_t)((std::min(rounds, cap_long) + c->bin_rounds - 1) / c->bin_rounds) * c->nslots;
-        const size_t need = (nb_long * bl.region + 8 + (size_t)bl.nbins * nb_long) * 4;      // one log + directory set, bytes
-        size_t have = 0, grow = 0;
-        for (int b = 0; b < 2; ++b) {                                            // (two sets: launches of a frame are pipelined)
-            have = (L(c).log_words[b] + L(c).dir_words[b]) * 4;
-            if (need > have) grow += need - have;
-        }
-        size_t mfree = 0, mtotal = 0;
-        if (grow && (hipMemGetInfo(&mfree, &mtotal) != hipSuccess || grow + (size_t(1) << 30) > mfree)) cap_long = cap_short;
-    }
-    const uint64_t cap = accum_mode != FL_ACCUM_BINNED ? ~0ull : c->launch_rounds ? c->launch_rounds :
-                         launches_with(cap_long) < launches_with(cap_short) ? cap_long : cap_short;
-    const uint32_t nlaunch = launches_with(cap);
-    const bool pipelined = accum_mode == FL_ACCUM_BINNED && nlaunch > 1 && !c->env_no_intra;
-    hipStream_t drain = pipelined ? L(c).aux : L(c).stream;
-    uint64_t batch = 4;
+    const bool pipelined = binned && plan.rounds.size() > 1 && !c->env_no_intra;
+    hipStream_t drain = pipelined ? ln.aux : ln.stream;
     uint32_t k = 0;
-    while (rounds) {
-        const uint64_t n = std::min(std::min(rounds, batch * unit), cap);
+    for (const uint32_t n : plan.rounds) {
         const uint32_t f = k == 0 ? fuse : 0;
         const int buf = pipelined ? (int)(k & 1u) : 0;
         // the drains of launch k-2 read this log / directory set: they must be done before it is rewritten
-        if (pipelined && k >= 2) HIPCHK(hipStreamWaitEvent(L(c).stream, L(c).ev_ac[buf], 0));
-        if ((rc = do_iter_launch(c, g, d, (uint32_t)n + f, f, false, accum_mode, buf, drain))) return rc;
-        if ((rc = do_flush(c, d, accum_mode != FL_ACCUM_BINNED, drain))) return rc;
-        if (pipelined) HIPCHK(hipEventRecord(L(c).ev_ac[buf], drain));
-        rounds -= n;
-        batch += batch / 2;
+        if (pipelined && k >= 2) HIPCHK(hipStreamWaitEvent(ln.stream, ln.ev_ac[buf], 0));
+        if ((rc = do_iter_launch(c, ln, g, d, n + f, f, false, accum_mode, buf, drain))) return rc;
+        if ((rc = do_flush(c, ln, d, !binned, drain))) return rc;
+        if (pipelined) HIPCHK(hipEventRecord(ln.ev_ac[buf], drain));
         ++k;
     }
     // the walkers are free once the last iterate kernel has run (the drain kernels that follow
     // touch only this lane's buffers)
-    HIPCHK(hipEventRecord(L(c).ev_iter_done, L(c).stream));
-    L(c).iter_rec = true;
+    HIPCHK(hipEventRecord(ln.ev_iter_done, ln.stream));
+    ln.iter_rec = true;
     if (pipelined) {                    // whatever comes next on this lane's stream sees the finished accumulator
-        HIPCHK(hipStreamWaitEvent(L(c).stream, L(c).ev_ac[(k - 1) & 1u], 0));
-        if (k >= 2) HIPCHK(hipStreamWaitEvent(L(c).stream, L(c).ev_ac[k & 1u], 0));
+        HIPCHK(hipStreamWaitEvent(ln.stream, ln.ev_ac[(k - 1) & 1u], 0));
+        if (k >= 2) HIPCHK(hipStreamWaitEvent(ln.stream, ln.ev_ac[k & 1u], 0));
     }
     return FL_OK;
 }
@@ -828,133 +819,81 @@ static void gauss7(float stdev, float *c)      // cuburn/filters.py:11-16
     for (int i = 0; i < 7; ++i) c[i] /= s;
 }
 
-// The filter entry point defers two cheap per-pixel steps so that the NEXT call can take them
-// along in one pass (cuburn's default chains are yuv -> bilateral -> logscale -> colorclip /
-// smearclip): `yuv` directly in front of `bilateral` becomes part of the DE's preparation pass,
-// and the DE's final un-normalising pass takes a following `logscale` and `colorclip` with it.
-// Anything else that looks at the buffers (another filter, output, the debug taps, the next
-// frame) first runs what is pending, so the observable behaviour is that of the separate kernels
-// (the fused kernels run the same per-pixel device functions in the same order).
-// The pending end of the DE: un-normalise (+ logscale if one was deferred, + colorclip if `clip` is
-// given) into d_front — through the last direction's kernel when that is what is pending.
-static void run_de_finish(fl_ctx *c, const float *clip)
+// What fl_filter refuses, found before it touches anything: an unknown id, too few scalars (or none to read), a bad `de` radius / curve.
+static int check_filter(int id, const float *p, uint32_t np)
 {
-    Lane &ln = L(c);
-    // the eight per-direction kernels of de.hip, all queued here (the tail is known now): the accumulator in d_front goes through
-    // d_back and ends in d_front
-    DeTail t = {ln.pend_log ? 1 : 0, ln.pend_k1, ln.pend_k2, clip ? 1 : 0, clip ? clip[0] : 0.f, clip ? clip[1] : 0.f,
-                clip ? clip[2] : 0.f, clip ? clip[3] : 0.f, clip ? clip[4] : 0.f};
-    EvPair *e = ev_begin(c, c->de_ev);                               // the DE proper: fl_timings_detail[4], whoever flushes it
-    float4 *Na = ln.d_back, *Nb = ln.d_front;
-    launch_de_dir(ln.stream, ln.pend_dim, 0, Na, Nb, ln.pend_k7, ln.pend_dp[0], ln.pend_dp[1], ln.pend_dp[2], ln.pend_dp[3], ln.pend_dp[4], ln.pend_in_mode, nullptr);
-    for (int pat = 1; pat < 7; ++pat) {
-        launch_de_dir(ln.stream, ln.pend_dim, pat, Nb, Na, ln.pend_k7, ln.pend_dp[0], ln.pend_dp[1], ln.pend_dp[2], ln.pend_dp[3], ln.pend_dp[4]);
-        std::swap(Na, Nb);
+    static const struct { uint32_t np; const char *msg; } need[] = {
+        {0, ""}, {5, "bilateral needs sstd,cstd,dstd,dpow,gspeed"}, {2, "logscale needs k1,k2"},
+        {5, "colorclip needs vib,highpow,gam,lin,lingam"}, {4, "smearclip needs width,gam_m_1,lin,lingam"}, {1, "haloclip needs gam_m_1"},
+        {4, "plainclip needs gam_m_1,lin,lingam,brightness"}, {1, "logencode needs degamma"}, {3, "de needs R,Rmin,curve"}};
+    if (id < FL_FILT_YUV || id > FL_FILT_DE) return fail(FL_E_UNSUPPORTED, "unknown filter id", __FILE__, __LINE__);
+    REQUIRE(np >= need[id].np, need[id].msg);
+    REQUIRE(p || !need[id].np, "null filter scalars");
+    if (id == FL_FILT_DE) {
+        REQUIRE(!(p[0] > (float)FL_DE_MAX_RADIUS), "de: R above 96 px");
+        REQUIRE(p[2] > 0.0f, "de: curve must be > 0");
     }
-    launch_de_dir(ln.stream, ln.pend_dim, 7, ln.d_front, Na, ln.pend_k7, ln.pend_dp[0], ln.pend_dp[1], ln.pend_dp[2], ln.pend_dp[3], ln.pend_dp[4], 0, &t);
-    ev_end(c, e);
-    ln.pend_finish = ln.pend_log = false;
-}
-
-static void flush_pending(fl_ctx *c)
-{
-    Lane &ln = L(c);
-    if (ln.pend_yuv) {
-        launch_yuv_to_rgb(ln.stream, ln.pend_dim, ln.d_back, ln.d_front);
-        std::swap(ln.d_front, ln.d_back);
-        ln.pend_yuv = false;
-    }
-    if (ln.pend_finish) run_de_finish(c, nullptr);
+    return FL_OK;
 }
 
 int fl_filter(fl_ctx *c, int id, uint32_t w, uint32_t h, const float *p, uint32_t np)
 {
     REQUIRE(c, "null ctx");
-    HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    int rc = check_filter(id, p, np);
     if (rc) return rc;
-    hipStream_t st = L(c).stream;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim d;
+    if ((rc = ensure_fb(ln, w, h, &d))) return rc;
+    hipStream_t st = ln.stream;
     float k7[7];
     EvPair *e = ev_begin(c, c->filt_ev);
-    switch (id) {
-    case FL_FILT_YUV:
-        flush_pending(c);
-        L(c).pend_yuv = true; L(c).pend_dim = d;             // runs with the next call
-        break;
-    case FL_FILT_BILATERAL: {            // cuburn/filters.py:62-95
-        REQUIRE(np >= 5, "bilateral needs sstd,cstd,dstd,dpow,gspeed");
-        gauss7(1.0f, k7);
-        if (L(c).pend_finish) flush_pending(c);
-        // One kernel per direction (de.hip), all eight deferred: the first normalises the accumulator as it stages it (after
-        // `yuv`, if that is pending), the last un-normalises and takes a following logscale / colorclip with it — queued
-        // together by run_de_finish once the tail is known (or when anything else looks at the buffers)
-        L(c).pend_in_mode = L(c).pend_yuv ? 2 : 1;
-        L(c).pend_yuv = false;
-        L(c).pend_finish = true; L(c).pend_log = false; L(c).pend_dim = d;
-        for (int i = 0; i < 5; ++i) L(c).pend_dp[i] = p[i];
-        for (int i = 0; i < 7; ++i) L(c).pend_k7[i] = k7[i];
+    bool took = false;
+    switch (id) {                        // what is pending either takes this step along, or runs first
+    case FL_FILT_BILATERAL: if (ln.pend.de) rc = flush_pending(c, ln); break;      // (a pending `yuv` stays: defer_bilateral absorbs it)
+    case FL_FILT_LOGSCALE: if (!(took = ln.pend.try_take(id, p))) rc = flush_pending(c, ln); break;
+    case FL_FILT_COLORCLIP: took = ln.pend.try_take(id, p); rc = flush_pending(c, ln); break;      // taken or not, the chain runs now
+    default: rc = flush_pending(c, ln); break;
+    }
+    if (!rc && !took) switch (id) {
+    case FL_FILT_YUV: ln.pend.defer_yuv(d); break;                     // runs with the next call
+    case FL_FILT_BILATERAL: {            // cuburn/filters.py:62-95; one kernel per direction (de.hip), all eight deferred
+        Bilateral b = {p[0], p[1], p[2], p[3], p[4], {}};
+        gauss7(1.0f, b.k7);
+        ln.pend.defer_bilateral(d, b);
     } break;
-    case FL_FILT_LOGSCALE:
-        REQUIRE(np >= 2, "logscale needs k1,k2");
-        if (L(c).pend_finish && !L(c).pend_log && !L(c).pend_yuv) { L(c).pend_log = true; L(c).pend_k1 = p[0]; L(c).pend_k2 = p[1]; break; }
-        flush_pending(c);
-        launch_logscale(st, d, L(c).d_front, p[0], p[1]);
-        break;
-    case FL_FILT_COLORCLIP:
-        REQUIRE(np >= 5, "colorclip needs vib,highpow,gam,lin,lingam");
-        if (L(c).pend_finish && !L(c).pend_yuv) {
-            run_de_finish(c, p);
-            break;
-        }
-        flush_pending(c);
-        launch_colorclip(st, d, L(c).d_front, p[0], p[1], p[2], p[3], p[4]);
-        break;
+    case FL_FILT_LOGSCALE: launch_logscale(st, d, ln.d_front, p[0], p[1]); break;
+    case FL_FILT_COLORCLIP: launch_colorclip(st, d, ln.d_front, p[0], p[1], p[2], p[3], p[4]); break;
     case FL_FILT_SMEARCLIP:              // cuburn/filters.py:142-163
-        flush_pending(c);
-        REQUIRE(np >= 4, "smearclip needs width,gam_m_1,lin,lingam");
         gauss7(p[0], k7);
-        launch_gamma_full_hi(st, d, L(c).d_side, L(c).d_front);
-        launch_full_blur(st, d, L(c).d_back, L(c).d_side, 2, 0, k7);
-        launch_full_blur(st, d, L(c).d_side, L(c).d_back, 3, 0, k7);
-        launch_full_blur(st, d, L(c).d_back, L(c).d_side, 0, 0, k7);
-        launch_full_blur(st, d, L(c).d_side, L(c).d_back, 1, 0, k7);
-        launch_smearclip(st, d, L(c).d_front, L(c).d_side, p[1], p[2], p[3]);
+        launch_gamma_full_hi(st, d, ln.d_side, ln.d_front);
+        launch_full_blur(st, d, ln.d_back, ln.d_side, 2, 0, k7);
+        launch_full_blur(st, d, ln.d_side, ln.d_back, 3, 0, k7);
+        launch_full_blur(st, d, ln.d_back, ln.d_side, 0, 0, k7);
+        launch_full_blur(st, d, ln.d_side, ln.d_back, 1, 0, k7);
+        launch_smearclip(st, d, ln.d_front, ln.d_side, p[1], p[2], p[3]);
         break;
     case FL_FILT_HALOCLIP:               // cuburn/filters.py:113-130
-        flush_pending(c);
-        REQUIRE(np >= 1, "haloclip needs gam_m_1");
         gauss7(1.0f, k7);
-        launch_apply_gamma(st, d, L(c).d_blur, L(c).d_front, 0.1f);
-        launch_den_blur_1c(st, d, (float *)L(c).d_side, L(c).d_blur, 2, 0, k7);
-        launch_den_blur_1c(st, d, L(c).d_blur, (const float *)L(c).d_side, 3, 0, k7);
-        launch_haloclip(st, d, L(c).d_front, L(c).d_blur, p[0]);
+        launch_apply_gamma(st, d, ln.d_blur, ln.d_front, 0.1f);
+        launch_den_blur_1c(st, d, (float *)ln.d_side.p, ln.d_blur, 2, 0, k7);
+        launch_den_blur_1c(st, d, ln.d_blur, (const float *)ln.d_side.p, 3, 0, k7);
+        launch_haloclip(st, d, ln.d_front, ln.d_blur, p[0]);
         break;
-    case FL_FILT_PLAINCLIP:
-        flush_pending(c);
-        REQUIRE(np >= 4, "plainclip needs gam_m_1,lin,lingam,brightness");
-        launch_plainclip(st, d, L(c).d_front, p[0], p[1], p[2], p[3]);
-        break;
+    case FL_FILT_PLAINCLIP: launch_plainclip(st, d, ln.d_front, p[0], p[1], p[2], p[3]); break;
     case FL_FILT_LOGENCODE:
-        flush_pending(c);
-        REQUIRE(np >= 1, "logencode needs degamma");
-        launch_logencode(st, d, L(c).d_back, L(c).d_front, p[0]);
-        std::swap(L(c).d_front, L(c).d_back);
+        launch_logencode(st, d, ln.d_back, ln.d_front, p[0]);
+        swap(ln.d_front, ln.d_back);
         break;
-    case FL_FILT_DE: {                   // not part of the deferred bilateral chain
-        flush_pending(c);
-        REQUIRE(np >= 3, "de needs R,Rmin,curve");
-        REQUIRE(!(p[0] > (float)FL_DE_MAX_RADIUS), "de: R above 96 px");
-        REQUIRE(p[2] > 0.0f, "de: curve must be > 0");
+    case FL_FILT_DE:                     // not part of the deferred bilateral chain
         if (!(p[0] > 0.0f)) break;       // R <= 0: every bin stays where it is
         // in place on d_front; d_back / d_blur hold the staged sources
-        launch_de_adaptive(st, d, L(c).d_front, L(c).d_back, L(c).d_blur, L(c).d_de_tmax, L(c).d_de_sinv,
+        launch_de_adaptive(st, d, ln.d_front, ln.d_back, ln.d_blur, ln.d_de_tmax, ln.d_de_sinv,
                            p[0], std::min(std::max(p[1], 0.0f), p[0]), p[2]);
-    } break;
-    default:
-        return fail(FL_E_UNSUPPORTED, "unknown filter id", __FILE__, __LINE__);
+        break;
     }
     ev_end(c, e);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return FL_OK;
 }
@@ -968,15 +907,18 @@ int fl_resample(fl_ctx *c, uint32_t w, uint32_t h, uint32_t ss, const float *tap
     REQUIRE(w <= 0x7fffffffu / ss && h <= 0x7fffffffu / ss, "resample: source size overflows");
     for (uint32_t i = 0; i < ntaps; ++i) REQUIRE(std::isfinite(taps[i]), "resample: non-finite tap");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim din, dout;
-    fl_calc_dim(ss * w, ss * h, &din); fl_calc_dim(w, h, &dout);
-    int rc = ensure_fb(c, din);
+    Lane &ln = c->lane();
+    fl_dim din;
+    const fl_dim dout = calc_dim(w, h);
+    int rc = ensure_fb(ln, ss * w, ss * h, &din);
     if (rc) return rc;
     EvPair *e = ev_begin(c, c->filt_ev);
-    flush_pending(c);                                       // a deferred yuv / DE belongs to the source size
-    launch_resample(L(c).stream, din, dout, (int)ss, L(c).d_back, L(c).d_front, taps, (int)ntaps);
-    std::swap(L(c).d_front, L(c).d_back);
+    if (!(rc = flush_pending(c, ln))) {                     // a deferred yuv / DE belongs to the source size
+        launch_resample(ln.stream, din, dout, (int)ss, ln.d_back, ln.d_front, taps, (int)ntaps);
+        swap(ln.d_front, ln.d_back);
+    }
     ev_end(c, e);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return FL_OK;
 }
@@ -999,19 +941,19 @@ int fl_output(fl_ctx *c, uint32_t w, uint32_t h, int fmt, void *host_out, uint64
     REQUIRE(c && fl_output_bytes(w, h, fmt) != 0, "bad argument");
     REQUIRE(fmt != FL_OUT_YUV420P10 || (w % 2 == 0 && h % 2 == 0), "4:2:0 needs even width and height");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
     if (rc) return rc;
-    flush_pending(c);                                       // deferred ends of the filter chain
-    void *dst = dev_out ? (void *)(uintptr_t)dev_out : L(c).d_outpix;
-    { int rc2 = wait_other(c, 2); if (rc2) return rc2; }   // the dither RNG states are shared between lanes
-    fl_mwc *rng_out = c->d_rng + (size_t)c->nslots * c->nw * 64 + FL_PAL_H * 256;
-    launch_f32_to_rgba(L(c).stream, d, L(c).d_front, rng_out, FL_NOUT, fmt, dst);
+    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
+    void *dst = dev_out ? (void *)(uintptr_t)dev_out : (void *)ln.d_outpix.p;
+    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
+    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, fmt, dst);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(L(c).ev_out_done, L(c).stream));
-    L(c).out_rec = true;
-    if (host_out) HIPCHK(hipMemcpyAsync(host_out, dst, fl_output_bytes(w, h, fmt), hipMemcpyDeviceToHost, L(c).stream));
-    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], L(c).stream));
+    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
+    ln.out_rec = true;
+    if (host_out) HIPCHK(hipMemcpyAsync(host_out, dst, fl_output_bytes(w, h, fmt), hipMemcpyDeviceToHost, ln.stream));
+    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
     return FL_OK;
 }
 
@@ -1023,16 +965,12 @@ int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint3
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) { if (nvalid) *nvalid = 0; return FL_OK; }
     size_t chunk_words = 0;
-    const size_t hist_words = sort_scratch_words(n, nbits, &chunk_words), need = hist_words + chunk_words;
+    const size_t hist_words = sort_scratch_words(n, nbits, &chunk_words);
     // Every pass runs on lane 0's stream whatever lane the frame loop is on: consecutive passes of a
     // multi-pass sort stay ordered across frame boundaries, and the scratch has ONE user stream.
     hipStream_t sst = c->lanes[0].stream;
-    if (need > c->sort_words) {
-        sync_all(c);                                        // nothing may still be using the old scratch
-        hipFree(c->d_sort); c->d_sort = nullptr; c->sort_words = 0;
-        HIPCHK(hipMalloc(&c->d_sort, need * 4));
-        c->sort_words = need;
-    }
+    // (nothing may still be using the old scratch)
+    if (int rc = c->d_sort.reserve(hist_words + chunk_words, "sort scratch", [c] { sync_all(c); return (int)FL_OK; })) return rc;
     uint32_t *chunk_tot = c->d_sort + hist_words, *total_dev = chunk_tot + (chunk_words - 1);
     launch_sort_pass(sst, (uint32_t *)(uintptr_t)dst_dev, (const uint32_t *)(uintptr_t)src_dev, n, lo_bit, nbits,
                      ignore_max, c->d_sort, chunk_tot, total_dev);
@@ -1124,46 +1062,25 @@ int fl_timings(fl_ctx *c, float *iter_ms, float *flush_ms, float *filter_ms, uin
     return FL_OK;
 }
 
-static int buf_ptr(fl_ctx *c, fl_genome *g, int which, void **p, size_t *cap)
+// A buffer of the debug taps: runs what the filter chain deferred, then names the buffer and its size in bytes.
+static int buf_ptr(fl_ctx *c, int which, void **p, size_t *cap)
 {
+    Lane &ln = c->lane();
+    if (int rc = flush_pending(c, ln)) return rc;
+    const auto is = [&](auto &b) { *p = b.p; *cap = b.bytes(); };
     switch (which) {
-    case FL_BUF_FRONT: *p = L(c).d_front; *cap = 16 * L(c).nbins; break;
-    case FL_BUF_BACK: *p = L(c).d_back; *cap = 16 * L(c).nbins; break;
-    case FL_BUF_SIDE: *p = L(c).d_side; *cap = 16 * L(c).nbins; break;
-    case FL_BUF_PARAMS: *p = L(c).d_params; *cap = 4 * L(c).params_floats; break;
-    case FL_BUF_PALETTE: *p = L(c).d_palette; *cap = 8 * FL_PAL_H * FL_PAL_W; break;
-    case FL_BUF_POINTS: *p = c->d_points; *cap = 16 * (size_t)c->nslots * c->nw * 64; break;
-    case FL_BUF_SEEDS: *p = c->d_rng; *cap = sizeof(fl_mwc) * (size_t)c->nwalkers; break;
-    case FL_BUF_ATOM: *p = L(c).d_atom; *cap = 8 * L(c).nbins; break;
-    case FL_BUF_HOT: *p = L(c).d_hot; *cap = 4 * (L(c).nbins / 16); break;
+    case FL_BUF_FRONT: is(ln.d_front); break;
+    case FL_BUF_BACK: is(ln.d_back); break;
+    case FL_BUF_SIDE: is(ln.d_side); break;
+    case FL_BUF_PARAMS: is(ln.d_params); break;
+    case FL_BUF_PALETTE: is(ln.d_palette); break;
+    case FL_BUF_POINTS: is(c->d_points); break;
+    case FL_BUF_SEEDS: is(c->d_rng); break;
+    case FL_BUF_ATOM: is(ln.d_atom); break;
+    case FL_BUF_HOT: is(ln.d_hot); break;
     default: return fail(FL_E_INVAL, "unknown buffer", __FILE__, __LINE__);
     }
     if (!*p) return fail(FL_E_INVAL, "buffer not allocated yet", __FILE__, __LINE__);
-    return FL_OK;
-}
-
-int fl_read_buffer(fl_ctx *c, fl_genome *g, int which, void *dst, size_t nbytes)
-{
-    REQUIRE(c && dst, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    flush_pending(c);
-    void *p; size_t cap;
-    int rc = buf_ptr(c, g, which, &p, &cap);
-    if (rc) return rc;
-    REQUIRE(nbytes <= cap, "read larger than buffer");
-    sync_all(c);
-    HIPCHK(hipMemcpy(dst, p, nbytes, hipMemcpyDeviceToHost));
-    return FL_OK;
-}
-
-int fl_buffer_ptr(fl_ctx *c, fl_genome *g, int which, void **dev_ptr, size_t *nbytes)
-{
-    REQUIRE(c && dev_ptr && nbytes, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    flush_pending(c);
-    int rc = buf_ptr(c, g, which, dev_ptr, nbytes);
-    if (rc) return rc;
-    sync_all(c);
     return FL_OK;
 }
 
@@ -1171,32 +1088,56 @@ int fl_buffer_ptr_async(fl_ctx *c, fl_genome *g, int which, void **dev_ptr, size
 {
     REQUIRE(c && dev_ptr && nbytes, "null argument");
     HIPCHK(hipSetDevice(c->device));
-    flush_pending(c);
-    return buf_ptr(c, g, which, dev_ptr, nbytes);
+    return buf_ptr(c, which, dev_ptr, nbytes);
 }
+
+int fl_buffer_ptr(fl_ctx *c, fl_genome *g, int which, void **dev_ptr, size_t *nbytes)
+{
+    const int rc = fl_buffer_ptr_async(c, g, which, dev_ptr, nbytes);
+    if (rc == FL_OK) sync_all(c);
+    return rc;
+}
+
+// the host copies of the debug taps: everything queued has run before the bytes move
+static int host_copy(fl_ctx *c, int which, void *host, size_t nbytes, bool to_device)
+{
+    REQUIRE(c && host, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    void *p; size_t cap;
+    int rc = buf_ptr(c, which, &p, &cap);
+    if (rc) return rc;
+    REQUIRE(nbytes <= cap, to_device ? "write larger than buffer" : "read larger than buffer");
+    sync_all(c);
+    if (to_device) HIPCHK(hipMemcpy(p, host, nbytes, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemcpy(host, p, nbytes, hipMemcpyDeviceToHost));
+    return FL_OK;
+}
+
+int fl_read_buffer(fl_ctx *c, fl_genome *g, int which, void *dst, size_t nbytes) { return host_copy(c, which, dst, nbytes, false); }
 
 int fl_reserve(fl_ctx *c, uint32_t w, uint32_t h)
 {
     REQUIRE(c && w && h, "bad argument");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    return ensure_fb(c, d);
+    fl_dim d;
+    return ensure_fb(c->lane(), w, h, &d);
 }
 
 int fl_stream_dependency(fl_ctx *c, void *stream, int ctx_waits)
 {
     REQUIRE(c, "null ctx");
     HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
     hipStream_t other = (hipStream_t)stream;
     // a small ring of events: an event may be re-recorded once the wait that used it has been queued
     hipEvent_t &ev = c->dep_ev[c->dep_next++ % fl_ctx::kDepEvents];
     if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     if (ctx_waits) {
         HIPCHK(hipEventRecord(ev, other));
-        HIPCHK(hipStreamWaitEvent(L(c).stream, ev, 0));
+        HIPCHK(hipStreamWaitEvent(ln.stream, ev, 0));
     } else {
-        flush_pending(c);                                    // deferred filter steps belong to "everything queued so far"
-        HIPCHK(hipEventRecord(ev, L(c).stream));
+        if (int rc = flush_pending(c, ln)) return rc;        // deferred filter steps belong to "everything queued so far"
+        HIPCHK(hipEventRecord(ev, ln.stream));
         HIPCHK(hipStreamWaitEvent(other, ev, 0));
     }
     return FL_OK;
@@ -1204,78 +1145,66 @@ int fl_stream_dependency(fl_ctx *c, void *stream, int ctx_waits)
 
 int fl_write_buffer(fl_ctx *c, fl_genome *g, int which, const void *src, size_t nbytes)
 {
-    REQUIRE(c && src, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    flush_pending(c);
-    void *p; size_t cap;
-    int rc = buf_ptr(c, g, which, &p, &cap);
-    if (rc) return rc;
-    REQUIRE(nbytes <= cap, "write larger than buffer");
-    sync_all(c);
-    HIPCHK(hipMemcpy(p, src, nbytes, hipMemcpyHostToDevice));
-    if (which == FL_BUF_PARAMS) L(c).params_serial = 0;       // whatever was written, the next fl_interp starts from zeroed blocks
-    return FL_OK;
+    const int rc = host_copy(c, which, const_cast<void *>(src), nbytes, true);
+    if (rc == FL_OK && which == FL_BUF_PARAMS) c->lane().params_serial = 0;       // whatever was written, the next fl_interp starts from zeroed blocks
+    return rc;
 }
 
 int fl_debug_clear(fl_ctx *c, uint32_t w, uint32_t h, int reset_points)
 {
     REQUIRE(c, "null ctx");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
     if (rc) return rc;
-    flush_pending(c);
-    return do_clear(c, d, reset_points != 0);
+    if ((rc = flush_pending(c, ln))) return rc;
+    return do_clear(c, ln, d, reset_points != 0);
 }
 
 int fl_debug_iter_launch(fl_ctx *c, fl_genome *g, uint32_t w, uint32_t h, uint32_t round0,
                          uint32_t nrounds, uint32_t fuse, int accum_mode)
 {
     REQUIRE(c && g && (accum_mode == FL_ACCUM_ATOMIC || accum_mode == FL_ACCUM_BINNED), "bad argument");
-    REQUIRE(L(c).params_floats >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
+    Lane &ln = c->lane();
+    REQUIRE(ln.d_params.cap >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
     HIPCHK(hipSetDevice(c->device));
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
     if (rc) return rc;
     c->round_counter = round0;
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, 32, L(c).stream));
-    return do_iter_launch(c, g, d, nrounds, fuse, true, accum_mode);
+    HIPCHK(hipMemsetAsync(c->d_counters, 0, 32, ln.stream));
+    return do_iter_launch(c, ln, g, d, nrounds, fuse, true, accum_mode);
 }
 
 int fl_debug_flush(fl_ctx *c, uint32_t w, uint32_t h)
 {
     REQUIRE(c, "null ctx");
-    fl_dim d; fl_calc_dim(w, h, &d);
-    int rc = ensure_fb(c, d);
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
     if (rc) return rc;
-    flush_pending(c);
-    return do_flush(c, d);
+    if ((rc = flush_pending(c, ln))) return rc;
+    return do_flush(c, ln, d);
 }
 
 int fl_debug_clear_hot(fl_ctx *c, uint32_t w, uint32_t h)
 {
-    REQUIRE(c && L(c).d_hot, "null ctx");
-    fl_dim d; fl_calc_dim(w, h, &d);
-    HIPCHK(hipMemsetAsync(L(c).d_hot, 0, 4 * ((size_t)d.ah * d.astride / 16), L(c).stream));
+    REQUIRE(c && c->lane().d_hot, "null ctx");
+    const fl_dim d = calc_dim(w, h);
+    HIPCHK(hipMemsetAsync(c->lane().d_hot, 0, 4 * ((size_t)d.ah * d.astride / 16), c->lane().stream));
     return FL_OK;
 }
-
-// scratch device memory of a debug tap, freed on every exit path
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n); }
-};
 
 int fl_debug_shuffle(fl_ctx *c, uint32_t round, uint32_t *out256)
 {
     REQUIRE(c && out256, "null argument");
     HIPCHK(hipSetDevice(c->device));
-    DevBuf d; const size_t n = (size_t)c->nw * 64;
-    HIPCHK(d.alloc(4 * n));
-    launch_shuffle_tap(L(c).stream, c->nw, (uint32_t *)d.p, round);
-    HIPCHK(hipStreamSynchronize(L(c).stream));
-    HIPCHK(hipMemcpy(out256, d.p, 4 * n, hipMemcpyDeviceToHost));
+    DevBuf<uint32_t> d; const size_t n = (size_t)c->nw * 64;
+    if (int rc = d.reserve(n, "shuffle tap scratch")) return rc;
+    launch_shuffle_tap(c->lane().stream, c->nw, d, round);
+    HIPCHK(hipStreamSynchronize(c->lane().stream));
+    HIPCHK(hipMemcpy(out256, d, 4 * n, hipMemcpyDeviceToHost));
     return FL_OK;
 }
 
@@ -1283,17 +1212,18 @@ int fl_debug_apply_xf(fl_ctx *c, fl_genome *g, uint32_t ts, int xfi, uint32_t n,
 {
     REQUIRE(c && g && xyzw && rng && n > 0 && ts < c->ntemporal(), "bad argument");
     REQUIRE(xfi >= 0 && xfi < g->prog[1] + g->prog[2], "xform index out of range");
-    REQUIRE(L(c).params_floats >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
+    Lane &ln = c->lane();
+    REQUIRE(ln.d_params.cap >= (size_t)c->ntemporal() * g->pstride, "fl_interp has not run for this genome");
     HIPCHK(hipSetDevice(c->device));
-    DevBuf dp, dr;
-    HIPCHK(dp.alloc(16 * (size_t)n));
-    HIPCHK(dr.alloc(sizeof(fl_mwc) * (size_t)n));
-    HIPCHK(hipMemcpy(dp.p, xyzw, 16 * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dr.p, rng, sizeof(fl_mwc) * (size_t)n, hipMemcpyHostToDevice));
-    launch_apply_xf_tap(L(c).stream, g->d_prog, L(c).d_params, ts, xfi, n, (float4 *)dp.p, (fl_mwc *)dr.p);
-    HIPCHK(hipStreamSynchronize(L(c).stream));
-    HIPCHK(hipMemcpy(xyzw, dp.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rng, dr.p, sizeof(fl_mwc) * (size_t)n, hipMemcpyDeviceToHost));
+    DevBuf<float4> dp; DevBuf<fl_mwc> dr;
+    int rc;
+    if ((rc = dp.reserve(n, "xform tap scratch")) || (rc = dr.reserve(n, "xform tap scratch"))) return rc;
+    HIPCHK(hipMemcpy(dp, xyzw, dp.bytes(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr, rng, dr.bytes(), hipMemcpyHostToDevice));
+    launch_apply_xf_tap(ln.stream, g->d_prog, ln.d_params, ts, xfi, n, dp, dr);
+    HIPCHK(hipStreamSynchronize(ln.stream));
+    HIPCHK(hipMemcpy(xyzw, dp, dp.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rng, dr, dr.bytes(), hipMemcpyDeviceToHost));
     return FL_OK;
 }
 
@@ -1303,18 +1233,7 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
     REQUIRE(prog && ops && nprog >= FL_PROG_HDR && (nw == 4 || nw == 8 || nw == 16) && acc >= 0 && acc <= 3, "bad argument");
     int rc = check_prog(prog, nprog);
     if (rc) return rc;
-    const int xo = prog[5], xs = prog[6], nrec = prog[1] + prog[2];
-    for (uint32_t i = 0; i < nops; ++i) {
-        const int32_t *o = ops + 4 * i;
-        if (o[0] == FL_OP_OPACITY) {
-            const int rel = o[1] - xo;
-            REQUIRE(rel >= 0 && rel / xs < prog[1] && rel % xs == 15, "opacity op must write word 15 of a selectable xform record");
-        }
-        if (o[0] != FL_OP_CONST) continue;
-        const int rel = o[1] - xo, rec = rel / xs, w = rel % xs;
-        REQUIRE(rel >= 0 && rec < nrec, "structure word outside the xform records");
-        if (w == 14) { REQUIRE((o[2] >> 10) == 0 && (((o[2] >> 9) & 1) == 0 || rec < prog[1]), "bad structure word"); }
-    }
+    for (uint32_t i = 0; i < nops; ++i) if ((rc = check_structure_op(prog, ops + 4 * i))) return rc;
     IterSpec spec = iter_spec(prog, nprog, ops, nops);
     for (std::vector<int> &v : spec.vids) for (int &id : v) if (id < 0) id = 0;      // (a variation without a number compiles as number 0 here; fl_genome_create refuses it)
     std::vector<char> code;

@@ -149,6 +149,48 @@ def test_argument_validation(mgr):
                                 packer.nrows, C.byref(h)) == _lib.FL_E_INVAL
 
 
+def test_refused_filter_calls_queue_and_record_nothing(mgr):
+    """fl_filter checks its arguments before it touches anything: a call it refuses (too few scalars; scalars required but a null
+    pointer) runs nothing that was deferred, queues nothing and takes no timing pair.  On a fixed random 64 x 48 accumulator: `yuv`
+    (deferred), the two refused calls, then bilateral -> logscale -> colorclip gives the bits of the same chain without the refused
+    calls, and the timers stay whole."""
+    lib = _lib.load()
+    W, H = 64, 48
+    dim = mgr.fb.calc_dim(W, H)
+    n = dim.ah * dim.astride
+    rs = np.random.RandomState(7)
+    dens = rs.poisson(rs.uniform(0, 400, n) * (rs.uniform(size=n) < 0.7)).astype(np.float32)
+    buf = np.concatenate([dens[:, None] * rs.uniform(0.1, 0.9, (n, 3)), dens[:, None]], 1).astype(np.float32)
+    steps = [('bilateral', [6.0 * W / 1920., 0.05, 1.5, 0.8, 4.0]), ('logscale', [4.1875, 0.002]),
+             ('colorclip', [1.0, -1.0, 0.25, 0.01, 0.01 ** (0.25 - 1)])]
+
+    def filt(name, vals, count=None, null=False):
+        arr = np.asarray(vals, np.float32)
+        return lib.fl_filter(mgr.fb.ctx, _lib.FILT[name], W, H, None if null else arr.ctypes.data, len(arr) if count is None else count)
+
+    def run(refused):
+        _lib.check(lib.fl_debug_clear(mgr.fb.ctx, W, H, 0))
+        mgr.fb.write('front', buf)
+        mgr.timings_reset()
+        _lib.check(filt('yuv', []))
+        if refused:
+            assert filt('bilateral', steps[0][1], count=2) == _lib.FL_E_INVAL
+            assert filt('colorclip', [], count=5, null=True) == _lib.FL_E_INVAL
+        for name, vals in steps:
+            _lib.check(filt(name, vals))
+        front = mgr.fb.read('front', buf.shape, np.float32)
+        it, fl, ft, nl = C.c_float(), C.c_float(), C.c_float(), C.c_uint32()
+        assert lib.fl_timings(mgr.fb.ctx, C.byref(it), C.byref(fl), C.byref(ft), C.byref(nl)) == _lib.FL_OK
+        assert filt(*steps[1]) == _lib.FL_OK
+        return front, ft.value
+
+    plain, _ = run(False)
+    front, filter_ms = run(True)
+    assert np.isfinite(plain).all() and plain[:, 3].max() > 0
+    assert np.array_equal(front.view(np.uint32), plain.view(np.uint32))
+    assert np.isfinite(filter_ms) and filter_ms > 0, filter_ms
+
+
 def test_malformed_op_lists_rejected(mgr):
     """Every word an op writes and every spline row it reads is checked against the block / row
     table at fl_genome_create (multi-word ops: camera / affine 6 words, CDF b words, perspective 3)."""
