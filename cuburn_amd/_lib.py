@@ -18,6 +18,7 @@ BUF = dict(front=0, back=1, params=2, palette=3, points=4, seeds=5, atom=6, hot=
 ACCUM_ATOMIC, ACCUM_BINNED = 0, 1
 FL_OP_CHAOS_CDF = 11                # include/flame_hip.h (6): dst[0..nxf-1] <- row of the chaos matrix (xaos)
 FL_OP_OPACITY = 10                  # include/flame_hip.h (6): dst <- plot probability of the xform's samples
+JPEG_HEADER_BYTES = 629             # include/flame_hip.h FL_JPEG_HEADER_BYTES
 OUT = dict(rgba8=0, rgba16=1, yuv444p=2, yuv444p10=3, yuv420p10=4, yuv444p12=5)     # include/flame_hip.h FL_OUT_*
 
 
@@ -43,6 +44,9 @@ _SIGS = {
     'fl_resample': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     'fl_output': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64]),
     'fl_output_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int]),
+    'fl_jpeg_bound': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'fl_jpeg_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_output_jpeg': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_sort_u32': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     'fl_frame_begin': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     'fl_frame_ms': (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),

@@ -106,6 +106,8 @@ struct Lane {
     DevBuf<unsigned char> d_outpix;                 // w*h*8 bytes
     DevBuf<uint32_t> d_de_tmax;                     // FL_FILT_DE: largest 16h per 64 x 16 tile [nbins / 256 + 64]
     DevBuf<float> d_de_sinv;                        // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
+    DevBuf<uint32_t> d_jpeg;                        // JPEG encode: coefficients, interval lengths and offsets (jpeg_layout)
+    DevBuf<unsigned char> d_jpeg_out;               // ... and the stream on its way to host memory that is not pinned
     size_t nbins() const { return d_front.cap; }
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
     // accumulate + flush of launch k run on `aux` while launch k+1 iterates on `stream` into the other set
@@ -140,7 +142,7 @@ struct Lane {
     void release()
     {
         release_fb();
-        d_params.release(); d_palette.release();
+        d_params.release(); d_palette.release(); d_jpeg.release(); d_jpeg_out.release();
         for (int k = 0; k < 2; ++k) { d_log[k].release(); d_dir[k].release(); }
         if (aux) hipStreamDestroy(aux);
         for (hipEvent_t *ev : events()) if (*ev) hipEventDestroy(*ev);
@@ -176,7 +178,7 @@ struct fl_ctx {
     hipEvent_t ev_begin_[kFrames] = {}, ev_end_[kFrames] = {};
     uint32_t frame_lane[kFrames] = {};
     uint32_t frame_seq = 0;                        // id of the current frame = frame_seq - 1
-    std::vector<EvPair> pool, iter_ev, accum_ev, flush_ev, filt_ev, de_ev;
+    std::vector<EvPair> pool, iter_ev, accum_ev, flush_ev, filt_ev, de_ev, jpeg_ev;
     size_t pool_used = 0;
     bool timing = true;
     static const uint32_t kDepEvents = 16;
@@ -185,6 +187,7 @@ struct fl_ctx {
     // environment switches, read once when the context is created (listed in include/flame_hip.h)
     bool env_bin_wide = false, env_no_intra = false;
     bool use_rtc = true;                    // FLAME_RTC=0: always the interpreter kernel
+    uint32_t jpeg_ri = FL_JPEG_RI;          // FLAME_JPEG_RI (1..21): MCUs per JPEG restart interval
     uint32_t n_spec_launch = 0, n_interp_launch = 0;      // iterate launches by kernel since fl_timings_reset (fl_launch_stats)
     BinLayout layout(const fl_dim &d) const { return bin_layout(d, nw, bin_rounds, env_bin_wide); }
 };
@@ -314,6 +317,7 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
     if (const char *e = getenv("FLAME_BIN_PARTS")) { int v = atoi(e); if (v >= 1 && v <= 64) c->bin_parts = (uint32_t)v; }
     c->env_bin_wide = env_on("FLAME_BIN_WIDE");
     if (const char *e = getenv("FLAME_RTC")) c->use_rtc = strcmp(e, "0") != 0;
+    if (const char *e = getenv("FLAME_JPEG_RI")) { const int v = atoi(e); if (v >= 1 && v <= 21) c->jpeg_ri = (uint32_t)v; }
     c->env_no_intra = env_on("FLAME_NO_INTRA_OVERLAP");      // launches of a frame strictly in series on one stream
     if (const char *e = getenv("FLAME_LAUNCH_ROUNDS")) { int v = atoi(e); if (v >= 16 && v <= 4096) c->launch_rounds = (uint32_t)(v / 16 * 16); }
     if (stream) { c->lanes[0].stream = (hipStream_t)stream; c->own_stream = false; c->nlanes = 1; }   // caller's stream: one lane
@@ -957,6 +961,83 @@ int fl_output(fl_ctx *c, uint32_t w, uint32_t h, int fmt, void *host_out, uint64
     return FL_OK;
 }
 
+// ---- JPEG stills (jpeg.hip) ----
+// No stream can be longer: a block codes its DC difference in at most 11 + 11 bits (the longest code of table K.4, category 11)
+// and each of its 63 AC coefficients in at most 16 + 10 (the longest code of K.5 / K.6, category 10; ZRL and EOB stand for
+// coefficients that then cost nothing): 22 + 63 * 26 = 1660 bits, 4980 per MCU of three blocks, 623 bytes once padded.  Every one
+// of those bytes can be 0xFF and take a stuffed zero with it, and the shortest restart interval — one MCU — puts a two-byte
+// marker (RSTm, or EOI) behind each: 2 * 623 + 2 = 1248 bytes per MCU.  Longer intervals pad and mark less often.
+size_t fl_jpeg_bound(uint32_t w, uint32_t h)
+{
+    if (!w || !h || w > 65535u || h > 65535u) return 0;
+    return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 1248u;
+}
+
+static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    REQUIRE(c, "null ctx");
+    REQUIRE(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+    REQUIRE(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u, "jpeg: width and height must be 1..65535");
+    REQUIRE(cap >= 16 + FL_JPEG_HEADER_BYTES, "jpeg: capacity below the record and the header");
+    REQUIRE(host_out || dev_out, "jpeg: no destination");
+    return FL_OK;
+}
+
+// The encode proper, queued on the lane's stream (arguments checked).  Where the kernels store: the caller's device buffer; else the
+// caller's host buffer through its device address when it is pinned; else a buffer of the lane's, copied to the host afterwards.
+static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality,
+                          void *host_out, uint64_t dev_out, size_t cap)
+{
+    unsigned char *dst = (unsigned char *)(uintptr_t)dev_out;
+    bool copy_back = host_out && dst;
+    if (!dst) {
+        hipPointerAttribute_t at = {};
+        const hipError_t e = hipPointerGetAttributes(&at, host_out);
+        if (e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) dst = (unsigned char *)at.devicePointer;
+        else {
+            (void)hipGetLastError();                            // (not a pointer the runtime knows: plain host memory)
+            if (int rc = ln.d_jpeg_out.reserve(std::min(cap, fl_jpeg_bound(w, h)), "jpeg stream", [&ln] { return ln.quiesce(false); })) return rc;
+            dst = ln.d_jpeg_out;
+            copy_back = true;
+        }
+    }
+    const size_t dcap = std::min(cap, fl_jpeg_bound(w, h));    // (what a fitting stream can occupy)
+    if (int rc = ln.d_jpeg.reserve(jpeg_layout(w, h, c->jpeg_ri).words, "jpeg scratch", [&ln] { return ln.quiesce(false); })) return rc;
+    EvPair *e = ev_begin_on(c, c->jpeg_ev, ln.stream);
+    launch_jpeg_encode(ln.stream, src, w, h, quality, c->jpeg_ri, ln.d_jpeg, dst, cap);
+    ev_end_on(e, ln.stream);
+    HIPCHK(hipGetLastError());
+    if (copy_back) HIPCHK(hipMemcpyAsync(host_out, dst, dcap, hipMemcpyDeviceToHost, ln.stream));
+    return FL_OK;
+}
+
+int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_jpeg(c, w, h, quality, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "jpeg: null source planes");
+    HIPCHK(hipSetDevice(c->device));
+    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, host_out, dev_out, cap);
+}
+
+int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_jpeg(c, w, h, quality, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
+    if (rc) return rc;
+    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
+    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
+    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, FL_OUT_YUV444P, ln.d_outpix.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
+    ln.out_rec = true;
+    if ((rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, host_out, dev_out, cap))) return rc;
+    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
+    return FL_OK;
+}
+
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
                 uint32_t *nvalid)
 {
@@ -1022,7 +1103,7 @@ int fl_timings_reset(fl_ctx *c)
 {
     REQUIRE(c, "null ctx");
     sync_all(c);
-    c->iter_ev.clear(); c->accum_ev.clear(); c->flush_ev.clear(); c->filt_ev.clear(); c->de_ev.clear(); c->pool_used = 0;
+    c->iter_ev.clear(); c->accum_ev.clear(); c->flush_ev.clear(); c->filt_ev.clear(); c->de_ev.clear(); c->jpeg_ev.clear(); c->pool_used = 0;
     c->n_spec_launch = c->n_interp_launch = 0;
     return FL_OK;
 }
@@ -1032,7 +1113,7 @@ int fl_timings_detail(fl_ctx *c, float ms[6])
     REQUIRE(c && ms, "null argument");
     sync_all(c);
     ms[0] = sum_ms(c->iter_ev); ms[1] = sum_ms(c->accum_ev); ms[2] = sum_ms(c->flush_ev);
-    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = 0.0f;      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: unused since round 5
+    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->jpeg_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG encodes
     return FL_OK;
 }
 

@@ -1,0 +1,421 @@
+// jpeg.hip — baseline JPEG (SOF0, 8 bit, 4:4:4, one interleaved scan, restart intervals) from u8 planar Y/Cb/Cr on the device.
+// DESIGN.md §4.8.  Four launches per frame, no host wait between them:
+//   k_jpeg_dct          one lane per 8x8 block: load (edge replicated), level shift, float32 DCT, quantise, zigzag -> int16, and the
+//                       bit length of the block's AC symbols
+//   k_jpeg_entropy<0>   one wave per restart interval: DC differences, prefix sum of the blocks' bit lengths, bits packed in LDS,
+//                       0xFF counted -> the interval's byte length (stuffing and marker included)
+//   k_jpeg_scan         one workgroup: exclusive scan of the intervals' byte lengths, the 16-byte record and the header
+//   k_jpeg_entropy<1>   the same packing again, stuffed in LDS, stored at the interval's place with dword stores
+// The intervals are byte aligned and independent (the DC predictor restarts), which is what makes the scan parallel; nothing is
+// stored at or beyond `cap`: the last pass stores nothing when the stream does not fit.
+#include "kernels.h"
+
+namespace {
+
+// ITU T.81 Annex K.3-K.6: the "typical" Huffman tables (BITS, HUFFVAL)
+constexpr uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr uint8_t kDcChrBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr uint8_t kAcLumBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+constexpr uint8_t kAcLumVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+constexpr uint8_t kAcChrBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+constexpr uint8_t kAcChrVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+// Annex K.1 / K.2: the base quantisation tables, row-major
+constexpr uint8_t kQLum[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                               14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+constexpr uint8_t kQChr[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                               47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// zigzag position -> row-major index (v * 8 + u, u the horizontal frequency)
+constexpr uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// code | length << 16 by symbol: [0, 16) DC luminance, [16, 32) DC chrominance, [32, 288) AC luminance, [288, 544) AC chrominance
+enum { kDcLum = 0, kDcChr = 16, kAcLum = 32, kAcChr = 288, kHuffWords = 544 };
+struct HuffTabs { uint32_t e[kHuffWords]; };
+constexpr void huff_fill(uint32_t *dst, const uint8_t *bits, const uint8_t *vals)      // T.81 Annex C: codes in order of length
+{
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < bits[len - 1]; ++i) dst[vals[k++]] = code++ | (uint32_t)len << 16;
+        code <<= 1;
+    }
+}
+constexpr HuffTabs make_huff()
+{
+    HuffTabs t = {};
+    huff_fill(t.e + kDcLum, kDcLumBits, kDcVals);
+    huff_fill(t.e + kDcChr, kDcChrBits, kDcVals);
+    huff_fill(t.e + kAcLum, kAcLumBits, kAcLumVals);
+    huff_fill(t.e + kAcChr, kAcChrBits, kAcChrVals);
+    return t;
+}
+__device__ const HuffTabs g_huff = make_huff();
+
+// 0.5 * C(u) * cos((2x + 1) u pi / 16), C(0) = 1 / sqrt(2): the T.81 normalisation, one factor per axis
+struct DctTab { float c[8][8]; };
+constexpr DctTab make_dct()
+{
+    constexpr double cs[9] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440,
+                              0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785, 0.0};
+    DctTab t = {};
+    for (int u = 0; u < 8; ++u)
+        for (int x = 0; x < 8; ++x) {
+            int m = (2 * x + 1) * u % 32;
+            if (m > 16) m = 32 - m;
+            const double c = m > 8 ? -cs[16 - m] : cs[m];
+            t.c[u][x] = (float)(0.5 * (u == 0 ? cs[4] : 1.0) * c);
+        }
+    return t;
+}
+constexpr DctTab kDct = make_dct();
+
+struct JpegQuant { float q[2][64]; };                     // divisors by row-major index: luminance, chrominance
+struct JpegHeaderArg { unsigned char b[640]; };           // FL_JPEG_HEADER_BYTES bytes, as a kernel argument: no copy to order
+
+__device__ __forceinline__ int nbits_of(int v) { const int a = v < 0 ? -v : v; return 32 - __clz(a); }      // magnitude category (0 for 0)
+
+// ---- load + DCT + quantise -------------------------------------------------------------------------------------------
+// grid (ceil(nmcu / 256), 3): blockIdx.y is the component, so the quantiser table is wave-uniform.  coef[(3 * mcu + comp) * 64 + k]
+// in zigzag order (the order of the scan); acbits[3 * mcu + comp] = bits of the block's AC symbols.
+__global__ void __launch_bounds__(256)
+k_jpeg_dct(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint32_t mw, uint32_t nmcu, JpegQuant Q,
+           short *__restrict__ coef, unsigned short *__restrict__ acbits)
+{
+    __shared__ unsigned char s_len[256];
+    const uint32_t comp = blockIdx.y;
+    s_len[threadIdx.x] = (unsigned char)(g_huff.e[(comp ? kAcChr : kAcLum) + threadIdx.x] >> 16);
+    __syncthreads();
+    const uint32_t mcu = blockIdx.x * 256u + threadIdx.x;
+    if (mcu >= nmcu) return;
+    const uint32_t bx = mcu % mw, by = mcu / mw;
+    const unsigned char *plane = src + (size_t)comp * w * h;
+    float f[64];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+        const uint32_t yy = min(by * 8u + y, h - 1u);         // the last row / column is replicated into partial blocks
+        const unsigned char *row = plane + (size_t)yy * w;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) f[y * 8 + x] = (float)row[min(bx * 8u + x, w - 1u)] - 128.0f;
+    }
+    float t[64];
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float s = kDct.c[u][0] * f[y * 8];
+#pragma unroll
+            for (int x = 1; x < 8; ++x) s += kDct.c[u][x] * f[y * 8 + x];
+            t[y * 8 + u] = s;
+        }
+    const float *q = Q.q[comp ? 1 : 0];
+    short z[64];                                              // row-major
+#pragma unroll
+    for (int v = 0; v < 8; ++v)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float s = kDct.c[v][0] * t[u];
+#pragma unroll
+            for (int y = 1; y < 8; ++y) s += kDct.c[v][y] * t[y * 8 + u];
+            // |AC| < 925 and |DC| <= 1024 for 8-bit samples: the clamp only keeps the symbol tables' index in range whatever the bytes
+            z[v * 8 + u] = (short)fminf(fmaxf(rintf(s / q[v * 8 + u]), v + u ? -1023.0f : -2047.0f), v + u ? 1023.0f : 2047.0f);
+        }
+    const uint32_t blk = 3u * mcu + comp;
+    uint4 *dst = (uint4 *)(coef + (size_t)blk * 64);
+    uint32_t bits = 0, run = 0;
+#pragma unroll
+    for (int k8 = 0; k8 < 8; ++k8) {
+        uint32_t pk[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k8 * 8 + 2 * j;
+            pk[j] = (uint32_t)(unsigned short)z[kZigzag[k]] | (uint32_t)(unsigned short)z[kZigzag[k + 1]] << 16;
+        }
+        dst[k8] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = k8 * 8 + j;
+            if (k == 0) continue;
+            const int v = z[kZigzag[k]];
+            if (v == 0) { ++run; continue; }
+            bits += (run >> 4) * s_len[0xf0];                 // ZRL per 16 zeros
+            const int s = nbits_of(v);
+            bits += s_len[(run & 15u) << 4 | s] + s;
+            run = 0;
+        }
+    }
+    if (run) bits += s_len[0];                                // EOB
+    acbits[blk] = (unsigned short)bits;
+}
+
+// ---- entropy coding of one restart interval per wave -------------------------------------------------------------------
+// Worst case of a block: DC 11 + 11 bits, 63 AC of 16 + 10 bits = 1660 bits; an MCU 4980.
+#define JPEG_MCU_BITS 4980u
+struct Bits {                         // a lane's writer into the interval's bit buffer (big-endian 32-bit words; a word may be shared with the neighbouring lanes' blocks)
+    uint32_t *words; uint32_t w; u64 acc; uint32_t n;
+    __device__ __forceinline__ void put(uint32_t code, uint32_t len)       // 1 <= len <= 26, n < 32
+    {
+        acc |= (u64)code << (64u - n - len);
+        n += len;
+        if (n >= 32u) { atomicOr(&words[w++], (uint32_t)(acc >> 32)); acc <<= 32; n -= 32u; }
+    }
+    __device__ __forceinline__ void flush() { if (n) atomicOr(&words[w], (uint32_t)(acc >> 32)); }
+};
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
+    return v;
+}
+
+// One workgroup of one wave per interval of `ri` MCUs (3 * ri <= 64: a lane per block).  WRITE = false: lens[interval] = bytes of the
+// interval, stuffing and the RSTm / EOI marker behind it included.  WRITE = true: the bytes go to out + base + offs[interval],
+// unless info[2] (the status the scan left) says that the stream does not fit.
+// LDS: the symbol tables | bit buffer of ceil(ri * 4980 / 32) + 2 words | stuffed bytes, 2 * ceil(ri * 4980 / 8) + 2 and 8 of padding
+template <bool WRITE>
+__global__ void __launch_bounds__(64)
+k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict__ acbits, uint32_t nmcu, uint32_t ri, uint32_t nint,
+               uint32_t *__restrict__ lens, const u64 *__restrict__ offs, const uint32_t *__restrict__ info,
+               unsigned char *__restrict__ out, uint32_t base)
+{
+    extern __shared__ uint32_t s_mem[];
+    uint32_t *s_huff = s_mem, *s_bits = s_mem + kHuffWords;
+    const uint32_t nbw = (ri * JPEG_MCU_BITS + 31u) / 32u + 2u;
+    unsigned char *s_out = (unsigned char *)(s_bits + nbw);
+    const uint32_t lane = threadIdx.x, it = blockIdx.x;
+    if (WRITE && info[2]) return;
+    for (uint32_t i = lane; i < kHuffWords; i += 64) s_huff[i] = g_huff.e[i];
+    const uint32_t mcu0 = it * ri, nb = 3u * min(ri, nmcu - mcu0);
+    const bool live = lane < nb;
+    const uint32_t comp = lane % 3u;
+    const size_t blk = (size_t)3u * mcu0 + lane;
+    const uint4 *cp = (const uint4 *)(coef + blk * 64);
+    uint4 cw[8];
+    int diff = 0;
+    uint32_t mybits = 0;
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cw[j] = cp[j];
+        const int dc = (short)(cw[0].x & 0xffffu);
+        const int pred = lane >= 3u ? (int)coef[(blk - 3u) * 64] : 0;      // the previous block of the component; 0 at the interval's start
+        diff = dc - pred;
+        mybits = acbits[blk] + (uint32_t)nbits_of(diff);                   // (the DC code's length is added below, from the table)
+    }
+    __syncthreads();                                                       // the tables are in LDS
+    const uint32_t *dctab = s_huff + (comp ? kDcChr : kDcLum), *actab = s_huff + (comp ? kAcChr : kAcLum);
+    const int ds = nbits_of(diff);
+    if (live) mybits += dctab[ds] >> 16;
+    const uint32_t incl = wave_incl_scan(mybits, lane);
+    const uint32_t T = __shfl(incl, 63, 64);
+    const uint32_t pad = (8u - (T & 7u)) & 7u, N = (T + pad) >> 3, nw = (N + 3u) >> 2;      // N bytes before stuffing, nw words
+    for (uint32_t i = lane; i <= nw; i += 64) s_bits[i] = 0;
+    __syncthreads();
+    if (live) {
+        const uint32_t start = incl - mybits;
+        Bits b = {s_bits, start >> 5, 0, start & 31u};
+        b.put(dctab[ds] & 0xffffu, dctab[ds] >> 16);
+        if (ds) b.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << ds) - 1u), (uint32_t)ds);
+        uint32_t run = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t wd[4] = {cw[j].x, cw[j].y, cw[j].z, cw[j].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if (j == 0 && e == 0) continue;
+                const int v = (short)(wd[e >> 1] >> ((e & 1) * 16) & 0xffffu);
+                if (v == 0) { ++run; continue; }
+                for (; run > 15u; run -= 16u) b.put(actab[0xf0] & 0xffffu, actab[0xf0] >> 16);
+                const int s = nbits_of(v);
+                const uint32_t sym = actab[run << 4 | (uint32_t)s];
+                b.put(sym & 0xffffu, sym >> 16);
+                b.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u), (uint32_t)s);
+                run = 0;
+            }
+        }
+        if (run) b.put(actab[0] & 0xffffu, actab[0] >> 16);
+        if (lane == nb - 1u && pad) b.put((1u << pad) - 1u, pad);          // the interval is padded to a byte with 1-bits
+        b.flush();
+    }
+    __syncthreads();
+    // stuffing: every lane takes `per` consecutive words; a prefix sum of their 0xFF counts places each lane's bytes
+    const uint32_t per = (nw + 63u) / 64u, lo = min(lane * per, nw), hi = min(lo + per, nw);
+    uint32_t nff = 0;
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint32_t wd = s_bits[i];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) nff += (4u * i + k < N && (wd >> (24u - 8u * k) & 0xffu) == 0xffu) ? 1u : 0u;
+    }
+    const uint32_t ffincl = wave_incl_scan(nff, lane);
+    const uint32_t L = N + __shfl(ffincl, 63, 64) + 2u;                    // + the marker
+    if (!WRITE) {
+        if (lane == 0) lens[it] = L;
+        return;
+    }
+    uint32_t o = 4u * lo + (ffincl - nff);
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint32_t wd = s_bits[i];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t byte = wd >> (24u - 8u * k) & 0xffu;
+            if (4u * i + k < N) {
+                s_out[o++] = (unsigned char)byte;
+                if (byte == 0xffu) s_out[o++] = 0;
+            }
+        }
+    }
+    if (lane == 0) {
+        s_out[L - 2u] = 0xff;
+        s_out[L - 1u] = it + 1u == nint ? 0xd9 : (unsigned char)(0xd0u + (it & 7u));      // EOI behind the last interval, RSTm behind the others
+    }
+    __syncthreads();
+    // to the stream: bytes up to the first 4-byte boundary of the destination, dwords, and the bytes that are left
+    unsigned char *dst = out + (size_t)base + offs[it];
+    const uint32_t head = min(L, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u)), nmid = (L - head) >> 2, tail0 = head + 4u * nmid;
+    if (lane < head) dst[lane] = s_out[lane];
+    const uint32_t *s32 = (const uint32_t *)s_out;
+    for (uint32_t m = lane; m < nmid; m += 64) {
+        const uint32_t so = head + 4u * m, sh = (so & 3u) * 8u;
+        const uint32_t a = s32[so >> 2], c = s32[(so >> 2) + 1u];
+        *(uint32_t *)(dst + so) = sh ? a >> sh | c << (32u - sh) : a;
+    }
+    if (lane < L - tail0) dst[tail0 + lane] = s_out[tail0 + lane];
+}
+
+// ---- where the intervals go ------------------------------------------------------------------------------------------
+// One workgroup: offs[i] = sum of lens[0 .. i), info = {total low, total high, status}; the record and the header go to `out`.
+__global__ void __launch_bounds__(1024)
+k_jpeg_scan(const uint32_t *__restrict__ lens, uint32_t nint, u64 *__restrict__ offs, uint32_t *__restrict__ info,
+            unsigned char *__restrict__ out, u64 cap, uint32_t ri, JpegHeaderArg hdr)
+{
+    __shared__ u64 s_sum[1024];
+    const uint32_t t = threadIdx.x, per = (nint + 1023u) / 1024u, lo = min(t * per, nint), hi = min(lo + per, nint);
+    u64 mine = 0;
+    for (uint32_t i = lo; i < hi; ++i) mine += lens[i];
+    s_sum[t] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const u64 o = t >= d ? s_sum[t - d] : 0;
+        __syncthreads();
+        s_sum[t] += o;
+        __syncthreads();
+    }
+    u64 run = s_sum[t] - mine;
+    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += lens[i]; }
+    const u64 need = (u64)FL_JPEG_HEADER_BYTES + s_sum[1023];              // bytes behind the record
+    const uint32_t status = need > cap - 16u ? 1u : 0u;
+    if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; }
+    if (t < 16) {
+        const uint32_t rec[4] = {need > 0xffffffffull ? 0xffffffffu : (uint32_t)need, status, ri, 0u};
+        out[t] = (unsigned char)(rec[t >> 2] >> (8u * (t & 3u)));
+    }
+    if (t < FL_JPEG_HEADER_BYTES) out[16u + t] = hdr.b[t];                 // (cap >= 16 + the header: the callers checked)
+}
+
+void put16(unsigned char *&p, uint32_t v) { *p++ = (unsigned char)(v >> 8); *p++ = (unsigned char)v; }
+void put_dht(unsigned char *&p, int cls_id, const uint8_t *bits, const uint8_t *vals, int nvals)
+{
+    put16(p, 0xffc4); put16(p, 2 + 1 + 16 + nvals);
+    *p++ = (unsigned char)cls_id;
+    for (int i = 0; i < 16; ++i) *p++ = bits[i];
+    for (int i = 0; i < nvals; ++i) *p++ = vals[i];
+}
+
+} // namespace
+
+// Annex K.1 / K.2 scaled the libjpeg way (jpeg_quality_scaling, jpeg_add_quant_table with force_baseline)
+static void jpeg_quant_table(int quality, int chroma, unsigned char q[64])
+{
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) {
+        const int v = ((chroma ? kQChr[i] : kQLum[i]) * s + 50) / 100;
+        q[i] = (unsigned char)(v < 1 ? 1 : v > 255 ? 255 : v);
+    }
+}
+
+// SOI, APP0 (JFIF 1.01), DQT x2, SOF0, DHT x4, DRI, SOS: FL_JPEG_HEADER_BYTES bytes
+static void jpeg_header(unsigned char *out, uint32_t w, uint32_t h, int quality, uint32_t ri)
+{
+    unsigned char *p = out, q[64];
+    put16(p, 0xffd8);
+    put16(p, 0xffe0); put16(p, 16);
+    for (const unsigned char c : {'J', 'F', 'I', 'F', '\0'}) *p++ = c;
+    *p++ = 1; *p++ = 1; *p++ = 0; put16(p, 1); put16(p, 1); *p++ = 0; *p++ = 0;        // 1.01, no units, 1:1, no thumbnail
+    for (int tab = 0; tab < 2; ++tab) {
+        jpeg_quant_table(quality, tab, q);
+        put16(p, 0xffdb); put16(p, 67); *p++ = (unsigned char)tab;
+        for (int k = 0; k < 64; ++k) *p++ = q[kZigzag[k]];
+    }
+    put16(p, 0xffc0); put16(p, 17); *p++ = 8; put16(p, h); put16(p, w); *p++ = 3;
+    for (int c = 0; c < 3; ++c) { *p++ = (unsigned char)(c + 1); *p++ = 0x11; *p++ = c ? 1 : 0; }
+    put_dht(p, 0x00, kDcLumBits, kDcVals, 12);
+    put_dht(p, 0x10, kAcLumBits, kAcLumVals, 162);
+    put_dht(p, 0x01, kDcChrBits, kDcVals, 12);
+    put_dht(p, 0x11, kAcChrBits, kAcChrVals, 162);
+    put16(p, 0xffdd); put16(p, 4); put16(p, ri);
+    put16(p, 0xffda); put16(p, 12); *p++ = 3;
+    for (int c = 0; c < 3; ++c) { *p++ = (unsigned char)(c + 1); *p++ = c ? 0x11 : 0x00; }
+    *p++ = 0; *p++ = 63; *p++ = 0;
+    static_assert(FL_JPEG_HEADER_BYTES == 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 6 + 14, "header layout");
+}
+
+JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri)
+{
+    JpegLayout l;
+    l.mw = (w + 7u) / 8u;
+    const uint64_t nmcu = (uint64_t)l.mw * ((h + 7u) / 8u);            // <= 8192^2
+    l.nmcu = (uint32_t)nmcu;
+    l.nint = (uint32_t)((nmcu + ri - 1u) / ri);
+    // words: coefficients (int16 x 64 per block) | offsets (u64) | lengths | AC bits (u16 per block) | info
+    l.coef = 0;
+    l.offs = l.coef + (size_t)nmcu * 3u * 32u;
+    l.lens = l.offs + 2u * (size_t)l.nint;
+    l.acbits = l.lens + l.nint;
+    l.info = l.acbits + ((size_t)nmcu * 3u + 1u) / 2u;
+    l.words = l.info + 4u;
+    return l;
+}
+
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri,
+                        uint32_t *scratch, unsigned char *out, size_t cap)
+{
+    const JpegLayout l = jpeg_layout(w, h, ri);
+    short *coef = (short *)(scratch + l.coef);
+    u64 *offs = (u64 *)(scratch + l.offs);
+    uint32_t *lens = scratch + l.lens, *info = scratch + l.info;
+    unsigned short *acbits = (unsigned short *)(scratch + l.acbits);
+    JpegQuant Q;
+    unsigned char q[64];
+    for (int tab = 0; tab < 2; ++tab) {
+        jpeg_quant_table(quality, tab, q);
+        for (int i = 0; i < 64; ++i) Q.q[tab][i] = (float)q[i];
+    }
+    JpegHeaderArg hdr = {};
+    jpeg_header(hdr.b, w, h, quality, ri);
+    const uint32_t nbw = (ri * JPEG_MCU_BITS + 31u) / 32u + 2u;
+    const size_t lds = 4 * (size_t)(kHuffWords + nbw) + 2 * (size_t)((ri * JPEG_MCU_BITS + 7u) / 8u) + 2 + 8 + 4;
+    hipLaunchKernelGGL(k_jpeg_dct, dim3((l.nmcu + 255u) / 256u, 3), dim3(256), 0, st, src, w, h, l.mw, l.nmcu, Q, coef, acbits);
+    hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES);
+    hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, st, lens, l.nint, offs, info, out, (u64)cap, ri, hdr);
+    hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES);
+}

@@ -102,6 +102,14 @@ void launch_resample(hipStream_t st, fl_dim din, fl_dim dout, int ss, float4 *ds
 // output.hip
 void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng, uint32_t nrng, int fmt, void *dst);
 
+// jpeg.hip: baseline JPEG from u8 [3][h][w] Y/Cb/Cr planes.  `scratch` holds jpeg_layout().words words; the 16-byte record, the header and
+// the stream go to `out`, of which nothing at or beyond `cap` (>= 16 + FL_JPEG_HEADER_BYTES) is touched.  ri: MCUs per restart interval, 1..21.
+#define FL_JPEG_RI 8u      // the default: how it was chosen is in DESIGN.md §4.8 (a wave codes one interval, a lane one block, so 3 * ri <= 64)
+struct JpegLayout { uint32_t mw, nmcu, nint; size_t coef, offs, lens, acbits, info, words; };      // MCUs per row / in all, intervals; word offsets into the scratch
+JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri);
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri,
+                        uint32_t *scratch, unsigned char *out, size_t cap);
+
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)
 
 // sort.hip: one stable radix pass (nbits <= 10 at lo_bit) over n keys; hist = scratch of

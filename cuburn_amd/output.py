@@ -132,6 +132,43 @@ class PILOutput(Output):
         return {'.' + self.type: self._save(buf)}, []
 
 
+class DeviceJPEGOutput(Output):
+    """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100}``): the frame leaves the
+    GPU as a finished baseline 4:4:4 file (include/flame_hip.h, fl_output_jpeg).  The host frame is a byte buffer: a 16-byte
+    record (u32 nbytes, status, restart interval, 0), then the file."""
+    suffix = '.jpg'
+
+    def __init__(self, quality=100, alpha=False):
+        if alpha:
+            raise ValueError('the device JPEG encoder has no alpha plane: use "device": false with "alpha"')
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+            raise ValueError('output.quality must be an integer in 1..100')
+        self.quality, self.alpha = quality, False
+
+    @staticmethod
+    def capacity(dim):
+        """Record, header and twice the raw planes: a stream that needs more (noise at quality 100 takes 0.65 of raw) is
+        reported by ``encode`` with the size it needs."""
+        return 16 + _lib.JPEG_HEADER_BYTES + 2 * 3 * dim.w * dim.h
+
+    def shape(self, dim):
+        return (self.capacity(dim),)
+
+    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
+        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
+        _lib.check(_lib.load().fl_output_jpeg(fb.ctx, dim.w, dim.h, self.quality, h_out.ctypes.data if host else None,
+                                              int(dev_out), self.capacity(dim)))
+        return h_out
+
+    def encode(self, buf):
+        if buf is None:
+            return {}, []
+        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
+        if status:
+            raise _lib.FlameError('the JPEG stream needs %d bytes and the frame buffer holds %d' % (nbytes, buf.size - 16))
+        return {'.jpg': io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
+
+
 class PNGOutput(PILOutput):
     def __init__(self, alpha=False):
         PILOutput.__init__(self, 'png', alpha=alpha)
@@ -181,6 +218,10 @@ def get_output_for_profile(gprof):
     """Output module for the profile's ``output`` block (cuburn/output.py:421-436)."""
     opts = dict(gprof.output.raw())
     handler = opts.pop('type', 'jpeg')
+    if opts.pop('device', False):
+        if handler != 'jpeg':
+            raise ValueError('output.device: only jpeg is encoded on the device, not "%s"' % handler)
+        return DeviceJPEGOutput(**opts)
     if handler in ('jpeg', 'png'):
         return PILOutput(codec=handler, **opts)
     if handler == 'tiff':

@@ -266,6 +266,26 @@ enum {
 size_t fl_output_bytes(uint32_t w, uint32_t h, int fmt);   /* 0 for an unknown format */
 int fl_output(fl_ctx *ctx, uint32_t w, uint32_t h, int fmt, void *host_out, uint64_t dev_out);
 
+/* Baseline JPEG stills encoded on the device: SOF0, 8 bit, JFIF 1.01, components 1, 2, 3 = Y, Cb, Cr all sampled
+ * 1x1 in one interleaved scan, the Huffman tables of ITU T.81 Annex K.3-K.6, the quantisation tables of Annex K.1 / K.2 scaled
+ * the libjpeg way for quality 1..100 (100: all ones), restart intervals (DRI) of a length the library chooses.  Partial blocks
+ * replicate the last column / row.  The same planes, quality and size give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status,
+ * u32 restart_interval, u32 0, and behind it the stream.  status 0: the nbytes bytes behind the record are the file.  status 1:
+ * the file needs nbytes bytes and cap - 16 is less; nothing behind the record is valid.  No byte at or beyond cap is touched.
+ * A host_out from fl_host_alloc (any pinned memory) is written by the kernels themselves, so that only the record and nbytes bytes
+ * cross the bus; other host memory receives an asynchronous copy of min(cap, fl_jpeg_bound) bytes.
+ * fl_jpeg_bound: what no stream of that size can exceed, record and header included (0 for w or h of 0 or above 65535).
+ * fl_jpeg_encode: src_dev = u8 [3][h][w] as FL_OUT_YUV444P writes them; queued on the current lane's stream.
+ * fl_output_jpeg: fl_output(FL_OUT_YUV444P) into the lane's pixel buffer (same draws, same dither states afterwards), then the
+ * encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: quality outside 1..100, w or h of 0 or above 65535, a null src_dev,
+ * cap < 16 + FL_JPEG_HEADER_BYTES, host_out and dev_out both null. */
+#define FL_JPEG_HEADER_BYTES 629   /* SOI, APP0, DQT x2, SOF0, DHT x4, DRI, SOS */
+size_t fl_jpeg_bound(uint32_t w, uint32_t h);
+int fl_jpeg_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_jpeg(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -299,7 +319,8 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
 /* The same, split further: ms[0] iterate kernels, [1] tile accumulate, [2] flush, [3] all fl_filter calls,
  * [4] the DE proper — the eight direction kernels, the first normalising the accumulator, the last un-normalising it with a
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
- * (the colorclip that follows, another filter, fl_output, a debug tap); [5] unused since round 5 (always 0). */
+ * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the JPEG encodes' kernels (fl_jpeg_encode,
+ * fl_output_jpeg; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
