@@ -108,6 +108,8 @@ struct Lane {
     DevBuf<float> d_de_sinv;                        // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
     DevBuf<uint32_t> d_jpeg;                        // JPEG encode: coefficients, interval lengths and offsets (jpeg_layout)
     DevBuf<unsigned char> d_jpeg_out;               // ... and the stream on its way to host memory that is not pinned
+    DevBuf<uint32_t> d_png;                         // PNG encode: filtered bytes, coded segments, lengths and offsets (png_layout)
+    DevBuf<unsigned char> d_png_out;                // ... and the file on its way to host memory that is not pinned
     size_t nbins() const { return d_front.cap; }
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
     // accumulate + flush of launch k run on `aux` while launch k+1 iterates on `stream` into the other set
@@ -142,7 +144,7 @@ struct Lane {
     void release()
     {
         release_fb();
-        d_params.release(); d_palette.release(); d_jpeg.release(); d_jpeg_out.release();
+        d_params.release(); d_palette.release(); d_jpeg.release(); d_jpeg_out.release(); d_png.release(); d_png_out.release();
         for (int k = 0; k < 2; ++k) { d_log[k].release(); d_dir[k].release(); }
         if (aux) hipStreamDestroy(aux);
         for (hipEvent_t *ev : events()) if (*ev) hipEventDestroy(*ev);
@@ -1038,6 +1040,83 @@ int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_ou
     return FL_OK;
 }
 
+// ---- PNG stills (png.hip) ----
+// No file can be longer: every segment stored is its bytes and 5 of block header, in an IDAT of 12; the first IDAT also holds the
+// 2 bytes of the zlib header and the last the Adler-32; IEND is 12.  A dynamic segment is only chosen where it is smaller.
+size_t fl_png_bound(uint32_t w, uint32_t h, int channels)
+{
+    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4)) return 0;
+    const uint64_t F = (uint64_t)h * (1u + (uint64_t)w * (uint32_t)channels), seg = png_segment_bytes();
+    const uint64_t n = 16u + FL_PNG_HEADER_BYTES + 2u + F + 17u * ((F + seg - 1u) / seg) + 4u + 12u;
+    return n > 0xffffffffull ? 0 : (size_t)n;
+}
+
+static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    REQUIRE(c, "null ctx");
+    REQUIRE(channels == 3 || channels == 4, "png: channels must be 3 or 4");
+    REQUIRE(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u, "png: width and height must be 1..65535");
+    REQUIRE(fl_png_bound(w, h, channels) != 0, "png: the file could pass 2^32 - 1 bytes");
+    REQUIRE(cap >= 16 + FL_PNG_HEADER_BYTES, "png: capacity below the record and the header");
+    REQUIRE(host_out || dev_out, "png: no destination");
+    return FL_OK;
+}
+
+// The encode proper, queued on the lane's stream (arguments checked); the destination is chosen as jpeg_encode_on chooses it.
+static int png_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels,
+                         void *host_out, uint64_t dev_out, size_t cap)
+{
+    unsigned char *dst = (unsigned char *)(uintptr_t)dev_out;
+    bool copy_back = host_out && dst;
+    const size_t dcap = std::min(cap, fl_png_bound(w, h, channels));      // (what a fitting file can occupy)
+    if (!dst) {
+        hipPointerAttribute_t at = {};
+        const hipError_t e = hipPointerGetAttributes(&at, host_out);
+        if (e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) dst = (unsigned char *)at.devicePointer;
+        else {
+            (void)hipGetLastError();                            // (not a pointer the runtime knows: plain host memory)
+            if (int rc = ln.d_png_out.reserve(dcap, "png file", [&ln] { return ln.quiesce(false); })) return rc;
+            dst = ln.d_png_out;
+            copy_back = true;
+        }
+    }
+    const uint32_t seg = png_segment_bytes();
+    if (int rc = ln.d_png.reserve(png_layout(w, h, channels, seg).words, "png scratch", [&ln] { return ln.quiesce(false); })) return rc;
+    EvPair *e = ev_begin_on(c, c->jpeg_ev, ln.stream);          // (slot 5 of fl_timings_detail: both device encoders)
+    launch_png_encode(ln.stream, src, w, h, channels, seg, ln.d_png, dst, cap);
+    ev_end_on(e, ln.stream);
+    HIPCHK(hipGetLastError());
+    if (copy_back) HIPCHK(hipMemcpyAsync(host_out, dst, dcap, hipMemcpyDeviceToHost, ln.stream));
+    return FL_OK;
+}
+
+int fl_png_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "png: null source pixels");
+    HIPCHK(hipSetDevice(c->device));
+    return png_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, host_out, dev_out, cap);
+}
+
+int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
+    if (rc) return rc;
+    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
+    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
+    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, FL_OUT_RGBA8, ln.d_outpix.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
+    ln.out_rec = true;
+    if ((rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap))) return rc;
+    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
+    return FL_OK;
+}
+
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
                 uint32_t *nvalid)
 {
@@ -1113,7 +1192,7 @@ int fl_timings_detail(fl_ctx *c, float ms[6])
     REQUIRE(c && ms, "null argument");
     sync_all(c);
     ms[0] = sum_ms(c->iter_ev); ms[1] = sum_ms(c->accum_ev); ms[2] = sum_ms(c->flush_ev);
-    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->jpeg_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG encodes
+    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->jpeg_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG and PNG encodes
     return FL_OK;
 }
 

@@ -1,0 +1,609 @@
+// png.hip — 8-bit truecolour PNG (colour type 2 or 6, not interlaced) from u8 [h][w][4] on the device.  DESIGN.md §4.9.
+// Four launches per frame, no host wait between them:
+//   k_png_filter    the Paeth filter on every row: pixels -> the filtered byte stream (a filter byte 4, then w * channels residuals per row)
+//   k_png_segment   one workgroup per segment of `seg` filtered bytes, coded with no reference before its start: tokens (literal / run
+//                   of distance 1) -> histogram -> length-limited Huffman code -> one dynamic block packed in LDS, or one stored block
+//                   when that is no smaller (decided from the counted bits, before anything is emitted); the segment's Adler-32 parts
+//   k_png_scan      one workgroup: the segments' places in the file, the Adler-32 of the whole stream, the 16-byte record and the header
+//   k_png_gather    one workgroup per segment: the finished IDAT (length, tag, bytes, CRC-32) copied to its place, IEND behind the last
+// The segments are byte aligned (an empty stored block behind a dynamic one) and share no history, which is what makes them parallel.
+// Nothing is stored at or beyond `cap`: the gather stores nothing when the file does not fit.
+#include "kernels.h"
+#include <cstdlib>
+
+namespace {
+
+constexpr uint32_t kAdlerMod = 65521u;
+constexpr uint32_t kCrcPoly = 0xedb88320u;
+constexpr uint32_t kLitSyms = 286u, kClSyms = 19u;
+constexpr uint32_t kSymPad = 288u;                            // kLitSyms, rounded up
+__device__ const unsigned char g_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};      // RFC 1951 3.2.7
+
+struct PngHeaderArg { unsigned char b[FL_PNG_HEADER_BYTES]; };
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
+    return v;
+}
+
+// ---- the filter ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t paeth(int a, int b, int c)
+{
+    const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
+    return (uint32_t)(pa <= pb && pa <= pc ? a : pb <= pc ? b : c);
+}
+
+// A thread per four bytes of the stream (F < 2^32 bytes, rows of rowlen = 1 + w * CH); filt holds ceil(F / 4) words.
+template <int CH>
+__global__ void __launch_bounds__(256)
+k_png_filter(const unsigned char *__restrict__ src, uint32_t w, uint32_t rowlen, uint32_t F, uint32_t *__restrict__ filt)
+{
+    const u64 p64 = ((u64)blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (p64 >= F) return;
+    const uint32_t p0 = (uint32_t)p64;
+    uint32_t row = p0 / rowlen, col = p0 - row * rowlen, out = 0;
+    const size_t pitch = (size_t)w * 4u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (p64 + k >= F) break;
+        uint32_t v = 4u;                                      // the row's filter byte: Paeth
+        if (col) {
+            const uint32_t x = col - 1u, px = x / CH, cp = x - px * CH;
+            const unsigned char *s = src + (size_t)row * pitch + (size_t)px * 4u + cp;
+            const int a = px ? s[-4] : 0, b = row ? *(s - pitch) : 0, c = px && row ? *(s - pitch - 4) : 0;
+            v = ((uint32_t)s[0] - paeth(a, b, c)) & 0xffu;
+        }
+        out |= v << (8u * k);
+        if (++col == rowlen) { col = 0; ++row; }
+    }
+    filt[p0 >> 2] = out;
+}
+
+// ---- tokens ---------------------------------------------------------------------------------------------------------
+// A segment's bytes fall into groups: a head, which differs from the byte before it (or starts the segment), and the bytes behind it
+// that repeat it.  The head is a literal; r repeats are matches of distance 1 and length min(r, 258) while r >= 3, then literals.
+// A group belongs to the lane in whose span its head lies, so the tokens do not depend on how the spans cut the segment.
+__device__ __forceinline__ void len_symbol(uint32_t L, uint32_t &sym, uint32_t &eb, uint32_t &ev)      // 3 <= L <= 258 (RFC 1951 3.2.5)
+{
+    const uint32_t l = L - 3u;
+    if (L == 258u) { sym = 285u; eb = 0; ev = 0; return; }
+    if (l < 8u) { sym = 257u + l; eb = 0; ev = 0; return; }
+    eb = 29u - (uint32_t)__clz(l);                            // floor(log2 l) - 2
+    sym = 261u + 4u * eb + (l >> eb & 3u);
+    ev = l & ((1u << eb) - 1u);
+}
+
+struct Tok { int prev; uint32_t run; };
+template <class S>
+__device__ __forceinline__ void flush_run(uint32_t run, int prev, S &s)
+{
+    while (run >= 3u) { const uint32_t L = min(run, 258u); s.match(L); run -= L; }
+    for (; run; --run) s.lit((uint32_t)prev);
+}
+template <class S>
+__device__ __forceinline__ void step(Tok &t, uint32_t b, S &s)
+{
+    if ((int)b == t.prev) { ++t.run; return; }
+    flush_run(t.run, t.prev, s);
+    t.run = 0; t.prev = (int)b;
+    s.lit(b);
+}
+
+// f(pos, byte) for the bytes [from, hi) of the segment at sp (16-byte aligned; the buffer is readable up to the next 16-byte boundary)
+template <class Fn>
+__device__ __forceinline__ void for_bytes(const unsigned char *sp, uint32_t from, uint32_t hi, Fn &&f)
+{
+    for (uint32_t q = from & ~15u; q < hi; q += 16u) {
+        const uint4 v = *(const uint4 *)(sp + q);
+        const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+#pragma unroll 1
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t pos = q + 4u * j + k;
+                if (pos >= from && pos < hi) f(pos, wd[j] >> (8u * k) & 0xffu);
+            }
+    }
+}
+
+struct Bits {                         // a lane's writer into the segment's bit buffer: bytes fill from the least significant bit, words are little-endian
+    uint32_t *words; uint32_t w; u64 acc; uint32_t n;
+    __device__ __forceinline__ void put(uint32_t v, uint32_t len)          // len <= 32, n < 32
+    {
+        acc |= (u64)v << n;
+        n += len;
+        if (n >= 32u) { atomicOr(&words[w++], (uint32_t)acc); acc >>= 32; n -= 32u; }
+    }
+    __device__ __forceinline__ void flush() { if (n) atomicOr(&words[w], (uint32_t)acc); }
+};
+__device__ __forceinline__ Bits bits_at(uint32_t *words, uint32_t bit) { return Bits{words, bit >> 5, 0, bit & 31u}; }
+
+struct HistSink {
+    uint32_t *hist; uint32_t nm;
+    __device__ __forceinline__ void lit(uint32_t b) { atomicAdd(&hist[b], 1u); }
+    __device__ __forceinline__ void match(uint32_t L) { uint32_t s, eb, ev; len_symbol(L, s, eb, ev); atomicAdd(&hist[s], 1u); ++nm; }
+};
+struct CountSink {                    // code[s] = bit-reversed code | length << 16
+    const uint32_t *code; uint32_t bits;
+    __device__ __forceinline__ void lit(uint32_t b) { bits += code[b] >> 16; }
+    __device__ __forceinline__ void match(uint32_t L) { uint32_t s, eb, ev; len_symbol(L, s, eb, ev); bits += (code[s] >> 16) + eb + 1u; }
+};
+struct EmitSink {
+    const uint32_t *code; Bits b;
+    __device__ __forceinline__ void lit(uint32_t v) { const uint32_t c = code[v]; b.put(c & 0xffffu, c >> 16); }
+    __device__ __forceinline__ void match(uint32_t L)
+    {
+        uint32_t s, eb, ev;
+        len_symbol(L, s, eb, ev);
+        const uint32_t c = code[s];
+        b.put(c & 0xffffu, c >> 16);
+        b.put(ev, eb + 1u);                                   // the extra bits, and the lone distance code (symbol 0, one bit: 0)
+    }
+};
+
+// ---- length-limited Huffman codes, by the whole workgroup (256 threads, nsym <= 288) ----------------------------------
+struct HuffTmp {
+    uint32_t sfreq[kSymPad], nfreq[kSymPad], cnt[32], next[16];
+    unsigned short ssym[kSymPad], lpar[kSymPad], npar[kSymPad];
+};
+
+// lens[s] = code length of symbol s (0: unused) of a complete prefix code with no length above maxlen, Huffman's where that obeys the
+// limit.  A lone used symbol gets a one-bit code and so does an unused neighbour, which keeps the code complete.
+__device__ void build_lengths(const uint32_t *freq, uint32_t nsym, uint32_t maxlen, unsigned char *lens, HuffTmp &T)
+{
+    const uint32_t t = threadIdx.x;
+    uint32_t used = 0;
+    for (uint32_t i = t; i < kSymPad; i += 256u) {
+        const uint32_t f = i < nsym ? freq[i] : 0u;
+        if (i < nsym) lens[i] = 0;
+        if (f) {                                              // rank by (frequency, symbol), ascending
+            uint32_t r = 0;
+#pragma unroll 8
+            for (uint32_t j = 0; j < nsym; ++j) { const uint32_t fj = freq[j]; r += fj && (fj < f || (fj == f && j < i)) ? 1u : 0u; }
+            T.sfreq[r] = f; T.ssym[r] = (unsigned short)i;
+            ++used;
+        }
+    }
+    if (t < 32u) T.cnt[t] = 0;
+    const uint32_t n = (uint32_t)__syncthreads_count(used >= 1u) + (uint32_t)__syncthreads_count(used >= 2u);
+    if (n == 0) return;
+    if (n == 1u) {
+        if (t == 0) { const uint32_t s = T.ssym[0]; lens[s] = 1; lens[s ? 0 : 1] = 1; }
+        __syncthreads();
+        return;
+    }
+    if (t == 0) {                                             // the two-queue merge: leaves in order, inner nodes in order of creation
+        constexpr uint32_t kNone = 0xffffffffu;               // an empty queue (no frequency reaches it)
+        uint32_t leaf = 0, node = 0;
+        uint32_t lf = T.sfreq[0], lf1 = T.sfreq[1], nf = kNone;      // the queues' heads, and the leaf behind the head: loaded ahead of their use
+        for (uint32_t k = 0; k + 1u < n; ++k) {
+            uint32_t f = 0;
+#pragma unroll
+            for (int pick = 0; pick < 2; ++pick) {
+                if (lf <= nf) {                               // (a tie takes the leaf)
+                    f += lf; T.lpar[leaf++] = (unsigned short)k;
+                    lf = lf1; lf1 = leaf + 1u < n ? T.sfreq[leaf + 1u] : kNone;
+                } else {
+                    f += nf; T.npar[node++] = (unsigned short)k;
+                    nf = node < k ? T.nfreq[node] : kNone;
+                }
+            }
+            T.nfreq[k] = f;
+            if (node == k) nf = f;                            // the new node is the only one waiting
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += 256u) {                  // a leaf's depth: the steps from it to the root, node n - 2
+        uint32_t d = 1u;
+        for (uint32_t k = T.lpar[i]; k != n - 2u; k = T.npar[k]) ++d;
+        atomicAdd(&T.cnt[min(d, maxlen)], 1u);
+    }
+    __syncthreads();
+    if (t == 0) {                                             // depths cut at maxlen over-subscribe the code: lengthen until Kraft's sum is 1 again
+        uint32_t total = 0;
+        for (uint32_t l = 1; l <= maxlen; ++l) total += T.cnt[l] << (maxlen - l);
+        while (total > 1u << maxlen) {
+            --T.cnt[maxlen];
+            for (uint32_t l = maxlen - 1u; l > 0; --l)
+                if (T.cnt[l]) { --T.cnt[l]; T.cnt[l + 1u] += 2u; break; }
+            --total;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += 256u) {                  // the rarest symbols take the longest codes
+        uint32_t l = maxlen, above = T.cnt[maxlen];
+        while (i >= above && l > 1u) above += T.cnt[--l];
+        lens[T.ssym[i]] = (unsigned char)l;
+    }
+    __syncthreads();
+}
+
+// code[s] = the canonical code of RFC 1951 3.2.2, bit-reversed (deflate sends Huffman codes from their most significant bit) | length << 16
+__device__ void canonical_codes(const unsigned char *lens, uint32_t nsym, uint32_t *code, HuffTmp &T)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < 32u) T.cnt[t] = 0;
+    __syncthreads();
+    for (uint32_t i = t; i < nsym; i += 256u) if (lens[i]) atomicAdd(&T.cnt[lens[i]], 1u);
+    __syncthreads();
+    if (t == 0) {
+        uint32_t c = 0;
+        T.next[0] = 0;
+        for (uint32_t b = 1; b < 16u; ++b) { c = (c + T.cnt[b - 1u]) << 1; T.next[b] = c; }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < nsym; i += 256u) {
+        const uint32_t l = lens[i];
+        uint32_t r = 0;
+        if (l) {
+#pragma unroll 8
+            for (uint32_t j = 0; j < i; ++j) r += lens[j] == l ? 1u : 0u;
+        }
+        code[i] = l ? __brev(T.next[l] + r) >> (32u - l) | l << 16 : 0u;
+    }
+    __syncthreads();
+}
+
+// ---- one segment per workgroup -----------------------------------------------------------------------------------------
+// Lane t owns the bytes [t * per, (t + 1) * per) of the segment (per a multiple of 16, 256 * per >= seg).  The segment's bytes
+// (lens[it] of them, at most n + 5: the stored form) go to segbuf + it * stride; adl[it] = its own Adler-32 (a | b << 16).
+// Dynamic LDS: the bit buffer, (seg + 8) / 4 + 2 words.
+__global__ void __launch_bounds__(256)
+k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, uint32_t nseg, uint32_t per,
+              unsigned char *__restrict__ segbuf, uint32_t stride, uint32_t *__restrict__ lens, uint32_t *__restrict__ adl)
+{
+    extern __shared__ uint32_t s_bits[];
+    __shared__ uint32_t s_hist[kSymPad], s_code[kSymPad], s_clfreq[kClSyms], s_clcode[kClSyms], s_misc[8], s_wsum[4];
+    __shared__ unsigned char s_len[kSymPad], s_cllen[kClSyms];
+    __shared__ unsigned short s_lead[256], s_seq[320];
+    __shared__ HuffTmp T;
+    enum { kMatches = 0, kSum1, kSum2, kNseq, kHdrBits, kHclen, kHlit };
+    const uint32_t t = threadIdx.x, it = blockIdx.x;
+    const uint32_t base = it * seg, n = min(seg, F - base);
+    const bool last = it + 1u == nseg;
+    const unsigned char *sp = filt + base;
+    const uint32_t lo = min(t * per, n), hi = min(lo + per, n);
+    for (uint32_t i = t; i < kSymPad; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;      // one end-of-block
+    if (t < kClSyms) s_clfreq[t] = 0;
+    if (t < 8u) s_misc[t] = 0;
+    __syncthreads();
+
+    // pass A: the histogram of the groups whose head lies here, the leading bytes that belong to a group before, the Adler sums
+    const int prevb = lo && lo < hi ? (int)sp[lo - 1u] : -1;
+    uint32_t lead = 0, s1 = 0, s2 = 0;
+    bool started = false;
+    HistSink hs = {s_hist, 0};
+    Tok tk = {prevb, 0};
+    for_bytes(sp, lo, hi, [&](uint32_t pos, uint32_t b) {
+        s1 += b; s2 += (n - pos) * b;                         // (per <= 128: below 2^30)
+        if (!started) {
+            if ((int)b == prevb) { ++lead; return; }
+            started = true;
+        }
+        step(tk, b, hs);
+    });
+    s_lead[t] = (unsigned short)lead;
+    if (s1) { atomicAdd(&s_misc[kSum1], s1 % kAdlerMod); atomicAdd(&s_misc[kSum2], s2 % kAdlerMod); }
+    __syncthreads();
+    uint32_t tail = 0;                                        // bytes of this lane's last group: its repeats here and in the lanes behind
+    if (started) {
+        tail = tk.run;
+        for (uint32_t j = t + 1u; j < 256u; ++j) {
+            const uint32_t jlo = min(j * per, n), jn = min(jlo + per, n) - jlo, l = s_lead[j];
+            tail += l;
+            if (jn == 0 || l < jn) break;
+        }
+        flush_run(tail, tk.prev, hs);
+    }
+    if (hs.nm) atomicAdd(&s_misc[kMatches], hs.nm);
+    __syncthreads();
+    const uint32_t nmatch = s_misc[kMatches];
+
+    build_lengths(s_hist, kLitSyms, 15u, s_len, T);
+    canonical_codes(s_len, kLitSyms, s_code, T);
+
+    // the code lengths, run-length coded in the code-length alphabet (RFC 1951 3.2.7): s_seq = symbol | extra << 8
+    if (t == 0) {
+        uint32_t hlit = kLitSyms;
+        while (hlit > 257u && s_len[hlit - 1u] == 0) --hlit;
+        const uint32_t N = hlit + 1u, dlen = nmatch ? 1u : 0u;            // one distance code: length 1 when a match uses it, 0 when none does
+        uint32_t ns = 0;
+        auto emit = [&](uint32_t sym, uint32_t extra) { s_seq[ns++] = (unsigned short)(sym | extra << 8); ++s_clfreq[sym]; };
+        for (uint32_t i = 0; i < N;) {
+            const uint32_t v = i < hlit ? s_len[i] : dlen;
+            uint32_t r = 1;
+            while (i + r < N && (i + r < hlit ? s_len[i + r] : dlen) == v) ++r;
+            i += r;
+            if (v == 0) {
+                while (r >= 11u) { const uint32_t k = min(r, 138u); emit(18u, k - 11u); r -= k; }
+                if (r >= 3u) { emit(17u, r - 3u); r = 0; }
+                for (; r; --r) emit(0u, 0u);
+            } else {
+                emit(v, 0u); --r;
+                while (r >= 3u) { const uint32_t k = min(r, 6u); emit(16u, k - 3u); r -= k; }
+                for (; r; --r) emit(v, 0u);
+            }
+        }
+        s_misc[kNseq] = ns; s_misc[kHlit] = hlit;
+    }
+    __syncthreads();
+    build_lengths(s_clfreq, kClSyms, 7u, s_cllen, T);
+    canonical_codes(s_cllen, kClSyms, s_clcode, T);
+    if (t == 0) {
+        uint32_t hclen = kClSyms;
+        while (hclen > 4u && s_cllen[g_cl_order[hclen - 1u]] == 0) --hclen;
+        uint32_t bits = 3u + 14u + 3u * hclen + 2u * s_clfreq[16] + 3u * s_clfreq[17] + 7u * s_clfreq[18];
+        for (uint32_t s = 0; s < kClSyms; ++s) bits += s_clfreq[s] * s_cllen[s];
+        s_misc[kHdrBits] = bits; s_misc[kHclen] = hclen;
+    }
+
+    // pass B: the bits of every lane's tokens, and their prefix sum
+    const uint32_t from = lo + lead;
+    CountSink cs = {s_code, 0};
+    if (started) {
+        Tok tb = {-1, 0};
+        for_bytes(sp, from, hi, [&](uint32_t, uint32_t b) { step(tb, b, cs); });
+        flush_run(tail, tb.prev, cs);
+    }
+    const uint32_t mybits = cs.bits, lane = t & 63u, wv = t >> 6;
+    uint32_t incl = wave_incl_scan(mybits, lane);
+    if (lane == 63u) s_wsum[wv] = incl;
+    __syncthreads();
+    for (uint32_t k = 0; k < wv; ++k) incl += s_wsum[k];
+    const uint32_t D = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+    const uint32_t hdr = s_misc[kHdrBits], eob = s_code[256] >> 16;
+    const uint32_t Tdyn = hdr + D + eob;                                 // (at most 15 bits a byte and a header below 3000: no overflow)
+    // behind a dynamic block that is not the last: an empty stored block — three header bits, padding to a byte, 00 00 FF FF
+    const uint32_t dynbytes = last ? (Tdyn + 7u) / 8u : (Tdyn + 3u + 7u) / 8u + 4u;
+    const bool dynamic = dynbytes < n + 5u;
+    const uint32_t outbytes = dynamic ? dynbytes : n + 5u, outwords = (outbytes + 3u) / 4u;
+    for (uint32_t i = t; i <= outwords; i += 256u) s_bits[i] = 0;
+    __syncthreads();
+
+    if (dynamic) {
+        if (t == 0) {
+            Bits b = bits_at(s_bits, 0);
+            const uint32_t hclen = s_misc[kHclen], ns = s_misc[kNseq];
+            b.put(last ? 1u : 0u, 1u); b.put(2u, 2u);
+            b.put(s_misc[kHlit] - 257u, 5u); b.put(0u, 5u); b.put(hclen - 4u, 4u);
+            for (uint32_t i = 0; i < hclen; ++i) b.put(s_cllen[g_cl_order[i]], 3u);
+            for (uint32_t i = 0; i < ns; ++i) {
+                const uint32_t e = s_seq[i], sym = e & 0xffu, c = s_clcode[sym];
+                b.put(c & 0xffffu, c >> 16);
+                if (sym >= 16u) b.put(e >> 8, sym == 16u ? 2u : sym == 17u ? 3u : 7u);
+            }
+            b.flush();
+            Bits e = bits_at(s_bits, hdr + D);
+            e.put(s_code[256] & 0xffffu, eob);
+            e.flush();
+            if (!last)                                                     // NLEN of the empty stored block (a word that tokens may share)
+                for (uint32_t pos = dynbytes - 2u; pos < dynbytes; ++pos) atomicOr(&s_bits[pos >> 2], 0xffu << (8u * (pos & 3u)));
+        }
+        if (started) {
+            EmitSink es = {s_code, bits_at(s_bits, hdr + incl - mybits)};
+            Tok tc = {-1, 0};
+            for_bytes(sp, from, hi, [&](uint32_t, uint32_t b) { step(tc, b, es); });
+            flush_run(tail, tc.prev, es);
+            es.b.flush();
+        }
+    } else {
+        unsigned char *bytes = (unsigned char *)s_bits;
+        if (t == 0) {
+            bytes[0] = last ? 1 : 0;
+            bytes[1] = (unsigned char)n; bytes[2] = (unsigned char)(n >> 8);
+            bytes[3] = (unsigned char)~n; bytes[4] = (unsigned char)(~n >> 8);
+        }
+        for (uint32_t i = t; i < n; i += 256u) bytes[5u + i] = sp[i];
+    }
+    __syncthreads();
+    uint32_t *dst = (uint32_t *)(segbuf + (size_t)it * stride);
+    for (uint32_t i = t; i < outwords; i += 256u) dst[i] = s_bits[i];
+    if (t == 0) {
+        lens[it] = outbytes;
+        adl[it] = (1u + s_misc[kSum1]) % kAdlerMod | ((n + s_misc[kSum2]) % kAdlerMod) << 16;
+    }
+}
+
+// ---- where the segments go ---------------------------------------------------------------------------------------------
+// IDAT i holds segment i; the first also the two bytes of the zlib header, the last also the Adler-32.  offs[i] = where IDAT i starts in
+// the file; info = {file bytes low, high, status, Adler-32}.  The record and the signature + IHDR go to `out`.
+__device__ __forceinline__ uint32_t idat_data_bytes(uint32_t len, uint32_t i, uint32_t nseg) { return len + (i == 0 ? 2u : 0u) + (i + 1u == nseg ? 4u : 0u); }
+
+__global__ void __launch_bounds__(1024)
+k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, uint32_t nseg, uint32_t seg, uint32_t F,
+           u64 *__restrict__ offs, uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap, PngHeaderArg hdr)
+{
+    __shared__ u64 s_sum[1024];
+    const uint32_t t = threadIdx.x, per = (nseg + 1023u) / 1024u, lo = min(t * per, nseg), hi = min(lo + per, nseg);
+    u64 mine = 0;
+    for (uint32_t i = lo; i < hi; ++i) mine += 12u + idat_data_bytes(lens[i], i, nseg);
+    s_sum[t] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const u64 o = t >= d ? s_sum[t - d] : 0;
+        __syncthreads();
+        s_sum[t] += o;
+        __syncthreads();
+    }
+    u64 run = (u64)FL_PNG_HEADER_BYTES + s_sum[t] - mine;
+    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += 12u + idat_data_bytes(lens[i], i, nseg); }
+    const u64 need = (u64)FL_PNG_HEADER_BYTES + s_sum[1023] + 12u;         // bytes behind the record, IEND included
+    const uint32_t status = need > cap - 16u ? 1u : 0u;
+    if (t == 0) {
+        // Adler-32 of a concatenation: a = a1 + a2 - 1, b = b1 + b2 + len2 * (a1 - 1), mod 65521
+        uint32_t A = 1u, B = 0u;
+        for (uint32_t i = 0; i < nseg; ++i) {
+            const uint32_t a2 = adl[i] & 0xffffu, b2 = adl[i] >> 16, len2 = i + 1u == nseg ? F - i * seg : seg;
+            B = (uint32_t)((B + b2 + (u64)(len2 % kAdlerMod) * ((A + kAdlerMod - 1u) % kAdlerMod)) % kAdlerMod);
+            A = (A + a2 + kAdlerMod - 1u) % kAdlerMod;
+        }
+        info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = B << 16 | A;
+    }
+    if (t < 16) {
+        const uint32_t rec[4] = {need > 0xffffffffull ? 0xffffffffu : (uint32_t)need, status, seg, 0u};
+        out[t] = (unsigned char)(rec[t >> 2] >> (8u * (t & 3u)));
+    }
+    if (t < FL_PNG_HEADER_BYTES) out[16u + t] = hdr.b[t];                  // (cap >= 16 + the header: the callers checked)
+}
+
+// ---- the finished chunks ---------------------------------------------------------------------------------------------
+// a * b mod the CRC-32 polynomial, both in the reflected form the CRC register has (bit 31 = x^0)
+__device__ __forceinline__ uint32_t crc_mul(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+#pragma unroll 4
+    for (uint32_t i = 0; i < 32u; ++i) {
+        p ^= a & 0x80000000u >> i ? b : 0u;
+        b = b & 1u ? b >> 1 ^ kCrcPoly : b >> 1;
+    }
+    return p;
+}
+__device__ __forceinline__ uint32_t crc_pow(uint32_t x, uint32_t e)
+{
+    uint32_t r = 0x80000000u;                                 // 1
+    for (; e; e >>= 1) { if (e & 1u) r = crc_mul(r, x); x = crc_mul(x, x); }
+    return r;
+}
+
+// One workgroup per segment: length, "IDAT", the bytes, the CRC-32 (and IEND behind the last) assembled in LDS and stored at
+// out + 16 + offs[it].  The CRC: with a register that starts at zero the CRC is linear in the message and blind to leading zero
+// bytes, so every lane takes an equal share of the (front-padded) message and the shares combine as sum of crc_k * x^(8 * bytes
+// behind share k).  The initial 0xFFFFFFFF is the first four bytes — the tag — inverted; the final inversion is applied at the end.
+// Dynamic LDS: seg + 5 + 38 bytes, rounded up to words, and 2 words of padding.
+__global__ void __launch_bounds__(256)
+k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const uint32_t *__restrict__ lens, const u64 *__restrict__ offs,
+             const uint32_t *__restrict__ info, uint32_t nseg, unsigned char *__restrict__ out)
+{
+    extern __shared__ uint32_t s_mem[];
+    __shared__ uint32_t s_tab[256], s_crc;
+    unsigned char *s_chunk = (unsigned char *)s_mem;
+    const uint32_t t = threadIdx.x, it = blockIdx.x;
+    if (info[2]) return;
+    const bool first = it == 0, last = it + 1u == nseg;
+    const uint32_t L = lens[it], dlen = idat_data_bytes(L, it, nseg), body = 8u + (first ? 2u : 0u);
+    {
+        uint32_t c = t;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c = c & 1u ? c >> 1 ^ kCrcPoly : c >> 1;
+        s_tab[t] = c;
+    }
+    if (t == 0) {
+        s_crc = 0;
+        const unsigned char head[10] = {(unsigned char)(dlen >> 24), (unsigned char)(dlen >> 16), (unsigned char)(dlen >> 8), (unsigned char)dlen,
+                                        'I', 'D', 'A', 'T', 0x78, 0x01};      // zlib: deflate, 32 KiB window, no dictionary, FCHECK
+        for (uint32_t i = 0; i < body; ++i) s_chunk[i] = head[i];
+        if (last) {
+            const uint32_t ad = info[3];
+            for (uint32_t i = 0; i < 4u; ++i) s_chunk[body + L + i] = (unsigned char)(ad >> (24u - 8u * i));
+            const unsigned char iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
+            for (uint32_t i = 0; i < 12u; ++i) s_chunk[12u + dlen + i] = iend[i];
+        }
+    }
+    const uint32_t *src = (const uint32_t *)(segbuf + (size_t)it * stride);
+    for (uint32_t i = t; i < (L + 3u) / 4u; i += 256u) {
+        const uint32_t wd = src[i];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) s_chunk[body + 4u * i + k] = (unsigned char)(wd >> (8u * k));
+    }
+    __syncthreads();
+    // the CRC of tag + data: M bytes from s_chunk + 4, padded in front to 256 shares of S
+    const uint32_t M = 4u + dlen, S = (M + 255u) / 256u, pad = 256u * S - M;
+    uint32_t crc = 0;
+    for (uint32_t v = t * S; v < (t + 1u) * S; ++v) {
+        if (v < pad) continue;
+        const uint32_t m = v - pad, byte = s_chunk[4u + m] ^ (m < 4u ? 0xffu : 0u);
+        crc = s_tab[(crc ^ byte) & 0xffu] ^ crc >> 8;
+    }
+    const uint32_t xs = crc_pow(0x00800000u, S);              // x^(8 S)
+    crc = crc_mul(crc, crc_pow(xs, 255u - t));
+    if (crc) atomicXor(&s_crc, crc);
+    __syncthreads();
+    if (t < 4u) s_chunk[8u + dlen + t] = (unsigned char)(~s_crc >> (24u - 8u * t));
+    __syncthreads();
+    // to the file: bytes up to the first 4-byte boundary of the destination, dwords, and the bytes that are left
+    const uint32_t N = 12u + dlen + (last ? 12u : 0u);
+    unsigned char *dst = out + 16u + offs[it];
+    const uint32_t head = min(N, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u)), nmid = (N - head) >> 2, tail0 = head + 4u * nmid;
+    if (t < head) dst[t] = s_chunk[t];
+    for (uint32_t m = t; m < nmid; m += 256u) {
+        const uint32_t so = head + 4u * m, sh = (so & 3u) * 8u;
+        const uint32_t a = s_mem[so >> 2], c = s_mem[(so >> 2) + 1u];
+        *(uint32_t *)(dst + so) = sh ? a >> sh | c << (32u - sh) : a;
+    }
+    if (t < N - tail0) dst[tail0 + t] = s_chunk[tail0 + t];
+}
+
+uint32_t crc32_host(const unsigned char *p, size_t n)
+{
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < n; ++i) {
+        c ^= p[i];
+        for (int k = 0; k < 8; ++k) c = c & 1u ? c >> 1 ^ kCrcPoly : c >> 1;
+    }
+    return ~c;
+}
+void put32(unsigned char *&p, uint32_t v) { *p++ = (unsigned char)(v >> 24); *p++ = (unsigned char)(v >> 16); *p++ = (unsigned char)(v >> 8); *p++ = (unsigned char)v; }
+
+} // namespace
+
+uint32_t png_segment_bytes()
+{
+    static const uint32_t seg = [] {
+        uint32_t v = FL_PNG_SEG;
+        if (const char *e = getenv("FLAME_PNG_SEG")) { const long x = atol(e); if (x >= 8192 && x <= 32768) v = (uint32_t)x & ~15u; }
+        return v;
+    }();
+    return seg;
+}
+
+PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg)
+{
+    PngLayout l;
+    l.rowlen = 1u + w * (uint32_t)channels;
+    l.F = (uint64_t)l.rowlen * h;
+    l.nseg = (uint32_t)((l.F + seg - 1u) / seg);
+    l.stride = seg + 16u;                                     // a stored segment is seg + 5 bytes; rows of the scratch stay 16-byte aligned
+    l.per = 16u * ((seg + 4095u) / 4096u);
+    // words: the filtered stream (read in 16-byte pieces) | the coded segments | offsets (u64) | lengths | Adler parts | info
+    l.filt = 0;
+    l.segbuf = l.filt + (size_t)((l.F + 15u) / 16u) * 4u + 4u;
+    l.offs = l.segbuf + (size_t)l.nseg * (l.stride / 4u);
+    l.offs += l.offs & 1u;
+    l.lens = l.offs + 2u * (size_t)l.nseg;
+    l.adl = l.lens + l.nseg;
+    l.info = l.adl + l.nseg;
+    l.words = l.info + 4u;
+    return l;
+}
+
+void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, uint32_t seg,
+                       uint32_t *scratch, unsigned char *out, size_t cap)
+{
+    const PngLayout l = png_layout(w, h, channels, seg);
+    const uint32_t F = (uint32_t)l.F;                         // (the callers refuse frames whose stream passes 2^32 - 1 bytes)
+    uint32_t *filt = scratch + l.filt, *lens = scratch + l.lens, *adl = scratch + l.adl, *info = scratch + l.info;
+    unsigned char *segbuf = (unsigned char *)(scratch + l.segbuf);
+    u64 *offs = (u64 *)(scratch + l.offs);
+    PngHeaderArg hdr = {};
+    unsigned char *p = hdr.b;
+    const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    for (const unsigned char c : sig) *p++ = c;
+    put32(p, 13);
+    unsigned char *ihdr = p;
+    for (const unsigned char c : {'I', 'H', 'D', 'R'}) *p++ = c;
+    put32(p, w); put32(p, h);
+    *p++ = 8; *p++ = channels == 4 ? 6 : 2; *p++ = 0; *p++ = 0; *p++ = 0;      // 8 bit, truecolour (with alpha), deflate, adaptive filtering, not interlaced
+    put32(p, crc32_host(ihdr, 17));
+    static_assert(FL_PNG_HEADER_BYTES == 8 + 12 + 13, "header layout");
+    const uint32_t nthreads4 = (uint32_t)((l.F + 3u) / 4u);
+    const dim3 fgrid((nthreads4 + 255u) / 256u);
+    if (channels == 4) hipLaunchKernelGGL(k_png_filter<4>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
+    else hipLaunchKernelGGL(k_png_filter<3>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
+    hipLaunchKernelGGL(k_png_segment, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 8u) / 4u + 2u), st, (const unsigned char *)filt, F, seg,
+                       l.nseg, l.per, segbuf, l.stride, lens, adl);
+    hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(1024), 0, st, lens, adl, l.nseg, seg, F, offs, info, out, (u64)cap, hdr);
+    hipLaunchKernelGGL(k_png_gather, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 5u + 38u + 3u) / 4u + 2u), st, segbuf, l.stride, lens, offs, info,
+                       l.nseg, out);
+}

@@ -169,6 +169,39 @@ class DeviceJPEGOutput(Output):
         return {'.jpg': io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
 
 
+class DevicePNGOutput(Output):
+    """PNG stills encoded on the device (``output: {"type": "png", "encoder": "device", "alpha": bool}``): the frame leaves the GPU
+    as a finished 8-bit truecolour file, Paeth-filtered and deflated in independent segments (include/flame_hip.h,
+    fl_output_png).  The host frame is a byte buffer: a 16-byte record (u32 nbytes, status, segment bytes, 0), then the file."""
+    suffix = '.png'
+
+    def __init__(self, alpha=False):
+        if not isinstance(alpha, bool):
+            raise ValueError('output.alpha must be true or false')
+        self.alpha, self.channels = alpha, 4 if alpha else 3
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (noise is stored, at 17 bytes per segment above its own size)."""
+        return int(_lib.load().fl_png_bound(dim.w, dim.h, self.channels))
+
+    def shape(self, dim):
+        return (self.capacity(dim),)
+
+    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
+        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
+        _lib.check(_lib.load().fl_output_png(fb.ctx, dim.w, dim.h, self.channels, h_out.ctypes.data if host else None,
+                                             int(dev_out), self.capacity(dim)))
+        return h_out
+
+    def encode(self, buf):
+        if buf is None:
+            return {}, []
+        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
+        if status:
+            raise _lib.FlameError('the PNG file needs %d bytes and the frame buffer holds %d' % (nbytes, buf.size - 16))
+        return {'.png': io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
+
+
 class PNGOutput(PILOutput):
     def __init__(self, alpha=False):
         PILOutput.__init__(self, 'png', alpha=alpha)
@@ -222,6 +255,15 @@ def get_output_for_profile(gprof):
         if handler != 'jpeg':
             raise ValueError('output.device: only jpeg is encoded on the device, not "%s"' % handler)
         return DeviceJPEGOutput(**opts)
+    encoder = opts.pop('encoder', None)
+    if encoder is not None:
+        if encoder != 'device':
+            raise ValueError('output.encoder: "device" is the only encoder to choose, not "%s"' % (encoder,))
+        if handler != 'png':
+            raise ValueError('output.encoder: selects the device PNG encoder ("device": true is the JPEG switch), not "%s"' % handler)
+        if set(opts) - {'alpha'}:
+            raise ValueError('the device PNG encoder takes "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha'})))
+        return DevicePNGOutput(**opts)
     if handler in ('jpeg', 'png'):
         return PILOutput(codec=handler, **opts)
     if handler == 'tiff':

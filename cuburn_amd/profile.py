@@ -53,7 +53,8 @@ def add_args(parser=None):
     out = parser.add_argument_group('Output options')
     out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'x264', 'vp8', 'vp9', 'prores', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
-                     help='Encode jpeg stills on the GPU (sets output.device)')
+                     help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
+                          'output.encoder to "device")')
     out.add_argument('--quality', type=int, metavar='N', help='JPEG quality, 1..100 (sets output.quality)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
@@ -82,7 +83,8 @@ def get_from_args(args):
     if ns.get('codec') is not None:
         prof['output'] = dict(prof.get('output') or {}, type=ns['codec'])
     if ns.get('device_encode'):
-        prof['output'] = dict(prof.get('output') or {}, device=True)
+        out = dict(prof.get('output') or {})
+        prof['output'] = dict(out, encoder='device') if out.get('type') == 'png' else dict(out, device=True)
     if ns.get('quality') is not None:
         prof['output'] = dict(prof.get('output') or {}, quality=ns['quality'])
     return name, prof

@@ -408,4 +408,5 @@ class RenderManager(object):
         return dict(iter_ms=it.value, flush_ms=fl.value, filter_ms=ft.value, launches=n.value,
                     accum_ms=d[1], flush_only_ms=d[2], de_ms=d[4], de_finish_ms=d[5],
                     jpeg_ms=d[5],           # (slot 5 was the DE's finish kernel until round 5; now the JPEG encodes' kernels)
+                    encode_ms=d[5],         # ... and the PNG encodes': the kernels of both device encoders
                     spec_launches=st[0], interp_launches=st[1])

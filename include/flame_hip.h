@@ -286,6 +286,32 @@ size_t fl_jpeg_bound(uint32_t w, uint32_t h);
 int fl_jpeg_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_jpeg(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap);
 
+/* PNG stills encoded on the device: 8-bit truecolour, colour type 2 (channels 3) or 6 (channels 4), not interlaced:
+ * the signature, IHDR, one IDAT per segment, IEND; no ancillary chunk.  The IDATs hold one zlib stream (header 78 01, deflate
+ * blocks, Adler-32).  Every row is filtered with Paeth (filter byte 4).  The filtered bytes are cut into segments of segment_bytes
+ * bytes (the library's choice; the last may be shorter), each coded with no reference before its own start as one block: dynamic
+ * Huffman (type 2) holding literals and matches of distance 1 and length 3..258, code lengths limited to 15 (7 for the code-length
+ * code), or stored (type 0) whenever the dynamic form would not be smaller.  Every segment but the last ends on a byte boundary
+ * (an empty stored block behind a dynamic one); only the last block has BFINAL set.  CRC-32s and Adler-32 are computed on the
+ * device.  The same pixels, size and channel count give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status,
+ * u32 segment_bytes, u32 0, and behind it the file.  status 0: the nbytes bytes behind the record are the file.  status 1: the
+ * file needs nbytes bytes and cap - 16 is less; nothing behind the record is valid.  No byte at or beyond cap is touched.
+ * A host_out from fl_host_alloc (any pinned memory) is written by the kernels themselves; other host memory receives an
+ * asynchronous copy of min(cap, fl_png_bound) bytes.
+ * fl_png_bound: the all-stored worst case — record, header, 17 bytes per segment (5 of the stored block, 12 of the IDAT), the
+ * zlib header and Adler-32, IEND; 0 for w or h of 0 or above 65535, channels other than 3 or 4, or a result beyond 2^32 - 1.
+ * fl_png_encode: src_dev = u8 [h][w][4] as FL_OUT_RGBA8 writes them (channels 3 leaves the alpha byte out of the file); queued on
+ * the current lane's stream.
+ * fl_output_png: fl_output(FL_OUT_RGBA8) into the lane's pixel buffer (same draws, same dither states afterwards), then the
+ * encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: channels other than 3 or 4, w or h of 0 or above 65535, a frame whose fl_png_bound is 0,
+ * a null src_dev, cap < 16 + FL_PNG_HEADER_BYTES, host_out and dev_out both null. */
+#define FL_PNG_HEADER_BYTES 33            /* signature + IHDR */
+size_t fl_png_bound(uint32_t w, uint32_t h, int channels);
+int fl_png_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_png(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -319,8 +345,8 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
 /* The same, split further: ms[0] iterate kernels, [1] tile accumulate, [2] flush, [3] all fl_filter calls,
  * [4] the DE proper — the eight direction kernels, the first normalising the accumulator, the last un-normalising it with a
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
- * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the JPEG encodes' kernels (fl_jpeg_encode,
- * fl_output_jpeg; 0 when none ran). */
+ * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of both device encoders (fl_jpeg_encode,
+ * fl_output_jpeg, fl_png_encode, fl_output_png; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
