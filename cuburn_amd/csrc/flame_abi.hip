@@ -106,10 +106,10 @@ struct Lane {
     DevBuf<unsigned char> d_outpix;                 // w*h*8 bytes
     DevBuf<uint32_t> d_de_tmax;                     // FL_FILT_DE: largest 16h per 64 x 16 tile [nbins / 256 + 64]
     DevBuf<float> d_de_sinv;                        // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
-    DevBuf<uint32_t> d_jpeg;                        // JPEG encode: coefficients, interval lengths and offsets (jpeg_layout)
-    DevBuf<unsigned char> d_jpeg_out;               // ... and the stream on its way to host memory that is not pinned
-    DevBuf<uint32_t> d_png;                         // PNG encode: filtered bytes, coded segments, lengths and offsets (png_layout)
-    DevBuf<unsigned char> d_png_out;                // ... and the file on its way to host memory that is not pinned
+    // The still encoders (encode_on) share one scratch and one staging buffer: their kernels are queued on `stream`, which orders one
+    // encode's use behind the other's, and a regrow first waits for the stream (quiesce).
+    DevBuf<uint32_t> d_enc;                         // the encoder's working set (jpeg_layout / png_layout)
+    DevBuf<unsigned char> d_enc_out;                // the file on its way to host memory that is not pinned
     size_t nbins() const { return d_front.cap; }
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
     // accumulate + flush of launch k run on `aux` while launch k+1 iterates on `stream` into the other set
@@ -144,7 +144,7 @@ struct Lane {
     void release()
     {
         release_fb();
-        d_params.release(); d_palette.release(); d_jpeg.release(); d_jpeg_out.release(); d_png.release(); d_png_out.release();
+        d_params.release(); d_palette.release(); d_enc.release(); d_enc_out.release();
         for (int k = 0; k < 2; ++k) { d_log[k].release(); d_dir[k].release(); }
         if (aux) hipStreamDestroy(aux);
         for (hipEvent_t *ev : events()) if (*ev) hipEventDestroy(*ev);
@@ -180,7 +180,7 @@ struct fl_ctx {
     hipEvent_t ev_begin_[kFrames] = {}, ev_end_[kFrames] = {};
     uint32_t frame_lane[kFrames] = {};
     uint32_t frame_seq = 0;                        // id of the current frame = frame_seq - 1
-    std::vector<EvPair> pool, iter_ev, accum_ev, flush_ev, filt_ev, de_ev, jpeg_ev;
+    std::vector<EvPair> pool, iter_ev, accum_ev, flush_ev, filt_ev, de_ev, enc_ev;
     size_t pool_used = 0;
     bool timing = true;
     static const uint32_t kDepEvents = 16;
@@ -942,28 +942,87 @@ size_t fl_output_bytes(uint32_t w, uint32_t h, int fmt)
     }
 }
 
+// What fl_output and the encoding outputs begin with: the front buffer, dithered and converted to `fmt`, in dst (null: the lane's
+// pixel buffer).
+static int convert_front(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, int fmt, void *dst)
+{
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
+    if (rc) return rc;
+    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
+    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
+    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, fmt, dst ? dst : (void *)ln.d_outpix.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
+    ln.out_rec = true;
+    return FL_OK;
+}
+
+// ... and end with, behind the encode and the copy to the host: the frame's end moves here (fl_frame_begin recorded it first)
+static int close_frame(fl_ctx *c, Lane &ln)
+{
+    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
+    return FL_OK;
+}
+
 int fl_output(fl_ctx *c, uint32_t w, uint32_t h, int fmt, void *host_out, uint64_t dev_out)
 {
     REQUIRE(c && fl_output_bytes(w, h, fmt) != 0, "bad argument");
     REQUIRE(fmt != FL_OUT_YUV420P10 || (w % 2 == 0 && h % 2 == 0), "4:2:0 needs even width and height");
     HIPCHK(hipSetDevice(c->device));
     Lane &ln = c->lane();
-    fl_dim d;
-    int rc = ensure_fb(ln, w, h, &d);
-    if (rc) return rc;
-    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
-    void *dst = dev_out ? (void *)(uintptr_t)dev_out : (void *)ln.d_outpix.p;
-    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
-    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, fmt, dst);
+    void *dev = (void *)(uintptr_t)dev_out;
+    if (int rc = convert_front(c, ln, w, h, fmt, dev)) return rc;
+    if (host_out) HIPCHK(hipMemcpyAsync(host_out, dev ? dev : (void *)ln.d_outpix.p, fl_output_bytes(w, h, fmt), hipMemcpyDeviceToHost, ln.stream));
+    return close_frame(c, ln);
+}
+
+// ---- stills encoded on the device (jpeg.hip, png.hip) ----
+// What both encoders ask of a call: a context, a frame whose sides fit the formats' 16 bits, room for the record and the
+// header (the placement kernel stores them whatever the status), and somewhere to put the file.
+static int check_encode(const fl_ctx *c, const char *enc, uint32_t w, uint32_t h, size_t header, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    REQUIRE(c, "null ctx");
+    const char *bad = !(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u) ? "width and height must be 1..65535"
+                      : cap < 16 + header                               ? "capacity below the record and the header"
+                      : !(host_out || dev_out)                          ? "no destination"
+                                                                        : nullptr;
+    if (!bad) return FL_OK;
+    return fail(FL_E_INVAL, (std::string(enc) + ": " + bad).c_str(), __FILE__, __LINE__);
+}
+
+// One encode, queued on the lane's stream (arguments checked).  Where the kernels store: the caller's device buffer; else the
+// caller's host buffer through its device address when it is pinned; else the lane's staging buffer, copied to the host afterwards.
+// bound: the encoder's fl_*_bound, so min(cap, bound) is what a fitting file can occupy; launch(scratch, dst) queues the kernels.
+extern "C++" template <class Launch>                            // (inside the extern "C" block a template needs its own linkage)
+static int encode_on(fl_ctx *c, Lane &ln, void *host_out, uint64_t dev_out, size_t cap, size_t bound, size_t scratch_words,
+                     const char *what_out, const char *what_scratch, Launch launch)
+{
+    unsigned char *dst = (unsigned char *)(uintptr_t)dev_out;
+    bool copy_back = host_out && dst;
+    const size_t dcap = std::min(cap, bound);
+    const auto quiesce = [&ln] { return ln.quiesce(false); };
+    if (!dst) {
+        hipPointerAttribute_t at = {};
+        const hipError_t e = hipPointerGetAttributes(&at, host_out);
+        if (e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) dst = (unsigned char *)at.devicePointer;
+        else {
+            (void)hipGetLastError();                            // (not a pointer the runtime knows: plain host memory)
+            if (int rc = ln.d_enc_out.reserve(dcap, what_out, quiesce)) return rc;
+            dst = ln.d_enc_out;
+            copy_back = true;
+        }
+    }
+    if (int rc = ln.d_enc.reserve(scratch_words, what_scratch, quiesce)) return rc;
+    EvPair *e = ev_begin_on(c, c->enc_ev, ln.stream);           // (slot 5 of fl_timings_detail: both device encoders)
+    launch(ln.d_enc.p, dst);
+    ev_end_on(e, ln.stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
-    ln.out_rec = true;
-    if (host_out) HIPCHK(hipMemcpyAsync(host_out, dst, fl_output_bytes(w, h, fmt), hipMemcpyDeviceToHost, ln.stream));
-    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
+    if (copy_back) HIPCHK(hipMemcpyAsync(host_out, dst, dcap, hipMemcpyDeviceToHost, ln.stream));
     return FL_OK;
 }
 
-// ---- JPEG stills (jpeg.hip) ----
+// ---- JPEG ----
 // No stream can be longer: a block codes its DC difference in at most 11 + 11 bits (the longest code of table K.4, category 11)
 // and each of its 63 AC coefficients in at most 16 + 10 (the longest code of K.5 / K.6, category 10; ZRL and EOB stand for
 // coefficients that then cost nothing): 22 + 63 * 26 = 1660 bits, 4980 per MCU of three blocks, 623 bytes once padded.  Every one
@@ -977,40 +1036,17 @@ size_t fl_jpeg_bound(uint32_t w, uint32_t h)
 
 static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, const void *host_out, uint64_t dev_out, size_t cap)
 {
-    REQUIRE(c, "null ctx");
+    if (int rc = check_encode(c, "jpeg", w, h, FL_JPEG_HEADER_BYTES, host_out, dev_out, cap)) return rc;
     REQUIRE(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
-    REQUIRE(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u, "jpeg: width and height must be 1..65535");
-    REQUIRE(cap >= 16 + FL_JPEG_HEADER_BYTES, "jpeg: capacity below the record and the header");
-    REQUIRE(host_out || dev_out, "jpeg: no destination");
     return FL_OK;
 }
 
-// The encode proper, queued on the lane's stream (arguments checked).  Where the kernels store: the caller's device buffer; else the
-// caller's host buffer through its device address when it is pinned; else a buffer of the lane's, copied to the host afterwards.
 static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality,
                           void *host_out, uint64_t dev_out, size_t cap)
 {
-    unsigned char *dst = (unsigned char *)(uintptr_t)dev_out;
-    bool copy_back = host_out && dst;
-    if (!dst) {
-        hipPointerAttribute_t at = {};
-        const hipError_t e = hipPointerGetAttributes(&at, host_out);
-        if (e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) dst = (unsigned char *)at.devicePointer;
-        else {
-            (void)hipGetLastError();                            // (not a pointer the runtime knows: plain host memory)
-            if (int rc = ln.d_jpeg_out.reserve(std::min(cap, fl_jpeg_bound(w, h)), "jpeg stream", [&ln] { return ln.quiesce(false); })) return rc;
-            dst = ln.d_jpeg_out;
-            copy_back = true;
-        }
-    }
-    const size_t dcap = std::min(cap, fl_jpeg_bound(w, h));    // (what a fitting stream can occupy)
-    if (int rc = ln.d_jpeg.reserve(jpeg_layout(w, h, c->jpeg_ri).words, "jpeg scratch", [&ln] { return ln.quiesce(false); })) return rc;
-    EvPair *e = ev_begin_on(c, c->jpeg_ev, ln.stream);
-    launch_jpeg_encode(ln.stream, src, w, h, quality, c->jpeg_ri, ln.d_jpeg, dst, cap);
-    ev_end_on(e, ln.stream);
-    HIPCHK(hipGetLastError());
-    if (copy_back) HIPCHK(hipMemcpyAsync(host_out, dst, dcap, hipMemcpyDeviceToHost, ln.stream));
-    return FL_OK;
+    const uint32_t ri = c->jpeg_ri;
+    return encode_on(c, ln, host_out, dev_out, cap, fl_jpeg_bound(w, h), jpeg_layout(w, h, ri).words, "jpeg stream", "jpeg scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_jpeg_encode(st, src, w, h, quality, ri, scratch, dst, cap); });
 }
 
 int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap)
@@ -1026,21 +1062,12 @@ int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_ou
     if (int rc = check_jpeg(c, w, h, quality, host_out, dev_out, cap)) return rc;
     HIPCHK(hipSetDevice(c->device));
     Lane &ln = c->lane();
-    fl_dim d;
-    int rc = ensure_fb(ln, w, h, &d);
-    if (rc) return rc;
-    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
-    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
-    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, FL_OUT_YUV444P, ln.d_outpix.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
-    ln.out_rec = true;
-    if ((rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, host_out, dev_out, cap))) return rc;
-    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
-    return FL_OK;
+    if (int rc = convert_front(c, ln, w, h, FL_OUT_YUV444P, nullptr)) return rc;
+    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
 }
 
-// ---- PNG stills (png.hip) ----
+// ---- PNG ----
 // No file can be longer: every segment stored is its bytes and 5 of block header, in an IDAT of 12; the first IDAT also holds the
 // 2 bytes of the zlib header and the last the Adler-32; IEND is 12.  A dynamic segment is only chosen where it is smaller.
 size_t fl_png_bound(uint32_t w, uint32_t h, int channels)
@@ -1053,41 +1080,18 @@ size_t fl_png_bound(uint32_t w, uint32_t h, int channels)
 
 static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap)
 {
-    REQUIRE(c, "null ctx");
+    if (int rc = check_encode(c, "png", w, h, FL_PNG_HEADER_BYTES, host_out, dev_out, cap)) return rc;
     REQUIRE(channels == 3 || channels == 4, "png: channels must be 3 or 4");
-    REQUIRE(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u, "png: width and height must be 1..65535");
     REQUIRE(fl_png_bound(w, h, channels) != 0, "png: the file could pass 2^32 - 1 bytes");
-    REQUIRE(cap >= 16 + FL_PNG_HEADER_BYTES, "png: capacity below the record and the header");
-    REQUIRE(host_out || dev_out, "png: no destination");
     return FL_OK;
 }
 
-// The encode proper, queued on the lane's stream (arguments checked); the destination is chosen as jpeg_encode_on chooses it.
 static int png_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels,
                          void *host_out, uint64_t dev_out, size_t cap)
 {
-    unsigned char *dst = (unsigned char *)(uintptr_t)dev_out;
-    bool copy_back = host_out && dst;
-    const size_t dcap = std::min(cap, fl_png_bound(w, h, channels));      // (what a fitting file can occupy)
-    if (!dst) {
-        hipPointerAttribute_t at = {};
-        const hipError_t e = hipPointerGetAttributes(&at, host_out);
-        if (e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) dst = (unsigned char *)at.devicePointer;
-        else {
-            (void)hipGetLastError();                            // (not a pointer the runtime knows: plain host memory)
-            if (int rc = ln.d_png_out.reserve(dcap, "png file", [&ln] { return ln.quiesce(false); })) return rc;
-            dst = ln.d_png_out;
-            copy_back = true;
-        }
-    }
     const uint32_t seg = png_segment_bytes();
-    if (int rc = ln.d_png.reserve(png_layout(w, h, channels, seg).words, "png scratch", [&ln] { return ln.quiesce(false); })) return rc;
-    EvPair *e = ev_begin_on(c, c->jpeg_ev, ln.stream);          // (slot 5 of fl_timings_detail: both device encoders)
-    launch_png_encode(ln.stream, src, w, h, channels, seg, ln.d_png, dst, cap);
-    ev_end_on(e, ln.stream);
-    HIPCHK(hipGetLastError());
-    if (copy_back) HIPCHK(hipMemcpyAsync(host_out, dst, dcap, hipMemcpyDeviceToHost, ln.stream));
-    return FL_OK;
+    return encode_on(c, ln, host_out, dev_out, cap, fl_png_bound(w, h, channels), png_layout(w, h, channels, seg).words, "png file", "png scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_png_encode(st, src, w, h, channels, seg, scratch, dst, cap); });
 }
 
 int fl_png_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
@@ -1103,18 +1107,9 @@ int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_ou
     if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
     HIPCHK(hipSetDevice(c->device));
     Lane &ln = c->lane();
-    fl_dim d;
-    int rc = ensure_fb(ln, w, h, &d);
-    if (rc) return rc;
-    if ((rc = flush_pending(c, ln))) return rc;             // deferred ends of the filter chain
-    if ((rc = wait_other(c, 2))) return rc;                 // the dither RNG states are shared between lanes
-    launch_f32_to_rgba(ln.stream, d, ln.d_front, c->rng_out(), FL_NOUT, FL_OUT_RGBA8, ln.d_outpix.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ln.ev_out_done, ln.stream));
-    ln.out_rec = true;
-    if ((rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap))) return rc;
-    if (c->frame_seq) HIPCHK(hipEventRecord(c->ev_end_[(c->frame_seq - 1) % fl_ctx::kFrames], ln.stream));
-    return FL_OK;
+    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
 }
 
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
@@ -1182,7 +1177,7 @@ int fl_timings_reset(fl_ctx *c)
 {
     REQUIRE(c, "null ctx");
     sync_all(c);
-    c->iter_ev.clear(); c->accum_ev.clear(); c->flush_ev.clear(); c->filt_ev.clear(); c->de_ev.clear(); c->jpeg_ev.clear(); c->pool_used = 0;
+    c->iter_ev.clear(); c->accum_ev.clear(); c->flush_ev.clear(); c->filt_ev.clear(); c->de_ev.clear(); c->enc_ev.clear(); c->pool_used = 0;
     c->n_spec_launch = c->n_interp_launch = 0;
     return FL_OK;
 }
@@ -1192,7 +1187,7 @@ int fl_timings_detail(fl_ctx *c, float ms[6])
     REQUIRE(c && ms, "null argument");
     sync_all(c);
     ms[0] = sum_ms(c->iter_ev); ms[1] = sum_ms(c->accum_ev); ms[2] = sum_ms(c->flush_ev);
-    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->jpeg_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG and PNG encodes
+    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->enc_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG and PNG encodes
     return FL_OK;
 }
 

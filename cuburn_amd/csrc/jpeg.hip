@@ -9,6 +9,7 @@
 // The intervals are byte aligned and independent (the DC predictor restarts), which is what makes the scan parallel; nothing is
 // stored at or beyond `cap`: the last pass stores nothing when the stream does not fit.
 #include "kernels.h"
+#include "encode_device.h"
 
 namespace {
 
@@ -180,13 +181,6 @@ struct Bits {                         // a lane's writer into the interval's bit
     __device__ __forceinline__ void flush() { if (n) atomicOr(&words[w], (uint32_t)(acc >> 32)); }
 };
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
-    return v;
-}
-
 // One workgroup of one wave per interval of `ri` MCUs (3 * ri <= 64: a lane per block).  WRITE = false: lens[interval] = bytes of the
 // interval, stuffing and the RSTm / EOI marker behind it included.  WRITE = true: the bytes go to out + base + offs[interval],
 // unless info[2] (the status the scan left) says that the stream does not fit.
@@ -287,17 +281,7 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
         s_out[L - 1u] = it + 1u == nint ? 0xd9 : (unsigned char)(0xd0u + (it & 7u));      // EOI behind the last interval, RSTm behind the others
     }
     __syncthreads();
-    // to the stream: bytes up to the first 4-byte boundary of the destination, dwords, and the bytes that are left
-    unsigned char *dst = out + (size_t)base + offs[it];
-    const uint32_t head = min(L, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u)), nmid = (L - head) >> 2, tail0 = head + 4u * nmid;
-    if (lane < head) dst[lane] = s_out[lane];
-    const uint32_t *s32 = (const uint32_t *)s_out;
-    for (uint32_t m = lane; m < nmid; m += 64) {
-        const uint32_t so = head + 4u * m, sh = (so & 3u) * 8u;
-        const uint32_t a = s32[so >> 2], c = s32[(so >> 2) + 1u];
-        *(uint32_t *)(dst + so) = sh ? a >> sh | c << (32u - sh) : a;
-    }
-    if (lane < L - tail0) dst[tail0 + lane] = s_out[tail0 + lane];
+    store_bytes<64>(out + (size_t)base + offs[it], s_bits + nbw, L, lane);      // (s_out, with the 8 bytes of padding behind it)
 }
 
 // ---- where the intervals go ------------------------------------------------------------------------------------------
@@ -308,25 +292,14 @@ k_jpeg_scan(const uint32_t *__restrict__ lens, uint32_t nint, u64 *__restrict__ 
 {
     __shared__ u64 s_sum[1024];
     const uint32_t t = threadIdx.x, per = (nint + 1023u) / 1024u, lo = min(t * per, nint), hi = min(lo + per, nint);
-    u64 mine = 0;
+    u64 mine = 0, total;
     for (uint32_t i = lo; i < hi; ++i) mine += lens[i];
-    s_sum[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const u64 o = t >= d ? s_sum[t - d] : 0;
-        __syncthreads();
-        s_sum[t] += o;
-        __syncthreads();
-    }
-    u64 run = s_sum[t] - mine;
+    u64 run = block_excl_scan_1024(s_sum, mine, t, total);
     for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += lens[i]; }
-    const u64 need = (u64)FL_JPEG_HEADER_BYTES + s_sum[1023];              // bytes behind the record
+    const u64 need = (u64)FL_JPEG_HEADER_BYTES + total;                    // bytes behind the record
     const uint32_t status = need > cap - 16u ? 1u : 0u;
     if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; }
-    if (t < 16) {
-        const uint32_t rec[4] = {need > 0xffffffffull ? 0xffffffffu : (uint32_t)need, status, ri, 0u};
-        out[t] = (unsigned char)(rec[t >> 2] >> (8u * (t & 3u)));
-    }
+    write_record(out, need, status, ri, t);
     if (t < FL_JPEG_HEADER_BYTES) out[16u + t] = hdr.b[t];                 // (cap >= 16 + the header: the callers checked)
 }
 

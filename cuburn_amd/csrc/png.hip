@@ -9,6 +9,7 @@
 // The segments are byte aligned (an empty stored block behind a dynamic one) and share no history, which is what makes them parallel.
 // Nothing is stored at or beyond `cap`: the gather stores nothing when the file does not fit.
 #include "kernels.h"
+#include "encode_device.h"
 #include <cstdlib>
 
 namespace {
@@ -20,13 +21,6 @@ constexpr uint32_t kSymPad = 288u;                            // kLitSyms, round
 __device__ const unsigned char g_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};      // RFC 1951 3.2.7
 
 struct PngHeaderArg { unsigned char b[FL_PNG_HEADER_BYTES]; };
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
-    return v;
-}
 
 // ---- the filter ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t paeth(int a, int b, int c)
@@ -417,19 +411,11 @@ k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, 
 {
     __shared__ u64 s_sum[1024];
     const uint32_t t = threadIdx.x, per = (nseg + 1023u) / 1024u, lo = min(t * per, nseg), hi = min(lo + per, nseg);
-    u64 mine = 0;
+    u64 mine = 0, total;
     for (uint32_t i = lo; i < hi; ++i) mine += 12u + idat_data_bytes(lens[i], i, nseg);
-    s_sum[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const u64 o = t >= d ? s_sum[t - d] : 0;
-        __syncthreads();
-        s_sum[t] += o;
-        __syncthreads();
-    }
-    u64 run = (u64)FL_PNG_HEADER_BYTES + s_sum[t] - mine;
+    u64 run = (u64)FL_PNG_HEADER_BYTES + block_excl_scan_1024(s_sum, mine, t, total);
     for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += 12u + idat_data_bytes(lens[i], i, nseg); }
-    const u64 need = (u64)FL_PNG_HEADER_BYTES + s_sum[1023] + 12u;         // bytes behind the record, IEND included
+    const u64 need = (u64)FL_PNG_HEADER_BYTES + total + 12u;               // bytes behind the record, IEND included
     const uint32_t status = need > cap - 16u ? 1u : 0u;
     if (t == 0) {
         // Adler-32 of a concatenation: a = a1 + a2 - 1, b = b1 + b2 + len2 * (a1 - 1), mod 65521
@@ -441,10 +427,7 @@ k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, 
         }
         info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = B << 16 | A;
     }
-    if (t < 16) {
-        const uint32_t rec[4] = {need > 0xffffffffull ? 0xffffffffu : (uint32_t)need, status, seg, 0u};
-        out[t] = (unsigned char)(rec[t >> 2] >> (8u * (t & 3u)));
-    }
+    write_record(out, need, status, seg, t);
     if (t < FL_PNG_HEADER_BYTES) out[16u + t] = hdr.b[t];                  // (cap >= 16 + the header: the callers checked)
 }
 
@@ -522,17 +505,7 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     __syncthreads();
     if (t < 4u) s_chunk[8u + dlen + t] = (unsigned char)(~s_crc >> (24u - 8u * t));
     __syncthreads();
-    // to the file: bytes up to the first 4-byte boundary of the destination, dwords, and the bytes that are left
-    const uint32_t N = 12u + dlen + (last ? 12u : 0u);
-    unsigned char *dst = out + 16u + offs[it];
-    const uint32_t head = min(N, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u)), nmid = (N - head) >> 2, tail0 = head + 4u * nmid;
-    if (t < head) dst[t] = s_chunk[t];
-    for (uint32_t m = t; m < nmid; m += 256u) {
-        const uint32_t so = head + 4u * m, sh = (so & 3u) * 8u;
-        const uint32_t a = s_mem[so >> 2], c = s_mem[(so >> 2) + 1u];
-        *(uint32_t *)(dst + so) = sh ? a >> sh | c << (32u - sh) : a;
-    }
-    if (t < N - tail0) dst[tail0 + t] = s_chunk[tail0 + t];
+    store_bytes<256>(out + 16u + offs[it], s_mem, 12u + dlen + (last ? 12u : 0u), t);      // (s_chunk, with the 2 words of padding behind it)
 }
 
 uint32_t crc32_host(const unsigned char *p, size_t n)

@@ -132,11 +132,34 @@ class PILOutput(Output):
         return {'.' + self.type: self._save(buf)}, []
 
 
-class DeviceJPEGOutput(Output):
-    """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100}``): the frame leaves the
-    GPU as a finished baseline 4:4:4 file (include/flame_hip.h, fl_output_jpeg).  The host frame is a byte buffer: a 16-byte
-    record (u32 nbytes, status, restart interval, 0), then the file."""
-    suffix = '.jpg'
+class DeviceEncodedOutput(Output):
+    """Stills encoded on the device: the frame leaves the GPU as a finished file.  The host frame is a byte buffer: a 16-byte
+    record (u32 nbytes, status, a parameter of the encoder, 0), then the file.  A subclass names the library's entry point
+    (``entry``), gives its one argument beyond the frame and the destination (``argument``) and the buffer's size
+    (``capacity``), and says what the file is (``suffix``, ``noun``)."""
+
+    def shape(self, dim):
+        return (self.capacity(dim),)
+
+    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
+        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
+        _lib.check(getattr(_lib.load(), self.entry)(fb.ctx, dim.w, dim.h, self.argument(), h_out.ctypes.data if host else None,
+                                                    int(dev_out), self.capacity(dim)))
+        return h_out
+
+    def encode(self, buf):
+        if buf is None:
+            return {}, []
+        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
+        if status:
+            raise _lib.FlameError('the %s needs %d bytes and the frame buffer holds %d' % (self.noun, nbytes, buf.size - 16))
+        return {self.suffix: io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
+
+
+class DeviceJPEGOutput(DeviceEncodedOutput):
+    """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100}``): a baseline 4:4:4
+    file (include/flame_hip.h, fl_output_jpeg).  The record's parameter is the restart interval."""
+    suffix, entry, noun = '.jpg', 'fl_output_jpeg', 'JPEG stream'
 
     def __init__(self, quality=100, alpha=False):
         if alpha:
@@ -145,61 +168,33 @@ class DeviceJPEGOutput(Output):
             raise ValueError('output.quality must be an integer in 1..100')
         self.quality, self.alpha = quality, False
 
+    def argument(self):
+        return self.quality
+
     @staticmethod
     def capacity(dim):
         """Record, header and twice the raw planes: a stream that needs more (noise at quality 100 takes 0.65 of raw) is
         reported by ``encode`` with the size it needs."""
         return 16 + _lib.JPEG_HEADER_BYTES + 2 * 3 * dim.w * dim.h
 
-    def shape(self, dim):
-        return (self.capacity(dim),)
 
-    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
-        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
-        _lib.check(_lib.load().fl_output_jpeg(fb.ctx, dim.w, dim.h, self.quality, h_out.ctypes.data if host else None,
-                                              int(dev_out), self.capacity(dim)))
-        return h_out
-
-    def encode(self, buf):
-        if buf is None:
-            return {}, []
-        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
-        if status:
-            raise _lib.FlameError('the JPEG stream needs %d bytes and the frame buffer holds %d' % (nbytes, buf.size - 16))
-        return {'.jpg': io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
-
-
-class DevicePNGOutput(Output):
-    """PNG stills encoded on the device (``output: {"type": "png", "encoder": "device", "alpha": bool}``): the frame leaves the GPU
-    as a finished 8-bit truecolour file, Paeth-filtered and deflated in independent segments (include/flame_hip.h,
-    fl_output_png).  The host frame is a byte buffer: a 16-byte record (u32 nbytes, status, segment bytes, 0), then the file."""
-    suffix = '.png'
+class DevicePNGOutput(DeviceEncodedOutput):
+    """PNG stills encoded on the device (``output: {"type": "png", "encoder": "device", "alpha": bool}``): an 8-bit truecolour
+    file, Paeth-filtered and deflated in independent segments (include/flame_hip.h, fl_output_png).  The record's parameter is
+    the segment's bytes."""
+    suffix, entry, noun = '.png', 'fl_output_png', 'PNG file'
 
     def __init__(self, alpha=False):
         if not isinstance(alpha, bool):
             raise ValueError('output.alpha must be true or false')
         self.alpha, self.channels = alpha, 4 if alpha else 3
 
+    def argument(self):
+        return self.channels
+
     def capacity(self, dim):
         """The library's bound: no frame needs more (noise is stored, at 17 bytes per segment above its own size)."""
         return int(_lib.load().fl_png_bound(dim.w, dim.h, self.channels))
-
-    def shape(self, dim):
-        return (self.capacity(dim),)
-
-    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
-        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
-        _lib.check(_lib.load().fl_output_png(fb.ctx, dim.w, dim.h, self.channels, h_out.ctypes.data if host else None,
-                                             int(dev_out), self.capacity(dim)))
-        return h_out
-
-    def encode(self, buf):
-        if buf is None:
-            return {}, []
-        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
-        if status:
-            raise _lib.FlameError('the PNG file needs %d bytes and the frame buffer holds %d' % (nbytes, buf.size - 16))
-        return {'.png': io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
 
 
 class PNGOutput(PILOutput):

@@ -23,14 +23,14 @@ import numpy as np
 import pytest
 
 from cuburn_amd import _lib, configs, output, profile, render
+import encoder_harness as H
+from encoder_harness import SENTINEL, SLACK, record, upload
 import jpeg_cases as JC
 import jpeg_model as J
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -8
-SENTINEL = 0xA5
-SLACK = 4096                  # sentinel bytes the tests keep behind a capacity
 
 
 @pytest.fixture(scope='module')
@@ -41,33 +41,12 @@ def mgr(built):
     m.fb.free()
 
 
-def upload(mgr, planes):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(planes)).to('cuda:%d' % mgr.fb.device)
-    torch.cuda.synchronize(mgr.fb.device)
-    return t
-
-
-def record(buf):
-    nbytes, status, ri, zero = (int(v) for v in np.frombuffer(buf[:16], '<u4'))
-    assert zero == 0
-    return nbytes, status, ri
-
-
 def encode(mgr, planes, quality, cap=None, buf=None):
     """fl_jpeg_encode into pinned memory (or `buf`) pre-filled with the sentinel; returns (buffer, cap)."""
-    lib = _lib.load()
     _, h, w = planes.shape
     if cap is None:
-        cap = lib.fl_jpeg_bound(w, h)
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    t = upload(mgr, planes)
-    _lib.check(lib.fl_jpeg_encode(mgr.fb.ctx, w, h, t.data_ptr(), quality, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert (buf[cap:] == SENTINEL).all(), 'bytes at or beyond cap were written'
-    return buf, cap
+        cap = _lib.load().fl_jpeg_bound(w, h)
+    return H.encode(mgr, 'fl_jpeg_encode', planes, w, h, quality, cap, buf)       # (checks the sentinel at and beyond cap)
 
 
 def stream_of(buf):
@@ -184,15 +163,16 @@ def test_device_destination(mgr, device_ri):
     _, h, w = planes.shape
     cap = 16 + len(data) + 7
     t = upload(mgr, planes)
-    out = torch.full((cap + SLACK,), SENTINEL, dtype=torch.uint8, device=t.device)
-    torch.cuda.synchronize(mgr.fb.device)
-    host = mgr.fb._pinned((cap + SLACK,), 'u1')
-    host[:] = SENTINEL
-    _lib.check(lib.fl_jpeg_encode(mgr.fb.ctx, w, h, t.data_ptr(), quality, host.ctypes.data, out.data_ptr() + 1, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    dev = out.cpu().numpy()
-    assert dev[0] == SENTINEL and (dev[1 + cap:] == SENTINEL).all() and (host[cap:] == SENTINEL).all()
-    assert stream_of(dev[1:]) == data and stream_of(host) == data
+    for odd in (1, 2, 3):
+        out = torch.full((cap + SLACK,), SENTINEL, dtype=torch.uint8, device=t.device)
+        torch.cuda.synchronize(mgr.fb.device)
+        host = mgr.fb._pinned((cap + SLACK,), 'u1')
+        host[:] = SENTINEL
+        _lib.check(lib.fl_jpeg_encode(mgr.fb.ctx, w, h, t.data_ptr(), quality, host.ctypes.data, out.data_ptr() + odd, cap))
+        _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
+        dev = out.cpu().numpy()
+        assert (dev[:odd] == SENTINEL).all() and (dev[odd + cap:] == SENTINEL).all() and (host[cap:] == SENTINEL).all()
+        assert stream_of(dev[odd:]) == data and stream_of(host) == data
 
 
 def test_whole_path(mgr, device_ri):

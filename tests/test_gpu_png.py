@@ -22,13 +22,12 @@ import numpy as np
 import pytest
 
 from cuburn_amd import _lib, configs, output, profile, render
+import encoder_harness as H
+from encoder_harness import SENTINEL, SLACK, record, upload
 import png_cases as PC
 import png_model as P
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xA5
-SLACK = 4096                  # sentinel bytes the tests keep behind a capacity
 
 
 @pytest.fixture(scope='module')
@@ -39,33 +38,12 @@ def mgr(built):
     m.fb.free()
 
 
-def upload(mgr, arr):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(arr)).to('cuda:%d' % mgr.fb.device)
-    torch.cuda.synchronize(mgr.fb.device)
-    return t
-
-
-def record(buf):
-    nbytes, status, seg, zero = (int(v) for v in np.frombuffer(buf[:16], '<u4'))
-    assert zero == 0
-    return nbytes, status, seg
-
-
 def encode(mgr, rgba, ch, cap=None, buf=None):
     """fl_png_encode into pinned memory (or `buf`) pre-filled with the sentinel; returns (buffer, cap)."""
-    lib = _lib.load()
     h, w, _ = rgba.shape
     if cap is None:
-        cap = lib.fl_png_bound(w, h, ch)
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    t = upload(mgr, rgba)
-    _lib.check(lib.fl_png_encode(mgr.fb.ctx, w, h, t.data_ptr(), ch, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert (buf[cap:] == SENTINEL).all(), 'bytes at or beyond cap were written'
-    return buf, cap
+        cap = _lib.load().fl_png_bound(w, h, ch)
+    return H.encode(mgr, 'fl_png_encode', rgba, w, h, ch, cap, buf)                # (checks the sentinel at and beyond cap)
 
 
 def file_of(buf):
