@@ -190,6 +190,7 @@ struct fl_ctx {
     bool env_bin_wide = false, env_no_intra = false;
     bool use_rtc = true;                    // FLAME_RTC=0: always the interpreter kernel
     uint32_t jpeg_ri = FL_JPEG_RI;          // FLAME_JPEG_RI (1..21): MCUs per JPEG restart interval
+    uint32_t jpeg_ri_420 = FL_JPEG_RI_420;  // ... in 4:2:0, where a value above 10 means 10
     uint32_t n_spec_launch = 0, n_interp_launch = 0;      // iterate launches by kernel since fl_timings_reset (fl_launch_stats)
     BinLayout layout(const fl_dim &d) const { return bin_layout(d, nw, bin_rounds, env_bin_wide); }
 };
@@ -319,7 +320,7 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
     if (const char *e = getenv("FLAME_BIN_PARTS")) { int v = atoi(e); if (v >= 1 && v <= 64) c->bin_parts = (uint32_t)v; }
     c->env_bin_wide = env_on("FLAME_BIN_WIDE");
     if (const char *e = getenv("FLAME_RTC")) c->use_rtc = strcmp(e, "0") != 0;
-    if (const char *e = getenv("FLAME_JPEG_RI")) { const int v = atoi(e); if (v >= 1 && v <= 21) c->jpeg_ri = (uint32_t)v; }
+    if (const char *e = getenv("FLAME_JPEG_RI")) { const int v = atoi(e); if (v >= 1 && v <= 21) { c->jpeg_ri = (uint32_t)v; c->jpeg_ri_420 = std::min((uint32_t)v, FL_JPEG_RI_420_MAX); } }
     c->env_no_intra = env_on("FLAME_NO_INTRA_OVERLAP");      // launches of a frame strictly in series on one stream
     if (const char *e = getenv("FLAME_LAUNCH_ROUNDS")) { int v = atoi(e); if (v >= 16 && v <= 4096) c->launch_rounds = (uint32_t)(v / 16 * 16); }
     if (stream) { c->lanes[0].stream = (hipStream_t)stream; c->own_stream = false; c->nlanes = 1; }   // caller's stream: one lane
@@ -1028,43 +1029,58 @@ static int encode_on(fl_ctx *c, Lane &ln, void *host_out, uint64_t dev_out, size
 // coefficients that then cost nothing): 22 + 63 * 26 = 1660 bits, 4980 per MCU of three blocks, 623 bytes once padded.  Every one
 // of those bytes can be 0xFF and take a stuffed zero with it, and the shortest restart interval — one MCU — puts a two-byte
 // marker (RSTm, or EOI) behind each: 2 * 623 + 2 = 1248 bytes per MCU.  Longer intervals pad and mark less often.
-size_t fl_jpeg_bound(uint32_t w, uint32_t h)
+// 4:2:0 by the same rule: an MCU of six blocks is 9960 bits, 1245 bytes, 2 * 1245 + 2 = 2492.
+size_t fl_jpeg_bound_s(uint32_t w, uint32_t h, int sampling)
 {
-    if (!w || !h || w > 65535u || h > 65535u) return 0;
+    if (!w || !h || w > 65535u || h > 65535u || (sampling != FL_JPEG_444 && sampling != FL_JPEG_420)) return 0;
+    if (sampling == FL_JPEG_420) return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 15u) / 16u) * ((h + 15u) / 16u) * 2492u;
     return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 1248u;
 }
 
-static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, const void *host_out, uint64_t dev_out, size_t cap)
+size_t fl_jpeg_bound(uint32_t w, uint32_t h) { return fl_jpeg_bound_s(w, h, FL_JPEG_444); }
+
+static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, const void *host_out, uint64_t dev_out, size_t cap)
 {
     if (int rc = check_encode(c, "jpeg", w, h, FL_JPEG_HEADER_BYTES, host_out, dev_out, cap)) return rc;
     REQUIRE(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
+    REQUIRE(sampling == FL_JPEG_444 || sampling == FL_JPEG_420, "jpeg: sampling must be FL_JPEG_444 or FL_JPEG_420");
     return FL_OK;
 }
 
-static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality,
+static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality, int sampling,
                           void *host_out, uint64_t dev_out, size_t cap)
 {
-    const uint32_t ri = c->jpeg_ri;
-    return encode_on(c, ln, host_out, dev_out, cap, fl_jpeg_bound(w, h), jpeg_layout(w, h, ri).words, "jpeg stream", "jpeg scratch",
-                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_jpeg_encode(st, src, w, h, quality, ri, scratch, dst, cap); });
+    const uint32_t ri = sampling == FL_JPEG_420 ? c->jpeg_ri_420 : c->jpeg_ri;
+    return encode_on(c, ln, host_out, dev_out, cap, fl_jpeg_bound_s(w, h, sampling), jpeg_layout(w, h, ri, sampling).words, "jpeg stream", "jpeg scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_jpeg_encode(st, src, w, h, quality, ri, sampling, scratch, dst, cap); });
+}
+
+int fl_jpeg_encode_s(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_jpeg(c, w, h, quality, sampling, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "jpeg: null source planes");
+    HIPCHK(hipSetDevice(c->device));
+    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, sampling, host_out, dev_out, cap);
 }
 
 int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "jpeg: null source planes");
+    return fl_jpeg_encode_s(c, w, h, src_dev, quality, FL_JPEG_444, host_out, dev_out, cap);
+}
+
+int fl_output_jpeg_s(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_jpeg(c, w, h, quality, sampling, host_out, dev_out, cap)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, host_out, dev_out, cap);
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, FL_OUT_YUV444P, nullptr)) return rc;
+    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, sampling, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
 }
 
 int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, FL_OUT_YUV444P, nullptr)) return rc;
-    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return fl_output_jpeg_s(c, w, h, quality, FL_JPEG_444, host_out, dev_out, cap);
 }
 
 // ---- PNG ----

@@ -1,11 +1,12 @@
-// jpeg.hip — baseline JPEG (SOF0, 8 bit, 4:4:4, one interleaved scan, restart intervals) from u8 planar Y/Cb/Cr on the device.
-// DESIGN.md §4.8.  Four launches per frame, no host wait between them:
+// jpeg.hip — baseline JPEG (SOF0, 8 bit, 4:4:4 or 4:2:0, one interleaved scan, restart intervals) from u8 planar Y/Cb/Cr on the
+// device.  DESIGN.md §4.8 (4:4:4) and §4.10 (4:2:0: the same kernels, instantiated for an MCU of six blocks).  Four launches per
+// frame, no host wait between them:
 //   k_jpeg_dct          one lane per 8x8 block: load (edge replicated), level shift, float32 DCT, quantise, zigzag -> int16, and the
 //                       bit length of the block's AC symbols
-//   k_jpeg_entropy<0>   one wave per restart interval: DC differences, prefix sum of the blocks' bit lengths, bits packed in LDS,
+//   k_jpeg_entropy<S,0> one wave per restart interval: DC differences, prefix sum of the blocks' bit lengths, bits packed in LDS,
 //                       0xFF counted -> the interval's byte length (stuffing and marker included)
 //   k_jpeg_scan         one workgroup: exclusive scan of the intervals' byte lengths, the 16-byte record and the header
-//   k_jpeg_entropy<1>   the same packing again, stuffed in LDS, stored at the interval's place with dword stores
+//   k_jpeg_entropy<S,1> the same packing again, stuffed in LDS, stored at the interval's place with dword stores
 // The intervals are byte aligned and independent (the DC predictor restarts), which is what makes the scan parallel; nothing is
 // stored at or beyond `cap`: the last pass stores nothing when the stream does not fit.
 #include "kernels.h"
@@ -94,15 +95,28 @@ struct JpegHeaderArg { unsigned char b[640]; };           // FL_JPEG_HEADER_BYTE
 
 __device__ __forceinline__ int nbits_of(int v) { const int a = v < 0 ? -v : v; return 32 - __clz(a); }      // magnitude category (0 for 0)
 
+// The sampling is a compile-time parameter S of every kernel (FL_JPEG_444 / FL_JPEG_420).  An MCU holds NB blocks, `slot` counting
+// them in the order of the scan: 4:4:4 Y, Cb, Cr of 8 x 8 pixels; 4:2:0 Y00, Y01, Y10, Y11, Cb, Cr of 16 x 16 pixels.
+template <int S> struct Mcu {
+    static constexpr uint32_t NB = S ? 6u : 3u;               // blocks
+    static constexpr uint32_t BITS = NB * 1660u;              // worst case of a block: DC 11 + 11 bits, 63 AC of 16 + 10 bits = 1660 bits
+    __host__ __device__ static constexpr uint32_t comp(uint32_t slot) { return S ? (slot < 4u ? 0u : slot - 3u) : slot; }
+    // how many blocks back the component's previous block lies: 4:2:0 Y runs through the MCU's four blocks and on into the next
+    // MCU (Y00 follows the Y11 three blocks before it), Cb and Cr run MCU to MCU
+    __host__ __device__ static constexpr uint32_t back(uint32_t slot) { return S ? (slot == 0u ? 3u : slot < 4u ? 1u : 6u) : 3u; }
+};
+
 // ---- load + DCT + quantise -------------------------------------------------------------------------------------------
-// grid (ceil(nmcu / 256), 3): blockIdx.y is the component, so the quantiser table is wave-uniform.  coef[(3 * mcu + comp) * 64 + k]
-// in zigzag order (the order of the scan); acbits[3 * mcu + comp] = bits of the block's AC symbols.
+// grid (ceil(nmcu / 256), NB): blockIdx.y is the block's slot in the MCU, so the quantiser table is wave-uniform.
+// coef[(NB * mcu + slot) * 64 + k] in zigzag order (the order of the scan); acbits[NB * mcu + slot] = bits of the block's AC symbols.
+// 4:2:0 chroma: a sample is (a + b + c + d + 2) >> 2 over the 2 x 2 full-resolution samples, their coordinates clamped first.
+template <int S>
 __global__ void __launch_bounds__(256)
 k_jpeg_dct(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint32_t mw, uint32_t nmcu, JpegQuant Q,
            short *__restrict__ coef, unsigned short *__restrict__ acbits)
 {
     __shared__ unsigned char s_len[256];
-    const uint32_t comp = blockIdx.y;
+    const uint32_t slot = blockIdx.y, comp = Mcu<S>::comp(slot);
     s_len[threadIdx.x] = (unsigned char)(g_huff.e[(comp ? kAcChr : kAcLum) + threadIdx.x] >> 16);
     __syncthreads();
     const uint32_t mcu = blockIdx.x * 256u + threadIdx.x;
@@ -110,12 +124,26 @@ k_jpeg_dct(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint32
     const uint32_t bx = mcu % mw, by = mcu / mw;
     const unsigned char *plane = src + (size_t)comp * w * h;
     float f[64];
+    if (S && comp) {
 #pragma unroll
-    for (int y = 0; y < 8; ++y) {
-        const uint32_t yy = min(by * 8u + y, h - 1u);         // the last row / column is replicated into partial blocks
-        const unsigned char *row = plane + (size_t)yy * w;
+        for (int y = 0; y < 8; ++y) {
+            const unsigned char *r0 = plane + (size_t)min(by * 16u + 2u * y, h - 1u) * w;
+            const unsigned char *r1 = plane + (size_t)min(by * 16u + 2u * y + 1u, h - 1u) * w;
 #pragma unroll
-        for (int x = 0; x < 8; ++x) f[y * 8 + x] = (float)row[min(bx * 8u + x, w - 1u)] - 128.0f;
+            for (int x = 0; x < 8; ++x) {
+                const uint32_t x0 = min(bx * 16u + 2u * x, w - 1u), x1 = min(bx * 16u + 2u * x + 1u, w - 1u);
+                f[y * 8 + x] = (float)(((uint32_t)r0[x0] + r0[x1] + r1[x0] + r1[x1] + 2u) >> 2) - 128.0f;
+            }
+        }
+    } else {
+        const uint32_t ox = S ? bx * 16u + (slot & 1u) * 8u : bx * 8u, oy = S ? by * 16u + (slot >> 1) * 8u : by * 8u;
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+            const uint32_t yy = min(oy + y, h - 1u);              // the last row / column is replicated into partial blocks
+            const unsigned char *row = plane + (size_t)yy * w;
+#pragma unroll
+            for (int x = 0; x < 8; ++x) f[y * 8 + x] = (float)row[min(ox + x, w - 1u)] - 128.0f;
+        }
     }
     float t[64];
 #pragma unroll
@@ -139,7 +167,7 @@ k_jpeg_dct(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint32
             // |AC| < 925 and |DC| <= 1024 for 8-bit samples: the clamp only keeps the symbol tables' index in range whatever the bytes
             z[v * 8 + u] = (short)fminf(fmaxf(rintf(s / q[v * 8 + u]), v + u ? -1023.0f : -2047.0f), v + u ? 1023.0f : 2047.0f);
         }
-    const uint32_t blk = 3u * mcu + comp;
+    const uint32_t blk = Mcu<S>::NB * mcu + slot;
     uint4 *dst = (uint4 *)(coef + (size_t)blk * 64);
     uint32_t bits = 0, run = 0;
 #pragma unroll
@@ -168,8 +196,7 @@ k_jpeg_dct(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint32
 }
 
 // ---- entropy coding of one restart interval per wave -------------------------------------------------------------------
-// Worst case of a block: DC 11 + 11 bits, 63 AC of 16 + 10 bits = 1660 bits; an MCU 4980.
-#define JPEG_MCU_BITS 4980u
+// Worst case of an MCU: Mcu<S>::BITS, 4980 bits in 4:4:4 and 9960 in 4:2:0.
 struct Bits {                         // a lane's writer into the interval's bit buffer (big-endian 32-bit words; a word may be shared with the neighbouring lanes' blocks)
     uint32_t *words; uint32_t w; u64 acc; uint32_t n;
     __device__ __forceinline__ void put(uint32_t code, uint32_t len)       // 1 <= len <= 26, n < 32
@@ -181,11 +208,12 @@ struct Bits {                         // a lane's writer into the interval's bit
     __device__ __forceinline__ void flush() { if (n) atomicOr(&words[w], (uint32_t)(acc >> 32)); }
 };
 
-// One workgroup of one wave per interval of `ri` MCUs (3 * ri <= 64: a lane per block).  WRITE = false: lens[interval] = bytes of the
+// One workgroup of one wave per interval of `ri` MCUs (NB * ri <= 64: a lane per block).  WRITE = false: lens[interval] = bytes of the
 // interval, stuffing and the RSTm / EOI marker behind it included.  WRITE = true: the bytes go to out + base + offs[interval],
 // unless info[2] (the status the scan left) says that the stream does not fit.
-// LDS: the symbol tables | bit buffer of ceil(ri * 4980 / 32) + 2 words | stuffed bytes, 2 * ceil(ri * 4980 / 8) + 2 and 8 of padding
-template <bool WRITE>
+// LDS, sized for the worst case of ri MCUs whatever the input (launch_jpeg_kernels): the symbol tables | bit buffer of
+// ceil(ri * BITS / 32) + 2 words | stuffed bytes, 2 * ceil(ri * BITS / 8) + 2 and 8 of padding
+template <int S, bool WRITE>
 __global__ void __launch_bounds__(64)
 k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict__ acbits, uint32_t nmcu, uint32_t ri, uint32_t nint,
                uint32_t *__restrict__ lens, const u64 *__restrict__ offs, const uint32_t *__restrict__ info,
@@ -193,15 +221,16 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
 {
     extern __shared__ uint32_t s_mem[];
     uint32_t *s_huff = s_mem, *s_bits = s_mem + kHuffWords;
-    const uint32_t nbw = (ri * JPEG_MCU_BITS + 31u) / 32u + 2u;
+    constexpr uint32_t NB = Mcu<S>::NB;
+    const uint32_t nbw = (ri * Mcu<S>::BITS + 31u) / 32u + 2u;
     unsigned char *s_out = (unsigned char *)(s_bits + nbw);
     const uint32_t lane = threadIdx.x, it = blockIdx.x;
     if (WRITE && info[2]) return;
     for (uint32_t i = lane; i < kHuffWords; i += 64) s_huff[i] = g_huff.e[i];
-    const uint32_t mcu0 = it * ri, nb = 3u * min(ri, nmcu - mcu0);
+    const uint32_t mcu0 = it * ri, nb = NB * min(ri, nmcu - mcu0);
     const bool live = lane < nb;
-    const uint32_t comp = lane % 3u;
-    const size_t blk = (size_t)3u * mcu0 + lane;
+    const uint32_t slot = lane % NB, comp = Mcu<S>::comp(slot), back = Mcu<S>::back(slot);
+    const size_t blk = (size_t)NB * mcu0 + lane;
     const uint4 *cp = (const uint4 *)(coef + blk * 64);
     uint4 cw[8];
     int diff = 0;
@@ -210,7 +239,7 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
 #pragma unroll
         for (int j = 0; j < 8; ++j) cw[j] = cp[j];
         const int dc = (short)(cw[0].x & 0xffffu);
-        const int pred = lane >= 3u ? (int)coef[(blk - 3u) * 64] : 0;      // the previous block of the component; 0 at the interval's start
+        const int pred = lane >= back ? (int)coef[(blk - back) * 64] : 0;  // the previous block of the component; 0 at the interval's start
         diff = dc - pred;
         mybits = acbits[blk] + (uint32_t)nbits_of(diff);                   // (the DC code's length is added below, from the table)
     }
@@ -325,7 +354,7 @@ static void jpeg_quant_table(int quality, int chroma, unsigned char q[64])
 }
 
 // SOI, APP0 (JFIF 1.01), DQT x2, SOF0, DHT x4, DRI, SOS: FL_JPEG_HEADER_BYTES bytes
-static void jpeg_header(unsigned char *out, uint32_t w, uint32_t h, int quality, uint32_t ri)
+static void jpeg_header(unsigned char *out, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling)
 {
     unsigned char *p = out, q[64];
     put16(p, 0xffd8);
@@ -338,7 +367,7 @@ static void jpeg_header(unsigned char *out, uint32_t w, uint32_t h, int quality,
         for (int k = 0; k < 64; ++k) *p++ = q[kZigzag[k]];
     }
     put16(p, 0xffc0); put16(p, 17); *p++ = 8; put16(p, h); put16(p, w); *p++ = 3;
-    for (int c = 0; c < 3; ++c) { *p++ = (unsigned char)(c + 1); *p++ = 0x11; *p++ = c ? 1 : 0; }
+    for (int c = 0; c < 3; ++c) { *p++ = (unsigned char)(c + 1); *p++ = sampling == FL_JPEG_420 && !c ? 0x22 : 0x11; *p++ = c ? 1 : 0; }
     put_dht(p, 0x00, kDcLumBits, kDcVals, 12);
     put_dht(p, 0x10, kAcLumBits, kAcLumVals, 162);
     put_dht(p, 0x01, kDcChrBits, kDcVals, 12);
@@ -350,31 +379,47 @@ static void jpeg_header(unsigned char *out, uint32_t w, uint32_t h, int quality,
     static_assert(FL_JPEG_HEADER_BYTES == 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 6 + 14, "header layout");
 }
 
-JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri)
+JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling)
 {
     JpegLayout l;
-    l.mw = (w + 7u) / 8u;
-    const uint64_t nmcu = (uint64_t)l.mw * ((h + 7u) / 8u);            // <= 8192^2
+    const uint32_t pix = sampling == FL_JPEG_420 ? 16u : 8u, nb = sampling == FL_JPEG_420 ? 6u : 3u;
+    l.mw = (w + pix - 1u) / pix;
+    const uint64_t nmcu = (uint64_t)l.mw * ((h + pix - 1u) / pix);     // <= 8192^2
     l.nmcu = (uint32_t)nmcu;
     l.nint = (uint32_t)((nmcu + ri - 1u) / ri);
     // words: coefficients (int16 x 64 per block) | offsets (u64) | lengths | AC bits (u16 per block) | info
     l.coef = 0;
-    l.offs = l.coef + (size_t)nmcu * 3u * 32u;
+    l.offs = l.coef + (size_t)nmcu * nb * 32u;
     l.lens = l.offs + 2u * (size_t)l.nint;
     l.acbits = l.lens + l.nint;
-    l.info = l.acbits + ((size_t)nmcu * 3u + 1u) / 2u;
+    l.info = l.acbits + ((size_t)nmcu * nb + 1u) / 2u;
     l.words = l.info + 4u;
     return l;
 }
 
-void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri,
-                        uint32_t *scratch, unsigned char *out, size_t cap)
+template <int S>
+static void launch_jpeg_kernels(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, uint32_t ri, const JpegLayout &l,
+                                const JpegQuant &Q, const JpegHeaderArg &hdr, uint32_t *scratch, unsigned char *out, size_t cap)
 {
-    const JpegLayout l = jpeg_layout(w, h, ri);
     short *coef = (short *)(scratch + l.coef);
     u64 *offs = (u64 *)(scratch + l.offs);
     uint32_t *lens = scratch + l.lens, *info = scratch + l.info;
     unsigned short *acbits = (unsigned short *)(scratch + l.acbits);
+    const uint32_t nbw = (ri * Mcu<S>::BITS + 31u) / 32u + 2u;
+    const size_t lds = 4 * (size_t)(kHuffWords + nbw) + 2 * (size_t)((ri * Mcu<S>::BITS + 7u) / 8u) + 2 + 8 + 4;
+    hipLaunchKernelGGL(k_jpeg_dct<S>, dim3((l.nmcu + 255u) / 256u, Mcu<S>::NB), dim3(256), 0, st, src, w, h, l.mw, l.nmcu, Q, coef, acbits);
+    hipLaunchKernelGGL((k_jpeg_entropy<S, false>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES);
+    hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, st, lens, l.nint, offs, info, out, (u64)cap, ri, hdr);
+    hipLaunchKernelGGL((k_jpeg_entropy<S, true>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES);
+}
+
+// ri: 1 .. 21 in 4:4:4, 1 .. 10 in 4:2:0 (the callers clamp it)
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling,
+                        uint32_t *scratch, unsigned char *out, size_t cap)
+{
+    const JpegLayout l = jpeg_layout(w, h, ri, sampling);
     JpegQuant Q;
     unsigned char q[64];
     for (int tab = 0; tab < 2; ++tab) {
@@ -382,13 +427,7 @@ void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, ui
         for (int i = 0; i < 64; ++i) Q.q[tab][i] = (float)q[i];
     }
     JpegHeaderArg hdr = {};
-    jpeg_header(hdr.b, w, h, quality, ri);
-    const uint32_t nbw = (ri * JPEG_MCU_BITS + 31u) / 32u + 2u;
-    const size_t lds = 4 * (size_t)(kHuffWords + nbw) + 2 * (size_t)((ri * JPEG_MCU_BITS + 7u) / 8u) + 2 + 8 + 4;
-    hipLaunchKernelGGL(k_jpeg_dct, dim3((l.nmcu + 255u) / 256u, 3), dim3(256), 0, st, src, w, h, l.mw, l.nmcu, Q, coef, acbits);
-    hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
-                       16u + FL_JPEG_HEADER_BYTES);
-    hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, st, lens, l.nint, offs, info, out, (u64)cap, ri, hdr);
-    hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
-                       16u + FL_JPEG_HEADER_BYTES);
+    jpeg_header(hdr.b, w, h, quality, ri, sampling);
+    if (sampling == FL_JPEG_420) launch_jpeg_kernels<FL_JPEG_420>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+    else launch_jpeg_kernels<FL_JPEG_444>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
 }

@@ -103,11 +103,14 @@ void launch_resample(hipStream_t st, fl_dim din, fl_dim dout, int ss, float4 *ds
 void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng, uint32_t nrng, int fmt, void *dst);
 
 // jpeg.hip: baseline JPEG from u8 [3][h][w] Y/Cb/Cr planes.  `scratch` holds jpeg_layout().words words; the 16-byte record, the header and
-// the stream go to `out`, of which nothing at or beyond `cap` (>= 16 + FL_JPEG_HEADER_BYTES) is touched.  ri: MCUs per restart interval, 1..21.
+// the stream go to `out`, of which nothing at or beyond `cap` (>= 16 + FL_JPEG_HEADER_BYTES) is touched.  sampling: FL_JPEG_444 or
+// FL_JPEG_420 (the chroma planes are averaged 2 x 2 on load).  ri: MCUs per restart interval, 1..21 in 4:4:4 and 1..10 in 4:2:0.
 #define FL_JPEG_RI 8u      // the default: how it was chosen is in DESIGN.md §4.8 (a wave codes one interval, a lane one block, so 3 * ri <= 64)
+#define FL_JPEG_RI_420 4u  // the default in 4:2:0 (6 * ri <= 64): the 24 working lanes of the 4:4:4 default; the sweep of DESIGN.md §4.10 does not separate 2 .. 10
+#define FL_JPEG_RI_420_MAX 10u
 struct JpegLayout { uint32_t mw, nmcu, nint; size_t coef, offs, lens, acbits, info, words; };      // MCUs per row / in all, intervals; word offsets into the scratch
-JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri);
-void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri,
+JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling);
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling,
                         uint32_t *scratch, unsigned char *out, size_t cap);
 
 // png.hip: 8-bit truecolour PNG from u8 [h][w][4] (channels 3: the alpha byte is left out).  `scratch` holds png_layout().words words; the

@@ -7,14 +7,19 @@ same encoder command lines, same ``encode(buf) -> (media, logs)`` protocol (``en
 flushes; a change of frame size flushes the x264 stream and starts a new one).  The encoders are
 separate programs (x264, vpxenc, ffmpeg) found on PATH at the first frame — ``command=`` replaces
 the program name, which is also how the tests drive the classes without them.
+
+MJPEGOutput needs no program: the device encodes every frame as a JPEG (output.DeviceJPEGOutput) and the host
+only puts the frames into an AVI file.
 """
+import fractions
+import struct
 import subprocess
 import tempfile
 
 import numpy as np
 
 from . import _lib
-from .output import Output
+from .output import DeviceJPEGOutput, Output
 
 
 class _EncoderPipe(object):
@@ -246,3 +251,95 @@ class VPxOutput(_PlanarOutput):
         else:
             self._pipe.write(buf)
         return {}, []
+
+
+AVI_MAX_BYTES = 2 ** 31 - 1       # AVI 1.0: sizes and offsets are u32 and players read them as signed; OpenDML is not written
+_AVI_MOVI_DATA = 224              # RIFF 12, LIST hdrl 8 + 192, LIST movi 12: where the first chunk's header lies
+_JPEG_SOF0 = 158                  # offset of the SOF0 segment in the device's header: SOI 2, APP0 18, DQT 2 x 69
+
+
+def _avi_header(w, h, fps, sizes, movi_bytes):
+    """Everything in front of the first chunk (AVI 1.0, little-endian).  sizes: the unpadded chunk sizes; movi_bytes: the
+    chunks with their headers and padding."""
+    n, largest = len(sizes), max(sizes) if sizes else 0
+    rate = fractions.Fraction(fps).limit_denominator(100000)
+    avih = struct.pack('<14I', int(round(1e6 / fps)), 0, 0, 0x10, n, 0, 1, largest, w, h, 0, 0, 0, 0)      # 0x10: AVIF_HASINDEX
+    strh = struct.pack('<4s4sIHHIIIIIIII4H', b'vids', b'MJPG', 0, 0, 0, 0, rate.denominator, rate.numerator, 0, n, largest,
+                       0xffffffff, 0, 0, 0, w, h)
+    strf = struct.pack('<IiiHH4sIiiII', 40, w, h, 1, 24, b'MJPG', w * h * 3, 0, 0, 0, 0)
+    assert len(avih) == 56 and len(strh) == 56 and len(strf) == 40
+
+    def chunk(tag, body):
+        return tag + struct.pack('<I', len(body)) + body
+
+    def lst(tag, body):
+        return b'LIST' + struct.pack('<I', 4 + len(body)) + tag + body
+    hdrl = lst(b'hdrl', chunk(b'avih', avih) + lst(b'strl', chunk(b'strh', strh) + chunk(b'strf', strf)))
+    riff = 4 + len(hdrl) + 12 + movi_bytes + 8 + 16 * n
+    out = b'RIFF' + struct.pack('<I', riff) + b'AVI ' + hdrl + b'LIST' + struct.pack('<I', 4 + movi_bytes) + b'movi'
+    assert len(out) == _AVI_MOVI_DATA
+    return out
+
+
+class MJPEGOutput(DeviceJPEGOutput):
+    """Animations as Motion-JPEG in an AVI 1.0 file (``output: {"type": "mjpeg", "quality": 1..100, "sampling": "420" | "444"}``,
+    ``--codec mjpeg``): every frame leaves the GPU as a finished baseline JPEG (``copy`` is DeviceJPEGOutput's) and becomes a
+    ``00dc`` chunk; ``encode(None)`` writes the header and the ``idx1`` index and returns the file.  No external program.
+    A change of frame size flushes and starts a new file, as X264Output does."""
+    suffix = '.avi'
+
+    def __init__(self, fps=24, quality=90, sampling='420', alpha=False):
+        if alpha:
+            raise ValueError('mjpeg has no alpha plane: use x264 with "alpha"')
+        if not fps > 0:
+            raise ValueError('mjpeg needs fps above 0')
+        DeviceJPEGOutput.__init__(self, quality=quality, sampling=sampling)
+        self.fps = fps
+        self._file, self._sizes, self._movi, self.framesize = None, [], 0, None
+
+    def abort(self):
+        if self._file is not None:
+            self._file.close()
+        self._file, self._sizes, self._movi = None, [], 0
+
+    def _flush(self):
+        if self._file is None:
+            return {}, []
+        f, sizes, off = self._file, self._sizes, 4
+        index = bytearray()
+        for n in sizes:                           # offsets count from the 'movi' fourcc
+            index += struct.pack('<4sIII', b'00dc', 0x10, off, n)       # 0x10: AVIIF_KEYFRAME
+            off += 8 + n + (n & 1)
+        f.write(b'idx1' + struct.pack('<I', len(index)) + index)
+        f.seek(0)
+        f.write(_avi_header(self.framesize[1], self.framesize[0], self.fps, sizes, self._movi))
+        f.seek(0)
+        self._file, self._sizes, self._movi = None, [], 0
+        return {'.avi': f}, []
+
+    def encode(self, buf):
+        out = ({}, [])
+        if buf is None:
+            return self._flush()
+        data = self.file_bytes(buf, self.noun)
+        if len(data) < _JPEG_SOF0 + 9 or bytes(data[_JPEG_SOF0:_JPEG_SOF0 + 2]) != b'\xff\xc0':
+            raise IOError('the frame is not a JPEG stream of the device encoder')
+        size = struct.unpack('>HH', bytes(data[_JPEG_SOF0 + 5:_JPEG_SOF0 + 9]))      # (height, width)
+        if self.framesize != size:
+            out = self._flush()
+            self.framesize = size
+        n = len(data)
+        if _AVI_MOVI_DATA + self._movi + 8 + n + (n & 1) + 8 + 16 * (len(self._sizes) + 1) > AVI_MAX_BYTES:
+            raise IOError('the AVI file would pass %d bytes at frame %d: render shorter files with "shard" (--shard SECS)'
+                          % (AVI_MAX_BYTES, len(self._sizes) + 1))
+        if self._file is None:
+            self._file = tempfile.TemporaryFile()
+            self._file.write(b'\0' * _AVI_MOVI_DATA)
+        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
+        self._file.write(b'00dc' + struct.pack('<I', n))
+        self._file.write(memoryview(np.ascontiguousarray(data)))
+        if n & 1:
+            self._file.write(b'\0')
+        self._sizes.append(n)
+        self._movi += 8 + n + (n & 1)
+        return out

@@ -135,41 +135,57 @@ class PILOutput(Output):
 class DeviceEncodedOutput(Output):
     """Stills encoded on the device: the frame leaves the GPU as a finished file.  The host frame is a byte buffer: a 16-byte
     record (u32 nbytes, status, a parameter of the encoder, 0), then the file.  A subclass names the library's entry point
-    (``entry``), gives its one argument beyond the frame and the destination (``argument``) and the buffer's size
-    (``capacity``), and says what the file is (``suffix``, ``noun``)."""
+    (``entry``), gives its one argument beyond the frame and the destination (``argument``; ``arguments`` where there are
+    more) and the buffer's size (``capacity``), and says what the file is (``suffix``, ``noun``)."""
 
     def shape(self, dim):
         return (self.capacity(dim),)
 
+    def arguments(self):
+        return (self.argument(),)
+
     def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
         h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
-        _lib.check(getattr(_lib.load(), self.entry)(fb.ctx, dim.w, dim.h, self.argument(), h_out.ctypes.data if host else None,
-                                                    int(dev_out), self.capacity(dim)))
+        _lib.check(getattr(_lib.load(), self.entry)(*((fb.ctx, dim.w, dim.h) + tuple(self.arguments())
+                                                      + (h_out.ctypes.data if host else None, int(dev_out), self.capacity(dim)))))
         return h_out
+
+    @staticmethod
+    def file_bytes(buf, noun):
+        """The file behind the record of a host frame, as a view of ``buf``; raises when the record says it did not fit."""
+        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
+        if status:
+            raise _lib.FlameError('the %s needs %d bytes and the frame buffer holds %d' % (noun, nbytes, buf.size - 16))
+        return buf[16:16 + nbytes]
 
     def encode(self, buf):
         if buf is None:
             return {}, []
-        nbytes, status = (int(v) for v in np.frombuffer(buf[:8], '<u4'))
-        if status:
-            raise _lib.FlameError('the %s needs %d bytes and the frame buffer holds %d' % (self.noun, nbytes, buf.size - 16))
-        return {self.suffix: io.BytesIO(buf[16:16 + nbytes].tobytes())}, []
+        return {self.suffix: io.BytesIO(self.file_bytes(buf, self.noun).tobytes())}, []
 
 
 class DeviceJPEGOutput(DeviceEncodedOutput):
-    """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100}``): a baseline 4:4:4
-    file (include/flame_hip.h, fl_output_jpeg).  The record's parameter is the restart interval."""
+    """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100, "sampling": "444" |
+    "420"}``): a baseline file, 4:4:4 unless ``sampling`` says 4:2:0 (include/flame_hip.h, fl_output_jpeg and fl_output_jpeg_s).
+    The record's parameter is the restart interval."""
     suffix, entry, noun = '.jpg', 'fl_output_jpeg', 'JPEG stream'
 
-    def __init__(self, quality=100, alpha=False):
+    def __init__(self, quality=100, alpha=False, sampling='444'):
         if alpha:
             raise ValueError('the device JPEG encoder has no alpha plane: use "device": false with "alpha"')
         if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
             raise ValueError('output.quality must be an integer in 1..100')
-        self.quality, self.alpha = quality, False
+        if str(sampling) not in _lib.JPEG_SAMPLING:
+            raise ValueError('output.sampling must be "444" or "420", not "%s"' % (sampling,))
+        self.quality, self.alpha, self.sampling = quality, False, str(sampling)
+        if self.sampling != '444':              # (4:4:4 stays on the entry point it has always used)
+            self.entry = 'fl_output_jpeg_s'
 
     def argument(self):
         return self.quality
+
+    def arguments(self):
+        return (self.quality,) if self.sampling == '444' else (self.quality, _lib.JPEG_SAMPLING[self.sampling])
 
     @staticmethod
     def capacity(dim):
@@ -233,12 +249,12 @@ class Raw16Output(Output):
     suffix = '.rgba16'
 
 
-_VIDEO = ('x264', 'vp8', 'vp9', 'prores')
+_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg')
 
 
 def get_suffix(codec, alpha=False):
     ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', raw='.rgba8', raw16='.rgba16', x264='.h264',
-               prores='.mov', vp8='.webm', vp9='.webm')[codec]
+               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi')[codec]
     return ('_color' + ext) if alpha else ext
 
 
@@ -273,6 +289,8 @@ def get_output_for_profile(gprof):
             return encoders.X264Output(**opts)
         if handler == 'prores':
             return encoders.ProResOutput(fps=gprof.fps, **opts)
+        if handler == 'mjpeg':
+            return encoders.MJPEGOutput(fps=gprof.fps, **opts)
         return encoders.VPxOutput(codec=handler, fps=gprof.fps, **opts)
     raise ValueError('Invalid output type "%s".' % handler)
 

@@ -51,11 +51,11 @@ def add_args(parser=None):
                      help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
-    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'x264', 'vp8', 'vp9', 'prores', 'raw'])
+    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')
-    out.add_argument('--quality', type=int, metavar='N', help='JPEG quality, 1..100 (sets output.quality)')
+    out.add_argument('--quality', type=int, metavar='N', help='JPEG quality, 1..100, of jpeg stills and mjpeg animations (sets output.quality)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')

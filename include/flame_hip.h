@@ -286,6 +286,21 @@ size_t fl_jpeg_bound(uint32_t w, uint32_t h);
 int fl_jpeg_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_jpeg(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap);
 
+/* The same with the chroma sampling chosen.  FL_JPEG_444: the three entry points above, byte for byte.
+ * FL_JPEG_420: SOF0 declares Y as 2x2 and Cb, Cr as 1x1; an MCU covers 16x16 pixels and holds six blocks, Y00 Y01 Y10 Y11 Cb Cr.
+ * The source is still the full-resolution planes of FL_OUT_YUV444P (fl_output_jpeg_s makes the draws of fl_output_jpeg and
+ * leaves the same dither states): the encoder takes each chroma sample as (a + b + c + d + 2) >> 2 over its 2x2 full-resolution
+ * samples, whose coordinates are clamped to w - 1, h - 1 first, so odd sizes and partial MCUs replicate the last column / row
+ * before the average.  The Y predictor runs through the four Y blocks of an MCU and on into the next MCU; all three restart
+ * with every interval.  The header keeps its FL_JPEG_HEADER_BYTES bytes; the record is the same.
+ * fl_jpeg_bound_s: 0 as fl_jpeg_bound, and for an unknown sampling.  Any other call with an unknown sampling is FL_E_INVAL. */
+enum { FL_JPEG_444 = 0, FL_JPEG_420 = 1 };
+size_t fl_jpeg_bound_s(uint32_t w, uint32_t h, int sampling);
+int fl_jpeg_encode_s(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling,
+                     void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_jpeg_s(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, int sampling,
+                     void *host_out, uint64_t dev_out, size_t cap);
+
 /* PNG stills encoded on the device: 8-bit truecolour, colour type 2 (channels 3) or 6 (channels 4), not interlaced:
  * the signature, IHDR, one IDAT per segment, IEND; no ancillary chunk.  The IDATs hold one zlib stream (header 78 01, deflate
  * blocks, Adler-32).  Every row is filtered with Paeth (filter byte 4).  The filtered bytes are cut into segments of segment_bytes
