@@ -20,6 +20,7 @@ FL_OP_CHAOS_CDF = 11                # include/flame_hip.h (6): dst[0..nxf-1] <- 
 FL_OP_OPACITY = 10                  # include/flame_hip.h (6): dst <- plot probability of the xform's samples
 JPEG_HEADER_BYTES = 629             # include/flame_hip.h FL_JPEG_HEADER_BYTES
 JPEG_SAMPLING = {'444': 0, '420': 1}        # include/flame_hip.h FL_JPEG_444, FL_JPEG_420
+JPEG_OPTIMIZE = 1                   # include/flame_hip.h FL_JPEG_OPTIMIZE
 PNG_HEADER_BYTES = 33               # include/flame_hip.h FL_PNG_HEADER_BYTES
 OUT = dict(rgba8=0, rgba16=1, yuv444p=2, yuv444p10=3, yuv420p10=4, yuv444p12=5)     # include/flame_hip.h FL_OUT_*
 
@@ -52,6 +53,9 @@ _SIGS = {
     'fl_jpeg_bound_s': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int]),
     'fl_jpeg_encode_s': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_jpeg_s': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_jpeg_bound_f': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint]),
+    'fl_jpeg_encode_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_output_jpeg_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_png_bound': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int]),
     'fl_png_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_png': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),

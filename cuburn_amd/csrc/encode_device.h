@@ -51,3 +51,81 @@ __device__ __forceinline__ void store_bytes(unsigned char *dst, const uint32_t *
     }
     if (t < nbytes - tail0) dst[tail0 + t] = lds_bytes[tail0 + t];
 }
+
+// ---- length-limited Huffman codes, by the whole workgroup (256 threads, nsym <= 288) ----------------------------------
+constexpr uint32_t kSymPad = 288u;                            // the largest alphabet (deflate's 286 literal / length symbols), rounded up
+struct HuffTmp {
+    uint32_t sfreq[kSymPad], nfreq[kSymPad], cnt[32], next[16];
+    unsigned short ssym[kSymPad], lpar[kSymPad], npar[kSymPad];
+};
+
+// lens[s] = code length of symbol s (0: unused) of a complete prefix code with no length above maxlen, Huffman's where that obeys the
+// limit.  A lone used symbol gets a one-bit code and so does an unused neighbour, which keeps the code complete.
+static __device__ void build_lengths(const uint32_t *freq, uint32_t nsym, uint32_t maxlen, unsigned char *lens, HuffTmp &T)
+{
+    const uint32_t t = threadIdx.x;
+    uint32_t used = 0;
+    for (uint32_t i = t; i < kSymPad; i += 256u) {
+        const uint32_t f = i < nsym ? freq[i] : 0u;
+        if (i < nsym) lens[i] = 0;
+        if (f) {                                              // rank by (frequency, symbol), ascending
+            uint32_t r = 0;
+#pragma unroll 8
+            for (uint32_t j = 0; j < nsym; ++j) { const uint32_t fj = freq[j]; r += fj && (fj < f || (fj == f && j < i)) ? 1u : 0u; }
+            T.sfreq[r] = f; T.ssym[r] = (unsigned short)i;
+            ++used;
+        }
+    }
+    if (t < 32u) T.cnt[t] = 0;
+    const uint32_t n = (uint32_t)__syncthreads_count(used >= 1u) + (uint32_t)__syncthreads_count(used >= 2u);
+    if (n == 0) return;
+    if (n == 1u) {
+        if (t == 0) { const uint32_t s = T.ssym[0]; lens[s] = 1; lens[s ? 0 : 1] = 1; }
+        __syncthreads();
+        return;
+    }
+    if (t == 0) {                                             // the two-queue merge: leaves in order, inner nodes in order of creation
+        constexpr uint32_t kNone = 0xffffffffu;               // an empty queue (no frequency reaches it)
+        uint32_t leaf = 0, node = 0;
+        uint32_t lf = T.sfreq[0], lf1 = T.sfreq[1], nf = kNone;      // the queues' heads, and the leaf behind the head: loaded ahead of their use
+        for (uint32_t k = 0; k + 1u < n; ++k) {
+            uint32_t f = 0;
+#pragma unroll
+            for (int pick = 0; pick < 2; ++pick) {
+                if (lf <= nf) {                               // (a tie takes the leaf)
+                    f += lf; T.lpar[leaf++] = (unsigned short)k;
+                    lf = lf1; lf1 = leaf + 1u < n ? T.sfreq[leaf + 1u] : kNone;
+                } else {
+                    f += nf; T.npar[node++] = (unsigned short)k;
+                    nf = node < k ? T.nfreq[node] : kNone;
+                }
+            }
+            T.nfreq[k] = f;
+            if (node == k) nf = f;                            // the new node is the only one waiting
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += 256u) {                  // a leaf's depth: the steps from it to the root, node n - 2
+        uint32_t d = 1u;
+        for (uint32_t k = T.lpar[i]; k != n - 2u; k = T.npar[k]) ++d;
+        atomicAdd(&T.cnt[min(d, maxlen)], 1u);
+    }
+    __syncthreads();
+    if (t == 0) {                                             // depths cut at maxlen over-subscribe the code: lengthen until Kraft's sum is 1 again
+        uint32_t total = 0;
+        for (uint32_t l = 1; l <= maxlen; ++l) total += T.cnt[l] << (maxlen - l);
+        while (total > 1u << maxlen) {
+            --T.cnt[maxlen];
+            for (uint32_t l = maxlen - 1u; l > 0; --l)
+                if (T.cnt[l]) { --T.cnt[l]; T.cnt[l + 1u] += 2u; break; }
+            --total;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < n; i += 256u) {                  // the rarest symbols take the longest codes
+        uint32_t l = maxlen, above = T.cnt[maxlen];
+        while (i >= above && l > 1u) above += T.cnt[--l];
+        lens[T.ssym[i]] = (unsigned char)l;
+    }
+    __syncthreads();
+}

@@ -1039,28 +1039,54 @@ size_t fl_jpeg_bound_s(uint32_t w, uint32_t h, int sampling)
 
 size_t fl_jpeg_bound(uint32_t w, uint32_t h) { return fl_jpeg_bound_s(w, h, FL_JPEG_444); }
 
-static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, const void *host_out, uint64_t dev_out, size_t cap)
+// FL_JPEG_OPTIMIZE, by the same rule with the longest codes a frame's own tables can have: a DC table of 13 leaves (the 12
+// categories and the pseudo-symbol) has no code above 12 bits, an AC code is limited to 16: 12 + 11 + 63 * 26 = 1661 bits a block.
+// 4:4:4: 4983 bits, 623 bytes, 1248 per MCU as before; 4:2:0: 9966 bits, 1246 bytes, 2 * 1246 + 2 = 2494.
+// The symbol counts must fit the table builder's 32-bit sums: no more than FL_JPEG_OPT_MAX_BLOCKS blocks.
+static uint64_t jpeg_blocks(uint32_t w, uint32_t h, int sampling)
+{
+    return sampling == FL_JPEG_420 ? (uint64_t)((w + 15u) / 16u) * ((h + 15u) / 16u) * 6u : (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 3u;
+}
+
+size_t fl_jpeg_bound_f(uint32_t w, uint32_t h, int sampling, unsigned flags)
+{
+    if (!flags) return fl_jpeg_bound_s(w, h, sampling);
+    if (flags != FL_JPEG_OPTIMIZE || !fl_jpeg_bound_s(w, h, sampling) || jpeg_blocks(w, h, sampling) > FL_JPEG_OPT_MAX_BLOCKS) return 0;
+    if (sampling == FL_JPEG_420) return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 15u) / 16u) * ((h + 15u) / 16u) * 2494u;
+    return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 1248u;
+}
+
+static int check_jpeg(const fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, unsigned flags, const void *host_out, uint64_t dev_out, size_t cap)
 {
     if (int rc = check_encode(c, "jpeg", w, h, FL_JPEG_HEADER_BYTES, host_out, dev_out, cap)) return rc;
     REQUIRE(quality >= 1 && quality <= 100, "jpeg: quality must be 1..100");
     REQUIRE(sampling == FL_JPEG_444 || sampling == FL_JPEG_420, "jpeg: sampling must be FL_JPEG_444 or FL_JPEG_420");
+    REQUIRE(!(flags & ~(unsigned)FL_JPEG_OPTIMIZE), "jpeg: unknown flag");
+    if (flags && jpeg_blocks(w, h, sampling) > FL_JPEG_OPT_MAX_BLOCKS) return fail(FL_E_UNSUPPORTED, "jpeg: FL_JPEG_OPTIMIZE takes frames of at most 2^24 blocks", __FILE__, __LINE__);
     return FL_OK;
 }
 
-static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality, int sampling,
+static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int quality, int sampling, unsigned flags,
                           void *host_out, uint64_t dev_out, size_t cap)
 {
     const uint32_t ri = sampling == FL_JPEG_420 ? c->jpeg_ri_420 : c->jpeg_ri;
-    return encode_on(c, ln, host_out, dev_out, cap, fl_jpeg_bound_s(w, h, sampling), jpeg_layout(w, h, ri, sampling).words, "jpeg stream", "jpeg scratch",
-                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_jpeg_encode(st, src, w, h, quality, ri, sampling, scratch, dst, cap); });
+    const bool optimize = flags & FL_JPEG_OPTIMIZE;
+    return encode_on(c, ln, host_out, dev_out, cap, fl_jpeg_bound_f(w, h, sampling, flags), jpeg_layout(w, h, ri, sampling).words, "jpeg stream", "jpeg scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_jpeg_encode(st, src, w, h, quality, ri, sampling, optimize, scratch, dst, cap); });
+}
+
+int fl_jpeg_encode_f(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, unsigned flags, void *host_out, uint64_t dev_out,
+                     size_t cap)
+{
+    if (int rc = check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "jpeg: null source planes");
+    HIPCHK(hipSetDevice(c->device));
+    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, sampling, flags, host_out, dev_out, cap);
 }
 
 int fl_jpeg_encode_s(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, sampling, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "jpeg: null source planes");
-    HIPCHK(hipSetDevice(c->device));
-    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, sampling, host_out, dev_out, cap);
+    return fl_jpeg_encode_f(c, w, h, src_dev, quality, sampling, 0u, host_out, dev_out, cap);
 }
 
 int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, void *host_out, uint64_t dev_out, size_t cap)
@@ -1068,14 +1094,19 @@ int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int qual
     return fl_jpeg_encode_s(c, w, h, src_dev, quality, FL_JPEG_444, host_out, dev_out, cap);
 }
 
-int fl_output_jpeg_s(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
+int fl_output_jpeg_f(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, unsigned flags, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, sampling, host_out, dev_out, cap)) return rc;
+    if (int rc = check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap)) return rc;
     HIPCHK(hipSetDevice(c->device));
     Lane &ln = c->lane();
     if (int rc = convert_front(c, ln, w, h, FL_OUT_YUV444P, nullptr)) return rc;
-    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, sampling, host_out, dev_out, cap)) return rc;
+    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, sampling, flags, host_out, dev_out, cap)) return rc;
     return close_frame(c, ln);
+}
+
+int fl_output_jpeg_s(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
+{
+    return fl_output_jpeg_f(c, w, h, quality, sampling, 0u, host_out, dev_out, cap);
 }
 
 int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_out, uint64_t dev_out, size_t cap)

@@ -9,6 +9,12 @@
 //   k_jpeg_entropy<S,1> the same packing again, stuffed in LDS, stored at the interval's place with dword stores
 // The intervals are byte aligned and independent (the DC predictor restarts), which is what makes the scan parallel; nothing is
 // stored at or beyond `cap`: the last pass stores nothing when the stream does not fit.
+// With `optimize` the frame's own Huffman tables take the place of Annex K's, three launches more:
+//   k_jpeg_hist         one lane per block: how often the scan will emit every symbol of the four tables
+//   k_jpeg_tables       a workgroup per table: the four length-limited codes (build_lengths), the symbol table the entropy kernel reads,
+//                       and BITS / HUFFVAL into the header's DHT segments
+//   k_jpeg_acbits       one lane per block: the bit length of the block's AC symbols under the new lengths
+// and k_jpeg_entropy<S, *, true> and k_jpeg_scan<true>, which read those tables and leave the DHT bodies alone.
 #include "kernels.h"
 #include "encode_device.h"
 
@@ -100,6 +106,8 @@ __device__ __forceinline__ int nbits_of(int v) { const int a = v < 0 ? -v : v; r
 template <int S> struct Mcu {
     static constexpr uint32_t NB = S ? 6u : 3u;               // blocks
     static constexpr uint32_t BITS = NB * 1660u;              // worst case of a block: DC 11 + 11 bits, 63 AC of 16 + 10 bits = 1660 bits
+    static constexpr uint32_t BITS_OPT = NB * 1661u;          // ... with a frame's own tables: a DC code of 13 leaves can take 12 bits
+    __host__ __device__ static constexpr uint32_t bits(bool opt) { return opt ? BITS_OPT : BITS; }
     __host__ __device__ static constexpr uint32_t comp(uint32_t slot) { return S ? (slot < 4u ? 0u : slot - 3u) : slot; }
     // how many blocks back the component's previous block lies: 4:2:0 Y runs through the MCU's four blocks and on into the next
     // MCU (Y00 follows the Y11 three blocks before it), Cb and Cr run MCU to MCU
@@ -213,20 +221,21 @@ struct Bits {                         // a lane's writer into the interval's bit
 // unless info[2] (the status the scan left) says that the stream does not fit.
 // LDS, sized for the worst case of ri MCUs whatever the input (launch_jpeg_kernels): the symbol tables | bit buffer of
 // ceil(ri * BITS / 32) + 2 words | stuffed bytes, 2 * ceil(ri * BITS / 8) + 2 and 8 of padding
-template <int S, bool WRITE>
+// OPT: the symbol tables are the frame's own, read from `huff` (k_jpeg_tables wrote them), and BITS is BITS_OPT.
+template <int S, bool WRITE, bool OPT = false>
 __global__ void __launch_bounds__(64)
 k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict__ acbits, uint32_t nmcu, uint32_t ri, uint32_t nint,
                uint32_t *__restrict__ lens, const u64 *__restrict__ offs, const uint32_t *__restrict__ info,
-               unsigned char *__restrict__ out, uint32_t base)
+               unsigned char *__restrict__ out, uint32_t base, const uint32_t *__restrict__ huff)
 {
     extern __shared__ uint32_t s_mem[];
     uint32_t *s_huff = s_mem, *s_bits = s_mem + kHuffWords;
     constexpr uint32_t NB = Mcu<S>::NB;
-    const uint32_t nbw = (ri * Mcu<S>::BITS + 31u) / 32u + 2u;
+    const uint32_t nbw = (ri * Mcu<S>::bits(OPT) + 31u) / 32u + 2u;
     unsigned char *s_out = (unsigned char *)(s_bits + nbw);
     const uint32_t lane = threadIdx.x, it = blockIdx.x;
     if (WRITE && info[2]) return;
-    for (uint32_t i = lane; i < kHuffWords; i += 64) s_huff[i] = g_huff.e[i];
+    for (uint32_t i = lane; i < kHuffWords; i += 64) s_huff[i] = OPT ? huff[i] : g_huff.e[i];
     const uint32_t mcu0 = it * ri, nb = NB * min(ri, nmcu - mcu0);
     const bool live = lane < nb;
     const uint32_t slot = lane % NB, comp = Mcu<S>::comp(slot), back = Mcu<S>::back(slot);
@@ -315,6 +324,16 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
 
 // ---- where the intervals go ------------------------------------------------------------------------------------------
 // One workgroup: offs[i] = sum of lens[0 .. i), info = {total low, total high, status}; the record and the header go to `out`.
+// OPT: but for BITS and HUFFVAL of the four DHT segments, which k_jpeg_tables has written there.
+// Where they lie in the header: SOI 2, APP0 18, DQT 2 x 69, SOF0 19 = 177, then FFC4, the length and the class / id in front of each.
+enum { kDhtDcLum = 177 + 5, kDhtAcLum = kDhtDcLum + 28 + 5, kDhtDcChr = kDhtAcLum + 178 + 5, kDhtAcChr = kDhtDcChr + 28 + 5 };
+static_assert(kDhtAcChr + 178 + 6 + 14 == FL_JPEG_HEADER_BYTES, "header layout");
+__host__ __device__ constexpr bool in_dht_body(uint32_t t)
+{
+    return (t >= kDhtDcLum && t < kDhtDcLum + 28u) || (t >= kDhtAcLum && t < kDhtAcLum + 178u) || (t >= kDhtDcChr && t < kDhtDcChr + 28u) ||
+           (t >= kDhtAcChr && t < kDhtAcChr + 178u);
+}
+template <bool OPT>
 __global__ void __launch_bounds__(1024)
 k_jpeg_scan(const uint32_t *__restrict__ lens, uint32_t nint, u64 *__restrict__ offs, uint32_t *__restrict__ info,
             unsigned char *__restrict__ out, u64 cap, uint32_t ri, JpegHeaderArg hdr)
@@ -329,7 +348,143 @@ k_jpeg_scan(const uint32_t *__restrict__ lens, uint32_t nint, u64 *__restrict__ 
     const uint32_t status = need > cap - 16u ? 1u : 0u;
     if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; }
     write_record(out, need, status, ri, t);
-    if (t < FL_JPEG_HEADER_BYTES) out[16u + t] = hdr.b[t];                 // (cap >= 16 + the header: the callers checked)
+    if (t < FL_JPEG_HEADER_BYTES && !(OPT && in_dht_body(t))) out[16u + t] = hdr.b[t];      // (cap >= 16 + the header: the callers checked)
+}
+
+// ---- a frame's own Huffman tables (`optimize`) --------------------------------------------------------
+// The legal symbols of a table, all of which its DHT lists whether the frame uses them or not (the header keeps its length):
+// the DC categories 0..11; EOB, ZRL and run 0..15 x size 1..10.
+__device__ __forceinline__ bool legal_symbol(bool ac, uint32_t s) { return ac ? s == 0u || s == 0xf0u || ((s & 15u) >= 1u && (s & 15u) <= 10u) : s < 12u; }
+
+// f(symbol) for every AC symbol the scan emits for the block whose coefficients are cw, in the order of the scan
+template <class Fn>
+__device__ __forceinline__ void for_ac_symbols(const uint4 (&cw)[8], Fn &&f)
+{
+    uint32_t run = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t wd[4] = {cw[j].x, cw[j].y, cw[j].z, cw[j].w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (j == 0 && e == 0) continue;
+            const int v = (short)(wd[e >> 1] >> ((e & 1) * 16) & 0xffffu);
+            if (v == 0) { ++run; continue; }
+            for (; run > 15u; run -= 16u) f(0xf0u);
+            f(run << 4 | (uint32_t)nbits_of(v));
+            run = 0;
+        }
+    }
+    if (run) f(0u);
+}
+
+// One lane per block (nblk = NB * nmcu <= 2^24 of them): counts[] += how often the scan emits each symbol, laid out as the symbol
+// tables are (kDcLum ..).  The DC difference is the entropy kernel's: the predictor is the component's previous block, 0 at the
+// start of every interval of ri MCUs.  A workgroup counts in LDS and adds what it found to the frame's counts, which the caller
+// cleared; integer sums, so the order does not matter.
+template <int S>
+__global__ void __launch_bounds__(256)
+k_jpeg_hist(const short *__restrict__ coef, uint32_t nblk, uint32_t ri, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t s_cnt[kHuffWords];
+    constexpr uint32_t NB = Mcu<S>::NB;
+    const uint32_t t = threadIdx.x, blk = blockIdx.x * 256u + t;
+    for (uint32_t i = t; i < kHuffWords; i += 256u) s_cnt[i] = 0;
+    __syncthreads();
+    if (blk < nblk) {
+        const uint32_t mcu = blk / NB, slot = blk - mcu * NB, comp = Mcu<S>::comp(slot), back = Mcu<S>::back(slot);
+        const uint32_t pos = (mcu % ri) * NB + slot;                       // the block's lane in its interval
+        const uint4 *cp = (const uint4 *)(coef + (size_t)blk * 64);
+        uint4 cw[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cw[j] = cp[j];
+        const int dc = (short)(cw[0].x & 0xffffu);
+        const int pred = pos >= back ? (int)coef[(size_t)(blk - back) * 64] : 0;
+        atomicAdd(&s_cnt[(comp ? kDcChr : kDcLum) + (uint32_t)nbits_of(dc - pred)], 1u);      // (a category is at most 12 < 16)
+        uint32_t *ac = s_cnt + (comp ? kAcChr : kAcLum);
+        for_ac_symbols(cw, [&](uint32_t sym) { atomicAdd(&ac[sym], 1u); });
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kHuffWords; i += 256u) { const uint32_t c = s_cnt[i]; if (c) atomicAdd(&counts[i], c); }
+}
+
+// Four workgroups of 256 threads, one per table in the order of the file: freq = 2 * count + 2 for the legal symbols and 1 for a
+// pseudo-symbol behind them (strictly the rarest: it takes a longest code, which keeps the all-ones codeword unassigned, as
+// T.81 demands), build_lengths with the limit 16, codes as in T.81 Annex C.  huff[] = code | length << 16 by symbol, the table
+// k_jpeg_entropy<.., true> reads; BITS and HUFFVAL (the legal symbols by (length, symbol)) go into the header at out + 16.
+// Listing every legal symbol has a price on frames of a few dozen symbols: where sum count * length is not below what Annex K's
+// table of the same kind costs, the table keeps Annex K's lengths.  Those tables too list their symbols by (length, symbol), so the
+// steps that follow write Annex K's BITS, HUFFVAL and codes; with all four kept the file is the one without `optimize`.
+__global__ void __launch_bounds__(256)
+k_jpeg_tables(const uint32_t *__restrict__ counts, uint32_t *__restrict__ huff, unsigned char *__restrict__ out)
+{
+    __shared__ HuffTmp T;
+    __shared__ uint32_t s_freq[kSymPad], s_n[17], s_first[17], s_pos[17];
+    __shared__ unsigned char s_lens[kSymPad];
+    __shared__ unsigned long long s_cost[2];                               // code bits of the frame's symbols: with the new lengths, with Annex K's
+    const uint32_t t = threadIdx.x, tab = blockIdx.x;
+    const bool ac = tab & 1u;
+    const uint32_t base = tab == 0 ? kDcLum : tab == 1u ? kAcLum : tab == 2u ? kDcChr : kAcChr;
+    const uint32_t body = tab == 0 ? kDhtDcLum : tab == 1u ? kDhtAcLum : tab == 2u ? kDhtDcChr : kDhtAcChr;
+    const uint32_t pseudo = ac ? 256u : 12u, nwords = ac ? 256u : 16u;
+    for (uint32_t i = t; i < kSymPad; i += 256u) s_freq[i] = i < pseudo ? (legal_symbol(ac, i) ? 2u * counts[base + i] + 2u : 0u) : i == pseudo ? 1u : 0u;
+    if (t < 17u) s_n[t] = 0;
+    if (t < 2u) s_cost[t] = 0;
+    __syncthreads();
+    build_lengths(s_freq, pseudo + 1u, 16u, s_lens, T);
+    for (uint32_t i = t; i < pseudo; i += 256u) {
+        const uint32_t c = legal_symbol(ac, i) ? counts[base + i] : 0u;
+        if (c) {
+            atomicAdd(&s_cost[0], (unsigned long long)c * s_lens[i]);
+            atomicAdd(&s_cost[1], (unsigned long long)c * (g_huff.e[base + i] >> 16));
+        }
+    }
+    __syncthreads();
+    if (s_cost[0] >= s_cost[1])
+        for (uint32_t i = t; i < pseudo; i += 256u) if (legal_symbol(ac, i)) s_lens[i] = (unsigned char)(g_huff.e[base + i] >> 16);
+    __syncthreads();
+    for (uint32_t i = t; i < pseudo; i += 256u) if (legal_symbol(ac, i)) atomicAdd(&s_n[s_lens[i]], 1u);
+    __syncthreads();
+    if (t == 0) {
+        uint32_t code = 0, k = 0;
+        for (uint32_t l = 1; l <= 16u; ++l) { s_first[l] = code; s_pos[l] = k; code = (code + s_n[l]) << 1; k += s_n[l]; }
+    }
+    __syncthreads();
+    unsigned char *dht = out + 16u + body;
+    if (t < 16u) dht[t] = (unsigned char)s_n[t + 1u];
+    for (uint32_t i = t; i < nwords; i += 256u) {
+        uint32_t e = 0;
+        if (legal_symbol(ac, i)) {
+            const uint32_t l = s_lens[i];
+            uint32_t r = 0;                                            // (the other symbols have length 0, the pseudo-symbol lies behind)
+#pragma unroll 8
+            for (uint32_t j = 0; j < i; ++j) r += s_lens[j] == l ? 1u : 0u;
+            e = (s_first[l] + r) | l << 16;
+            dht[16u + s_pos[l] + r] = (unsigned char)i;
+        }
+        huff[base + i] = e;
+    }
+}
+
+// One lane per block: acbits[] of k_jpeg_dct again, with the lengths of the frame's own AC tables
+template <int S>
+__global__ void __launch_bounds__(256)
+k_jpeg_acbits(const short *__restrict__ coef, uint32_t nblk, const uint32_t *__restrict__ huff, unsigned short *__restrict__ acbits)
+{
+    __shared__ unsigned char s_len[512];                                   // luminance | chrominance
+    static_assert(kAcChr == kAcLum + 256, "the AC tables are adjacent");
+    const uint32_t t = threadIdx.x, blk = blockIdx.x * 256u + t;
+    s_len[t] = (unsigned char)(huff[kAcLum + t] >> 16);
+    s_len[256u + t] = (unsigned char)(huff[kAcLum + 256u + t] >> 16);
+    __syncthreads();
+    if (blk >= nblk) return;
+    const unsigned char *len = s_len + (Mcu<S>::comp(blk % Mcu<S>::NB) ? 256u : 0u);
+    const uint4 *cp = (const uint4 *)(coef + (size_t)blk * 64);
+    uint4 cw[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cw[j] = cp[j];
+    uint32_t bits = 0;
+    for_ac_symbols(cw, [&](uint32_t sym) { bits += len[sym] + (sym & 15u); });      // (ZRL and EOB: no value bits, and their low nibble is 0)
+    acbits[blk] = (unsigned short)bits;
 }
 
 void put16(unsigned char *&p, uint32_t v) { *p++ = (unsigned char)(v >> 8); *p++ = (unsigned char)v; }
@@ -387,17 +542,19 @@ JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling)
     const uint64_t nmcu = (uint64_t)l.mw * ((h + pix - 1u) / pix);     // <= 8192^2
     l.nmcu = (uint32_t)nmcu;
     l.nint = (uint32_t)((nmcu + ri - 1u) / ri);
-    // words: coefficients (int16 x 64 per block) | offsets (u64) | lengths | AC bits (u16 per block) | info
+    // words: coefficients (int16 x 64 per block) | offsets (u64) | lengths | AC bits (u16 per block) | info | `optimize`: symbol counts | symbol tables
     l.coef = 0;
     l.offs = l.coef + (size_t)nmcu * nb * 32u;
     l.lens = l.offs + 2u * (size_t)l.nint;
     l.acbits = l.lens + l.nint;
     l.info = l.acbits + ((size_t)nmcu * nb + 1u) / 2u;
-    l.words = l.info + 4u;
+    l.counts = l.info + 4u;
+    l.huff = l.counts + kHuffWords;
+    l.words = l.huff + kHuffWords;
     return l;
 }
 
-template <int S>
+template <int S, bool OPT>
 static void launch_jpeg_kernels(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, uint32_t ri, const JpegLayout &l,
                                 const JpegQuant &Q, const JpegHeaderArg &hdr, uint32_t *scratch, unsigned char *out, size_t cap)
 {
@@ -405,18 +562,27 @@ static void launch_jpeg_kernels(hipStream_t st, const unsigned char *src, uint32
     u64 *offs = (u64 *)(scratch + l.offs);
     uint32_t *lens = scratch + l.lens, *info = scratch + l.info;
     unsigned short *acbits = (unsigned short *)(scratch + l.acbits);
-    const uint32_t nbw = (ri * Mcu<S>::BITS + 31u) / 32u + 2u;
-    const size_t lds = 4 * (size_t)(kHuffWords + nbw) + 2 * (size_t)((ri * Mcu<S>::BITS + 7u) / 8u) + 2 + 8 + 4;
+    uint32_t *counts = scratch + l.counts, *huff = OPT ? scratch + l.huff : nullptr;
+    constexpr uint32_t BITS = Mcu<S>::bits(OPT);
+    const uint32_t nbw = (ri * BITS + 31u) / 32u + 2u;
+    const size_t lds = 4 * (size_t)(kHuffWords + nbw) + 2 * (size_t)((ri * BITS + 7u) / 8u) + 2 + 8 + 4;
+    if (OPT) (void)hipMemsetAsync(counts, 0, 4 * kHuffWords, st);      // (an error stays the runtime's last error, which the caller reads)
     hipLaunchKernelGGL(k_jpeg_dct<S>, dim3((l.nmcu + 255u) / 256u, Mcu<S>::NB), dim3(256), 0, st, src, w, h, l.mw, l.nmcu, Q, coef, acbits);
-    hipLaunchKernelGGL((k_jpeg_entropy<S, false>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
-                       16u + FL_JPEG_HEADER_BYTES);
-    hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, st, lens, l.nint, offs, info, out, (u64)cap, ri, hdr);
-    hipLaunchKernelGGL((k_jpeg_entropy<S, true>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
-                       16u + FL_JPEG_HEADER_BYTES);
+    if (OPT) {
+        const uint32_t nblk = Mcu<S>::NB * l.nmcu;                         // <= 2^24: the callers refuse larger frames
+        hipLaunchKernelGGL(k_jpeg_hist<S>, dim3((nblk + 255u) / 256u), dim3(256), 0, st, coef, nblk, ri, counts);
+        hipLaunchKernelGGL(k_jpeg_tables, dim3(4), dim3(256), 0, st, counts, huff, out);
+        hipLaunchKernelGGL(k_jpeg_acbits<S>, dim3((nblk + 255u) / 256u), dim3(256), 0, st, coef, nblk, huff, acbits);
+    }
+    hipLaunchKernelGGL((k_jpeg_entropy<S, false, OPT>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES, huff);
+    hipLaunchKernelGGL(k_jpeg_scan<OPT>, dim3(1), dim3(1024), 0, st, lens, l.nint, offs, info, out, (u64)cap, ri, hdr);
+    hipLaunchKernelGGL((k_jpeg_entropy<S, true, OPT>), dim3(l.nint), dim3(64), lds, st, coef, acbits, l.nmcu, ri, l.nint, lens, offs, info, out,
+                       16u + FL_JPEG_HEADER_BYTES, huff);
 }
 
-// ri: 1 .. 21 in 4:4:4, 1 .. 10 in 4:2:0 (the callers clamp it)
-void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling,
+// ri: 1 .. 21 in 4:4:4, 1 .. 10 in 4:2:0 (the callers clamp it).  optimize: the frame's own Huffman tables (at most 2^24 blocks).
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling, bool optimize,
                         uint32_t *scratch, unsigned char *out, size_t cap)
 {
     const JpegLayout l = jpeg_layout(w, h, ri, sampling);
@@ -428,6 +594,11 @@ void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, ui
     }
     JpegHeaderArg hdr = {};
     jpeg_header(hdr.b, w, h, quality, ri, sampling);
-    if (sampling == FL_JPEG_420) launch_jpeg_kernels<FL_JPEG_420>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
-    else launch_jpeg_kernels<FL_JPEG_444>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+    if (sampling == FL_JPEG_420) {
+        if (optimize) launch_jpeg_kernels<FL_JPEG_420, true>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+        else launch_jpeg_kernels<FL_JPEG_420, false>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+    } else {
+        if (optimize) launch_jpeg_kernels<FL_JPEG_444, true>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+        else launch_jpeg_kernels<FL_JPEG_444, false>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
+    }
 }

@@ -108,9 +108,11 @@ void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng
 #define FL_JPEG_RI 8u      // the default: how it was chosen is in DESIGN.md §4.8 (a wave codes one interval, a lane one block, so 3 * ri <= 64)
 #define FL_JPEG_RI_420 4u  // the default in 4:2:0 (6 * ri <= 64): the 24 working lanes of the 4:4:4 default; the sweep of DESIGN.md §4.10 does not separate 2 .. 10
 #define FL_JPEG_RI_420_MAX 10u
-struct JpegLayout { uint32_t mw, nmcu, nint; size_t coef, offs, lens, acbits, info, words; };      // MCUs per row / in all, intervals; word offsets into the scratch
+// optimize: the Huffman tables are built from the frame's own symbol counts; the frame has at most FL_JPEG_OPT_MAX_BLOCKS blocks.
+#define FL_JPEG_OPT_MAX_BLOCKS (1u << 24)      // 63 symbols a block at frequency 2 * count + 2: the builder's 32-bit sums hold them
+struct JpegLayout { uint32_t mw, nmcu, nint; size_t coef, offs, lens, acbits, info, counts, huff, words; };      // MCUs per row / in all, intervals; word offsets into the scratch
 JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling);
-void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling,
+void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling, bool optimize,
                         uint32_t *scratch, unsigned char *out, size_t cap);
 
 // png.hip: 8-bit truecolour PNG from u8 [h][w][4] (channels 3: the alpha byte is left out).  `scratch` holds png_layout().words words; the

@@ -282,18 +282,18 @@ def _avi_header(w, h, fps, sizes, movi_bytes):
 
 
 class MJPEGOutput(DeviceJPEGOutput):
-    """Animations as Motion-JPEG in an AVI 1.0 file (``output: {"type": "mjpeg", "quality": 1..100, "sampling": "420" | "444"}``,
-    ``--codec mjpeg``): every frame leaves the GPU as a finished baseline JPEG (``copy`` is DeviceJPEGOutput's) and becomes a
+    """Animations as Motion-JPEG in an AVI 1.0 file (``output: {"type": "mjpeg", "quality": 1..100, "sampling": "420" | "444",
+    "optimize": bool}``, ``--codec mjpeg``; ``optimize`` as DeviceJPEGOutput's, every frame with tables of its own): every frame leaves the GPU as a finished baseline JPEG (``copy`` is DeviceJPEGOutput's) and becomes a
     ``00dc`` chunk; ``encode(None)`` writes the header and the ``idx1`` index and returns the file.  No external program.
     A change of frame size flushes and starts a new file, as X264Output does."""
     suffix = '.avi'
 
-    def __init__(self, fps=24, quality=90, sampling='420', alpha=False):
+    def __init__(self, fps=24, quality=90, sampling='420', alpha=False, optimize=False):
         if alpha:
             raise ValueError('mjpeg has no alpha plane: use x264 with "alpha"')
         if not fps > 0:
             raise ValueError('mjpeg needs fps above 0')
-        DeviceJPEGOutput.__init__(self, quality=quality, sampling=sampling)
+        DeviceJPEGOutput.__init__(self, quality=quality, sampling=sampling, optimize=optimize)
         self.fps = fps
         self._file, self._sizes, self._movi, self.framesize = None, [], 0, None
 

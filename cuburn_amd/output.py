@@ -166,25 +166,33 @@ class DeviceEncodedOutput(Output):
 
 class DeviceJPEGOutput(DeviceEncodedOutput):
     """JPEG stills encoded on the device (``output: {"type": "jpeg", "device": true, "quality": 1..100, "sampling": "444" |
-    "420"}``): a baseline file, 4:4:4 unless ``sampling`` says 4:2:0 (include/flame_hip.h, fl_output_jpeg and fl_output_jpeg_s).
+    "420", "optimize": bool}``): a baseline file, 4:4:4 unless ``sampling`` says 4:2:0 (include/flame_hip.h, fl_output_jpeg and
+    fl_output_jpeg_s).  ``optimize``: Huffman tables built from each frame's own symbol counts, as libjpeg's and Pillow's
+    ``optimize`` (fl_output_jpeg_f with FL_JPEG_OPTIMIZE): the same coefficients in a smaller file, for some more time on the GPU.
     The record's parameter is the restart interval."""
     suffix, entry, noun = '.jpg', 'fl_output_jpeg', 'JPEG stream'
 
-    def __init__(self, quality=100, alpha=False, sampling='444'):
+    def __init__(self, quality=100, alpha=False, sampling='444', optimize=False):
         if alpha:
             raise ValueError('the device JPEG encoder has no alpha plane: use "device": false with "alpha"')
         if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
             raise ValueError('output.quality must be an integer in 1..100')
         if str(sampling) not in _lib.JPEG_SAMPLING:
             raise ValueError('output.sampling must be "444" or "420", not "%s"' % (sampling,))
-        self.quality, self.alpha, self.sampling = quality, False, str(sampling)
-        if self.sampling != '444':              # (4:4:4 stays on the entry point it has always used)
+        if not isinstance(optimize, bool):
+            raise ValueError('output.optimize must be true or false')
+        self.quality, self.alpha, self.sampling, self.optimize = quality, False, str(sampling), optimize
+        if optimize:
+            self.entry = 'fl_output_jpeg_f'
+        elif self.sampling != '444':            # (4:4:4 stays on the entry point it has always used)
             self.entry = 'fl_output_jpeg_s'
 
     def argument(self):
         return self.quality
 
     def arguments(self):
+        if self.optimize:
+            return (self.quality, _lib.JPEG_SAMPLING[self.sampling], _lib.JPEG_OPTIMIZE)
         return (self.quality,) if self.sampling == '444' else (self.quality, _lib.JPEG_SAMPLING[self.sampling])
 
     @staticmethod
@@ -275,6 +283,9 @@ def get_output_for_profile(gprof):
         if set(opts) - {'alpha'}:
             raise ValueError('the device PNG encoder takes "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha'})))
         return DevicePNGOutput(**opts)
+    if 'optimize' in opts and handler != 'mjpeg':
+        raise ValueError('output.optimize: only the device JPEG encoder optimises its Huffman tables: '
+                         'set "device": true on a jpeg output, or use mjpeg')
     if handler in ('jpeg', 'png'):
         return PILOutput(codec=handler, **opts)
     if handler == 'tiff':

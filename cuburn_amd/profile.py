@@ -56,6 +56,9 @@ def add_args(parser=None):
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')
     out.add_argument('--quality', type=int, metavar='N', help='JPEG quality, 1..100, of jpeg stills and mjpeg animations (sets output.quality)')
+    out.add_argument('--optimize', action='store_true', default=None,
+                     help='Huffman tables from each frame\'s own statistics in device-encoded jpeg stills and mjpeg animations: '
+                          'smaller files of the same pixels (sets output.optimize)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -87,6 +90,8 @@ def get_from_args(args):
         prof['output'] = dict(out, encoder='device') if out.get('type') == 'png' else dict(out, device=True)
     if ns.get('quality') is not None:
         prof['output'] = dict(prof.get('output') or {}, quality=ns['quality'])
+    if ns.get('optimize'):
+        prof['output'] = dict(prof.get('output') or {}, optimize=True)
     return name, prof
 
 

@@ -301,6 +301,29 @@ int fl_jpeg_encode_s(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int 
 int fl_output_jpeg_s(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, int sampling,
                      void *host_out, uint64_t dev_out, size_t cap);
 
+/* The same with flags.  flags = 0: the three entry points above, byte for byte.
+ * FL_JPEG_OPTIMIZE: the same coefficients coded with Huffman tables built from the frame's own symbol counts (libjpeg's
+ * "optimize"), on the device and on the lane's stream.  The header keeps its FL_JPEG_HEADER_BYTES bytes and its marker order:
+ * only BITS / HUFFVAL inside the four DHT segments and the scan's bits differ.  Every table lists all its legal symbols (DC:
+ * the categories 0..11; AC: 0x00, 0xF0 and run 0..15 x size 1..10), used or not.  For each table count[s] is how often the
+ * scan emits s; freq[s] = 2 * count[s] + 2, and 1 for one pseudo-symbol behind the alphabet, which therefore takes a longest
+ * code and keeps the all-ones codeword unassigned; the lengths are Huffman's for those frequencies (ranked by (frequency, symbol),
+ * a tie between a leaf and an inner node takes the leaf), cut at 16 bits with the Kraft sum repaired, the rarest symbols taking
+ * the longest codes; HUFFVAL orders the legal symbols by (length, symbol) and the codes follow T.81 Annex C.  A table that
+ * does not cost the frame fewer code bits (sum count * length) than the Annex K table of its kind is that Annex K table, which
+ * obeys the same rules: on a frame of a few symbols all four can be, and the file is then the file of flags = 0.  The same planes,
+ * quality and size give the same bytes.  The record is the same.
+ * fl_jpeg_bound_f: with FL_JPEG_OPTIMIZE a DC code can take 12 bits, so 4:2:0 allows 2494 bytes per MCU (4:4:4: 1248 as before);
+ * 0 as fl_jpeg_bound_s, for an unknown flag bit, and with FL_JPEG_OPTIMIZE for a frame of more than 2^24 blocks (the counts must
+ * fit 32-bit sums).  Any other call is FL_E_INVAL for an unknown flag bit and FL_E_UNSUPPORTED for such a frame, after every
+ * refusal of the entry points above and before anything is queued. */
+enum { FL_JPEG_OPTIMIZE = 1 };
+size_t fl_jpeg_bound_f(uint32_t w, uint32_t h, int sampling, unsigned flags);
+int fl_jpeg_encode_f(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, unsigned flags,
+                     void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_jpeg_f(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, int sampling, unsigned flags,
+                     void *host_out, uint64_t dev_out, size_t cap);
+
 /* PNG stills encoded on the device: 8-bit truecolour, colour type 2 (channels 3) or 6 (channels 4), not interlaced:
  * the signature, IHDR, one IDAT per segment, IEND; no ancillary chunk.  The IDATs hold one zlib stream (header 78 01, deflate
  * blocks, Adler-32).  Every row is filtered with Paeth (filter byte 4).  The filtered bytes are cut into segments of segment_bytes

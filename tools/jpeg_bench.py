@@ -3,6 +3,7 @@ JPEG stills: the host encoder against the device encoder on cfg2 at 1920x1080 (D
 
   python tools/jpeg_bench.py [--frames N] [--quality Q] [--out profiles/jpeg_bench.json] [--sweep] [--sampling 444|420]
   python tools/jpeg_bench.py --codec mjpeg [--frames N] [--out profiles/mjpeg_bench.json] [--sweep]      
+  python tools/jpeg_bench.py --optimize [--frames N] [--out profiles/jpeg_opt_bench.json]                
 
 Prints and writes, per frame:
   * the host Pillow encode (PILOutput.encode of a rendered frame, one thread);
@@ -15,6 +16,9 @@ Prints and writes, per frame:
   * --sampling 420: the device figures for 4:2:0 stills (the sweep then covers 1, 2, 4, 5, 8, 10).
   * --codec mjpeg: the loop with MJPEGOutput (4:2:0, frames appended to an AVI file) at quality 90 and 100, against device 4:4:4
     stills and no encode; bytes per frame 4:2:0 against 4:4:4; fl_timings_detail()[5] per frame; --sweep over the 4:2:0 intervals.
+  * --optimize: the loop with and without `optimize` (Huffman tables from each frame's own statistics) for device
+    4:4:4 stills at quality 100 and mjpeg at quality 90 and 100: frames/s, bytes per frame, fl_timings_detail()[5] per frame; per
+    kernel from the rocprofv3 child for the optimised 4:4:4 stills and the optimised 4:2:0 frames at quality 90.
 There is no fallback: without a GPU the tool fails.
 """
 import argparse
@@ -112,21 +116,38 @@ def mjpeg(args):
     return res
 
 
-def kernels_only(quality, nframes, sampling='444'):
+def optimize(args):
+    """--optimize: every loop once without and once with the key, the pairs next to each other."""
+    n = args.frames
+    res = dict(config='cfg2 1920x1080 2^28 samples', frames=n, runs=1)
+    res['loop_no_encode'], _ = loop({'type': 'raw'}, n, encode=False)
+    for name, block in (('device_jpeg_444_q100', device_block(100, '444')), ('mjpeg_420_q90', {'type': 'mjpeg', 'quality': 90}),
+                        ('mjpeg_420_q100', {'type': 'mjpeg', 'quality': 100})):
+        off, _ = loop(block, n)
+        on, _ = loop(dict(block, optimize=True), n)
+        res['loop_' + name], res['loop_' + name + '_optimize'] = off, on
+        if not args.no_profile and name != 'mjpeg_420_q100':
+            res['rocprofv3_kernels_' + name + '_optimize'] = profiled_kernels(block['quality'], 40, block.get('sampling', '420' if block['type'] == 'mjpeg' else '444'), True)
+        res['optimize_' + name] = dict(bytes_ratio=on['bytes'] / float(off['bytes']), fps_ratio=on['fps'] / off['fps'],
+                                       jpeg_slot_ms_added=on['jpeg_slot_ms_per_frame'] - off['jpeg_slot_ms_per_frame'])
+    return res
+
+
+def kernels_only(quality, nframes, sampling='444', optimize=False):
     """What the profiled child runs: device-encoded frames, nothing else."""
-    mgr, rdr, gnm, gprof = setup(device_block(quality, sampling))
+    mgr, rdr, gnm, gprof = setup(dict(device_block(quality, sampling), optimize=True) if optimize else device_block(quality, sampling))
     for _ in range(nframes):
         evt, frame = mgr.queue_frame(rdr, gnm, gprof, 0.5)
         evt.synchronize()
     mgr.fb.free()
 
 
-def profiled_kernels(quality, nframes, sampling='444'):
+def profiled_kernels(quality, nframes, sampling='444', optimize=False):
     """Average duration per launch of the JPEG kernels, from rocprofv3's kernel statistics of a child process."""
     out = tempfile.mkdtemp(prefix='jpeg_prof_', dir=os.environ.get('TMPDIR', '/tmp'))
     cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', out, '-o', 'jpeg', '--',
            sys.executable, os.path.abspath(__file__), '--kernels-only', '--quality', str(quality), '--frames', str(nframes),
-           '--sampling', sampling]
+           '--sampling', sampling] + (['--optimize'] if optimize else [])
     subprocess.run(cmd, check=True, env=dict(os.environ, FLAME_LANES='1'), stdout=subprocess.DEVNULL, timeout=600)
     found = glob.glob(os.path.join(out, '**', '*kernel_stats.csv'), recursive=True)
     if not found:
@@ -147,13 +168,14 @@ def main():
     ap.add_argument('--sweep-runs', type=int, default=1, help='repeat the whole sweep this many times (figures become lists)')
     ap.add_argument('--sampling', choices=['444', '420'], default='444', help='chroma sampling of the device stills')
     ap.add_argument('--codec', choices=['jpeg', 'mjpeg'], default='jpeg', help='mjpeg: the Motion-JPEG figures of DESIGN.md 4.10')
+    ap.add_argument('--optimize', action='store_true', help='the figures of DESIGN.md 4.11: every loop with and without output.optimize')
     ap.add_argument('--no-profile', action='store_true', help='skip the rocprofv3 child')
     ap.add_argument('--kernels-only', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.kernels_only:
-        return kernels_only(args.quality, args.frames, args.sampling)
-    if args.codec == 'mjpeg':
-        text = json.dumps(mjpeg(args), indent=1, sort_keys=True)
+        return kernels_only(args.quality, args.frames, args.sampling, args.optimize)
+    if args.codec == 'mjpeg' or args.optimize:
+        text = json.dumps(optimize(args) if args.optimize else mjpeg(args), indent=1, sort_keys=True)
         print(text)
         if args.out:
             with open(args.out, 'w') as f:
