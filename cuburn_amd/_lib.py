@@ -86,7 +86,11 @@ _SIGS = {
     'fl_debug_counters': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fl_rtc_compile_check': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     'fl_debug_apply_xf': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
+    'fl_debug_math': (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# include/flame_hip.h FL_MATH_*
+MATH = dict((n, i) for i, n in enumerate(
+    'rcp div sqrt exp2 log2 exp log pow sin cos tan atan2 sinh cosh fmod fmod_pi trunca hw_sin hw_cos'.split()))
 EXPORTS = sorted(_SIGS)
 
 _lib = None

@@ -1429,6 +1429,24 @@ int fl_debug_apply_xf(fl_ctx *c, fl_genome *g, uint32_t ts, int xfi, uint32_t n,
     return FL_OK;
 }
 
+int fl_debug_math(fl_ctx *c, int fn, uint32_t n, const float *a, const float *b, uint32_t *out_bits)
+{
+    REQUIRE(c && a && b && out_bits, "null argument");
+    REQUIRE(n > 0, "no elements");
+    REQUIRE(fn >= 0 && fn < FL_MATH_COUNT, "unknown math helper");
+    Lane &ln = c->lane();
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf<float> da, db; DevBuf<uint32_t> dout;
+    int rc;
+    if ((rc = da.reserve(n, "math tap scratch")) || (rc = db.reserve(n, "math tap scratch")) || (rc = dout.reserve(n, "math tap scratch"))) return rc;
+    HIPCHK(hipMemcpy(da, a, da.bytes(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, b, db.bytes(), hipMemcpyHostToDevice));
+    launch_math_tap(ln.stream, fn, n, da, db, dout);
+    HIPCHK(hipStreamSynchronize(ln.stream));
+    HIPCHK(hipMemcpy(out_bits, dout, dout.bytes(), hipMemcpyDeviceToHost));
+    return FL_OK;
+}
+
 int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops, int nw, int count, int acc,
                          char *log, size_t log_bytes)
 {

@@ -69,9 +69,14 @@ __device__ __forceinline__ float fpow(float x, float y) { return __builtin_amdgc
 // reference wherever a pixel is empty.  Here the exponent 0 (kernel-uniform) means what it says: w^0 = 1.
 __device__ __forceinline__ float de_pow(float w, float dpow) { return dpow == 0.0f ? 1.0f : fpow(w, dpow); }
 __device__ __forceinline__ float fsqrt(float a) { return __builtin_amdgcn_sqrtf(a); }
-// v_sin/v_cos take revolutions; v_fract keeps the argument in the instruction's valid domain
-__device__ __forceinline__ float fsin(float x) { return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(x * 0.15915494309189532f)); }
-__device__ __forceinline__ float fcos(float x) { return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(x * 0.15915494309189532f)); }
+// v_sin/v_cos take revolutions; v_fract keeps the argument in the instruction's valid domain.  The fraction is taken of |t| (a source
+// modifier) and, for the sine, given t's sign back (one v_bfi_b32): v_fract_f32 of a NEGATIVE t is 1 + t rounded to the 2^-24 grid below
+// 1 — up to 2 pi 2^-24 = 3.7e-7 of angle lost, and fsin(x) = -3.7e-7 for every -1.9e-7 < x < 0 — while the fraction of |t| is exact
+// below one revolution and the sine is odd, the cosine even.  Results for x >= 0 are what they were, bit for bit.  Accuracy against
+// float64 (measured on an MI355X, DESIGN.md "Accuracy of the lean math"; tests/test_gpu_lean_math.py): the instructions are good to
+// 1.26e-7 absolute, the float32 product x / 2 pi adds 2^-23 |x|.
+__device__ __forceinline__ float fsin(float x) { const float t = x * 0.15915494309189532f; return __builtin_amdgcn_sinf(copysignf(__builtin_amdgcn_fractf(fabsf(t)), t)); }
+__device__ __forceinline__ float fcos(float x) { return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(fabsf(x * 0.15915494309189532f))); }
 __device__ __forceinline__ float ftan(float x) { return fsin(x) * frcp(fcos(x)); }
 
 // cvt.rni.s32.f32 (cuburn/code/util.py:194-200): round-to-nearest-even, saturating, NaN -> 0

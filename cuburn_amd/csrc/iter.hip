@@ -985,6 +985,45 @@ void launch_apply_xf_tap(hipStream_t st, const int32_t *prog, const float *param
     hipLaunchKernelGGL(k_apply_xf_tap, dim3((n + 255) / 256), dim3(256), 0, st, prog, params, ts, xfi, n, pts, rng);
 }
 
+// Math tap: one helper of flame_device.h / variations.h per launch (fn is launch-uniform), one element per thread, the raw bits
+// of the result out.  Compiled here, with this file's flags, so that the helpers are the ones the iterate kernels run.
+__global__ void __launch_bounds__(256)
+k_math_tap(int fn, uint32_t n, const float *__restrict__ a, const float *__restrict__ b, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float x = a[i], y = b[i];
+    float r = 0.0f;
+    switch (fn) {
+    case FL_MATH_RCP: r = frcp(x); break;
+    case FL_MATH_DIV: r = fdiv(x, y); break;
+    case FL_MATH_SQRT: r = fsqrt(x); break;
+    case FL_MATH_EXP2: r = fexp2(x); break;
+    case FL_MATH_LOG2: r = flog2(x); break;
+    case FL_MATH_EXP: r = fexp(x); break;
+    case FL_MATH_LOG: r = flog(x); break;
+    case FL_MATH_POW: r = fpow(x, y); break;
+    case FL_MATH_SIN: r = fsin(x); break;
+    case FL_MATH_COS: r = fcos(x); break;
+    case FL_MATH_TAN: r = ftan(x); break;
+    case FL_MATH_ATAN2: r = v_atan2(x, y); break;
+    case FL_MATH_SINH: r = v_sinh(x); break;
+    case FL_MATH_COSH: r = v_cosh(x); break;
+    case FL_MATH_FMOD: r = v_fmod(x, y); break;
+    case FL_MATH_FMOD_PI: r = v_fmod_pi(x); break;
+    case FL_MATH_TRUNCA: out[i] = trunca(x); return;
+    case FL_MATH_HW_SIN: r = __builtin_amdgcn_sinf(x); break;
+    case FL_MATH_HW_COS: r = __builtin_amdgcn_cosf(x); break;
+    default: break;
+    }
+    out[i] = __float_as_uint(r);
+}
+
+void launch_math_tap(hipStream_t st, int fn, uint32_t n, const float *a, const float *b, uint32_t *out)
+{
+    hipLaunchKernelGGL(k_math_tap, dim3((n + 255) / 256), dim3(256), 0, st, fn, n, a, b, out);
+}
+
 // Point-shuffle tap: one swap of the identity payload, for the bit-exact permutation test.
 template <int NW>
 __global__ void __launch_bounds__(NW * 64) k_shuffle_tap(uint32_t *out, uint32_t round)

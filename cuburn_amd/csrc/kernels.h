@@ -38,6 +38,7 @@ void launch_clear_frame(hipStream_t st, float4 *front, u64 *atom, uint32_t *hot,
 void launch_shuffle_tap(hipStream_t st, int nw, uint32_t *out, uint32_t round);
 void launch_apply_xf_tap(hipStream_t st, const int32_t *prog, const float *params, uint32_t ts, int xfi,
                          uint32_t n, float4 *pts, fl_mwc *rng);
+void launch_math_tap(hipStream_t st, int fn, uint32_t n, const float *a, const float *b, uint32_t *out);
 
 // rtc.hip: structure of a genome as the run-time specialised iterate kernel needs it (include/flame_hip.h (5))
 #include <string>

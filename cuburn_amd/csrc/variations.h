@@ -16,12 +16,17 @@
 // atan2(a, b) in ~24 instructions (the device library's atan2f is 38: it divides through frexp / ldexp so that the quotient
 // survives operands near the ends of the float range, and sorts out zeros and infinities one compare at a time; the reference's is
 // CUDA's library function under -use_fast_math, 2-3 ulp).  min / max -> one hardware reciprocal -> atan(q) = q + q^3 P(q^2) on [0, 1]
-// (own least-squares minimax fit, degree 6 in q^2: 1.2e-7 absolute, 2.9e-7 relative in float arithmetic) -> octant fix-ups.
-// atan2(0, 0) = 0; NaN in, NaN out; both operands infinite gives NaN (such a point is discarded by the caller either way).
-// Ranges the lean forms do NOT cover (the tests' CPU restatement takes libm's answer there; such points lie outside any picture, and a walker
-// that reaches them is re-seeded within a few rounds): v_atan2 with max(|a|, |b|) > 2^126 — the reciprocal is a denormal, flushed: the
-// angle comes out as 0 or pi/2 — or with BOTH operands denormal (the FLT_MIN clamp); v_fmod with |b| > 2^126 (one subtraction
-// where up to three may be needed); v_fmod_pi next to multiples of pi, where the result may be a few ulp of pi below 0 or at pi.
+// (own least-squares minimax fit, degree 6 in q^2: 1.2e-7 absolute as a polynomial) -> octant fix-ups.  In float arithmetic, with the
+// reciprocal's ulp and the rounding of pi/2 - r and pi - r, the whole function stays within 3.8e-7 absolute of float64's atan2 and,
+// in the first octant, within 4.8e-7 relative (tests/lean_math_model.py restates it operation for operation: 3.77e-7 and 4.71e-7
+// over its input sets; an MI355X measures 3.2e-7 and 3.8e-7; the tests' bar is 6e-7 for both).
+// atan2(+-0, +-0) = +-0 (a's sign, whatever b's); NaN in, NaN out; both operands infinite gives NaN (such a point is discarded by the
+// caller either way).
+// Ranges the lean forms do NOT cover (the CPU restatement of the tests, tests/lean_math_model.py, takes libm's answer there and marks
+// them; such points lie outside any picture, and a walker that reaches them is re-seeded within a few rounds): v_atan2 with
+// max(|a|, |b|) > 2^126 — the reciprocal is a denormal, flushed: the angle comes out as 0 or pi/2 — or with BOTH operands denormal
+// (the FLT_MIN clamp); v_fmod with |b| > 2^126 (one subtraction where up to three may be needed; an infinite b gives NaN, not a);
+// v_fmod_pi next to multiples of pi, where the result may be a few ulp of pi below 0 or at pi.
 // -DFL_LIBM_MATH (through FLAME_RTC_FLAGS) compiles the device library's functions back in.
 #ifndef FL_LIBM_MATH
 __device__ __forceinline__ float v_atan2(float a, float b)
@@ -48,15 +53,19 @@ __device__ __forceinline__ float v_atan2(float a, float b) { return atan2f(a, b)
 // CUDA's library functions over ex2.approx under -use_fast_math).  h = e^|x| / 2 from ONE v_exp_f32 (the halving in the exponent, so that
 // nothing overflows before the result does), cosh = h + 1/(4h), sinh = h - 1/(4h); below |x| = 0.5, where that difference cancels, the
 // odd series to x^9 / 9! (next term 1.2e-11 relative).  The thirteen trigonometric / hyperbolic variations (sin .. coth) call both.
+// The exponent |x| log2 e - 1 takes log2 e in two floats (FM_LOG2E + V_LOG2E_LO; one more fma): the float32 constant alone is 1.93e-8
+// short, which the exponential turns into 0.22 |x| 2^-24 of the result — 19 ulp at |x| = 88.  With it both stay within
+// (8 + |x|) 2^-24 relative of float64 up to |x| = 88 (the |x| term: the rounding of the exponent itself; tests/lean_math_model.py).
+#define V_LOG2E_LO 1.925963e-8f
 #ifndef FL_LIBM_MATH
 __device__ __forceinline__ float v_cosh(float x)
 {
-    const float h = fexp2(fmaf(fabsf(x), FM_LOG2E, -1.0f));
+    const float ax = fabsf(x), h = fexp2(fmaf(ax, FM_LOG2E, fmaf(ax, V_LOG2E_LO, -1.0f)));
     return fmaf(0.25f, frcp(h), h);
 }
 __device__ __forceinline__ float v_sinh(float x)
 {
-    const float ax = fabsf(x), h = fexp2(fmaf(ax, FM_LOG2E, -1.0f));
+    const float ax = fabsf(x), h = fexp2(fmaf(ax, FM_LOG2E, fmaf(ax, V_LOG2E_LO, -1.0f)));
     const float big = fmaf(-0.25f, frcp(h), h), x2 = x * x;
     float p = fmaf(x2, 2.7557319e-6f, 1.9841270e-4f);
     p = fmaf(x2, p, 8.3333333e-3f);

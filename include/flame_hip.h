@@ -447,6 +447,19 @@ int fl_debug_shuffle(fl_ctx *ctx, uint32_t round, uint32_t *out256);
 /* Xform tap: apply xform `xfi` (nxf = the final xform) of temporal sample `ts` once to n points
  * {x, y, color, unused} with one RNG state each; results overwrite the inputs. */
 int fl_debug_apply_xf(fl_ctx *ctx, fl_genome *g, uint32_t ts, int xfi, uint32_t n, float *xyzw, fl_mwc *rng);
+/* Math tap: out_bits[i] = the raw 32 bits of device helper `fn` applied to a[i] (and b[i]; unary helpers ignore b, which must
+ * still point at n floats), compiled with the iterate kernels' flags.  The helpers are those of csrc/flame_device.h and
+ * csrc/variations.h: ATAN2 is v_atan2(a, b), FMOD v_fmod(a, b), POW fpow(a, b), DIV fdiv(a, b); TRUNCA returns its integer;
+ * HW_SIN / HW_COS are the bare sine / cosine instructions on an argument in revolutions, without the range reduction. */
+enum {
+    FL_MATH_RCP = 0, FL_MATH_DIV, FL_MATH_SQRT, FL_MATH_EXP2, FL_MATH_LOG2, FL_MATH_EXP, FL_MATH_LOG, FL_MATH_POW,
+    FL_MATH_SIN, FL_MATH_COS, FL_MATH_TAN,
+    FL_MATH_ATAN2, FL_MATH_SINH, FL_MATH_COSH, FL_MATH_FMOD, FL_MATH_FMOD_PI,
+    FL_MATH_TRUNCA,
+    FL_MATH_HW_SIN, FL_MATH_HW_COS,
+    FL_MATH_COUNT
+};
+int fl_debug_math(fl_ctx *ctx, int fn, uint32_t n, const float *a, const float *b, uint32_t *out_bits);
 /* Compile (only) the iterate kernel specialised for a genome structure, as fl_iterate does on a genome's
  * first launch — the counterpart of cuburn/render.py:232-236 Renderer.compile.  Needs libhiprtc but no
  * GPU; FL_E_UNSUPPORTED if hipRTC is not installed.  nw = 4 | 8 | 16, acc = 0 (atomic), 1 / 3 (binned narrow / wide);

@@ -21,6 +21,7 @@ import pytest
 from common import O, prepare, mwc
 from cuburn_amd import configs, profile, render, _lib
 from cuburn_amd.genome import variations as V
+import variation_branch_cases as B
 
 pytestmark = pytest.mark.gpu
 N = 4096
@@ -44,35 +45,10 @@ def genome_for(name):
     }
 
 
-@pytest.mark.parametrize('name', sorted(V.var_ids, key=lambda n: V.var_ids[n]))
-def test_variation_matches_oracle(mgr, name):
-    lib = _lib.load()
-    gnm = genome_for(name)
-    prof = {'width': 64, 'height': 64, 'spp': 1, 'fps': 1, 'duration': 1, 'frame_width': 0}
-    gprof = profile.wrap(prof, gnm)
-    rdr = render.Renderer(gnm, gprof)
-    g = rdr._handle(mgr.fb)
-    mgr._copy(rdr, gnm)
-    _lib.check(lib.fl_interp(mgr.fb.ctx, g, 64, 64, 0.5, 0.0))
-    params = mgr.fb.read('params', (mgr.fb.nslots, rdr.packer.pstride), np.float32, g)
-
-    rs = np.random.RandomState(V.var_ids[name])
-    pts = np.zeros((N, 4), np.float32)
-    pts[:, 0] = rs.uniform(-1.5, 1.5, N)
-    pts[:, 1] = rs.uniform(-1.5, 1.5, N)
-    pts[:, 2] = rs.uniform(0, 1, N)
-    rng = mwc.make_seeds(N, 99)
-    dev_pts, dev_rng = pts.copy(), rng.copy()
-    _lib.check(lib.fl_debug_apply_xf(mgr.fb.ctx, g, 5, 0, N, dev_pts.ctypes.data, dev_rng.ctypes.data))
-
-    L = O.lib()
-    L.ref_apply_xf.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    ref_pts, ref_rng = pts.copy(), rng.copy()
-    P = params[5]
-    # one oracle call for all points (a ctypes call per point was a tenth of the GPU suite's time)
-    L.ref_apply_xf_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
-    assert L.ref_apply_xf_n(rdr.packer.prog.ctypes.data, P.ctypes.data, 0, N, ref_pts.ctypes.data, ref_rng.ctypes.data) == 0
-
+def assert_matches_oracle(name, L, prog, P, pts, rng, dev_pts, dev_rng, ref_pts, ref_rng):
+    """The acceptance rule of this file (module docstring): RNG and colour exact, every point within the plain tolerance of the
+    oracle's or explained by the oracle's own spread over the inputs within 6 ulp, and at most 1.5 % of the points the latter."""
+    N = len(pts)
     assert np.array_equal(dev_rng, ref_rng), 'RNG draws differ'
     assert np.array_equal(dev_pts[:, 2], ref_pts[:, 2]), 'colour blend differs'
     d, r = dev_pts[:, :2].astype(np.float64), ref_pts[:, :2].astype(np.float64)
@@ -105,7 +81,7 @@ def test_variation_matches_oracle(mgr, name):
             for dv in range(-6, 7, 2):
                 x, y, c = C.c_float(step(pts[i, 0], du)), C.c_float(step(pts[i, 1], dv)), C.c_float(pts[i, 2])
                 st = rng[i:i + 1].copy()
-                assert L.ref_apply_xf(rdr.packer.prog.ctypes.data, P.ctypes.data, 0, C.byref(x), C.byref(y), C.byref(c), st.ctypes.data) == 0
+                assert L.ref_apply_xf(prog.ctypes.data, P.ctypes.data, 0, C.byref(x), C.byref(y), C.byref(c), st.ctypes.data) == 0
                 outs.append((x.value, y.value))
         outs = np.array(outs, np.float64)
         if not np.isfinite(outs).all() or np.abs(outs).max() >= 1e6:
@@ -124,6 +100,63 @@ def test_variation_matches_oracle(mgr, name):
             unexplained.append(int(i))
     assert not unexplained, (name, 'points off the oracle at a well-conditioned input', unexplained[:5],
                              pts[unexplained[:3]], d[unexplained[:3]], r[unexplained[:3]])
+
+
+@pytest.mark.parametrize('name', sorted(V.var_ids, key=lambda n: V.var_ids[n]))
+def test_variation_matches_oracle(mgr, name):
+    lib = _lib.load()
+    gnm = genome_for(name)
+    prof = {'width': 64, 'height': 64, 'spp': 1, 'fps': 1, 'duration': 1, 'frame_width': 0}
+    gprof = profile.wrap(prof, gnm)
+    rdr = render.Renderer(gnm, gprof)
+    g = rdr._handle(mgr.fb)
+    mgr._copy(rdr, gnm)
+    _lib.check(lib.fl_interp(mgr.fb.ctx, g, 64, 64, 0.5, 0.0))
+    params = mgr.fb.read('params', (mgr.fb.nslots, rdr.packer.pstride), np.float32, g)
+
+    rs = np.random.RandomState(V.var_ids[name])
+    pts = np.zeros((N, 4), np.float32)
+    pts[:, 0] = rs.uniform(-1.5, 1.5, N)
+    pts[:, 1] = rs.uniform(-1.5, 1.5, N)
+    pts[:, 2] = rs.uniform(0, 1, N)
+    rng = mwc.make_seeds(N, 99)
+    dev_pts, dev_rng = pts.copy(), rng.copy()
+    _lib.check(lib.fl_debug_apply_xf(mgr.fb.ctx, g, 5, 0, N, dev_pts.ctypes.data, dev_rng.ctypes.data))
+
+    L = O.lib()
+    L.ref_apply_xf.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    ref_pts, ref_rng = pts.copy(), rng.copy()
+    P = params[5]
+    # one oracle call for all points (a ctypes call per point was a tenth of the GPU suite's time)
+    L.ref_apply_xf_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+    assert L.ref_apply_xf_n(rdr.packer.prog.ctypes.data, P.ctypes.data, 0, N, ref_pts.ctypes.data, ref_rng.ctypes.data) == 0
+
+    assert_matches_oracle(name, L, rdr.packer.prog, P, pts, rng, dev_pts, dev_rng, ref_pts, ref_rng)
+
+
+@pytest.mark.parametrize('index', range(len(B.CASES)), ids=[c['id'] for c in B.CASES])
+def test_variation_branches_match_oracle(mgr, index):
+    """The branches of the variations that parameters, the sign of the weight or the range of the point select
+    (tests/variation_branch_cases.py: each case reaches its branches and stays under the neighbourhood cap by the oracle alone,
+    tests/test_cpu_variation_branches.py), device against oracle by the rule of test_variation_matches_oracle."""
+    lib = _lib.load()
+    case = B.CASES[index]
+    gnm = B.genome_for(case)
+    gprof = profile.wrap(B.PROFILE, gnm)
+    rdr = render.Renderer(gnm, gprof)
+    g = rdr._handle(mgr.fb)
+    mgr._copy(rdr, gnm)
+    _lib.check(lib.fl_interp(mgr.fb.ctx, g, 64, 64, 0.5, 0.0))
+    P = mgr.fb.read('params', (mgr.fb.nslots, rdr.packer.pstride), np.float32, g)[5]
+    pts, rng = B.inputs(case, index)
+    dev_pts, dev_rng = pts.copy(), rng.copy()
+    _lib.check(lib.fl_debug_apply_xf(mgr.fb.ctx, g, 5, 0, len(pts), dev_pts.ctypes.data, dev_rng.ctypes.data))
+    L = O.lib()
+    L.ref_apply_xf.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.ref_apply_xf_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+    ref_pts, ref_rng = pts.copy(), rng.copy()
+    assert L.ref_apply_xf_n(rdr.packer.prog.ctypes.data, P.ctypes.data, 0, len(pts), ref_pts.ctypes.data, ref_rng.ctypes.data) == 0
+    assert_matches_oracle(case['id'], L, rdr.packer.prog, P, pts, rng, dev_pts, dev_rng, ref_pts, ref_rng)
 
 
 def _ref_cases():
