@@ -1117,13 +1117,17 @@ int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_ou
 // ---- PNG ----
 // No file can be longer: every segment stored is its bytes and 5 of block header, in an IDAT of 12; the first IDAT also holds the
 // 2 bytes of the zlib header and the last the Adler-32; IEND is 12.  A dynamic segment is only chosen where it is smaller.
-size_t fl_png_bound(uint32_t w, uint32_t h, int channels)
+// Rows of 1 + w * channels * bits / 8 bytes; the filter choice changes no size.  (A frame over the limit at 8 bits is over it at 16.)
+size_t fl_png_bound_f(uint32_t w, uint32_t h, int channels, int bits, unsigned flags)
 {
     if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4)) return 0;
-    const uint64_t F = (uint64_t)h * (1u + (uint64_t)w * (uint32_t)channels), seg = png_segment_bytes();
+    if ((bits != 8 && bits != 16) || (flags & ~(unsigned)FL_PNG_ADAPTIVE)) return 0;
+    const uint64_t F = (uint64_t)h * (1u + (uint64_t)w * (uint32_t)(channels * bits / 8)), seg = png_segment_bytes();
     const uint64_t n = 16u + FL_PNG_HEADER_BYTES + 2u + F + 17u * ((F + seg - 1u) / seg) + 4u + 12u;
     return n > 0xffffffffull ? 0 : (size_t)n;
 }
+
+size_t fl_png_bound(uint32_t w, uint32_t h, int channels) { return fl_png_bound_f(w, h, channels, 8, 0u); }
 
 static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap)
 {
@@ -1133,30 +1137,54 @@ static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, cons
     return FL_OK;
 }
 
-static int png_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels,
+// What the _f entry points refuse beyond check_png (and, in fl_png_encode_f, the null source), after those
+static int check_png_f(uint32_t w, uint32_t h, int channels, int bits, unsigned flags)
+{
+    REQUIRE(bits == 8 || bits == 16, "png: bits must be 8 or 16");
+    REQUIRE(!(flags & ~(unsigned)FL_PNG_ADAPTIVE), "png: unknown flag");
+    REQUIRE(fl_png_bound_f(w, h, channels, bits, flags) != 0, "png: the file could pass 2^32 - 1 bytes");
+    return FL_OK;
+}
+
+static int png_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels, int bits, unsigned flags,
                          void *host_out, uint64_t dev_out, size_t cap)
 {
     const uint32_t seg = png_segment_bytes();
-    return encode_on(c, ln, host_out, dev_out, cap, fl_png_bound(w, h, channels), png_layout(w, h, channels, seg).words, "png file", "png scratch",
-                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_png_encode(st, src, w, h, channels, seg, scratch, dst, cap); });
+    return encode_on(c, ln, host_out, dev_out, cap, fl_png_bound_f(w, h, channels, bits, flags), png_layout(w, h, channels, seg, bits, flags).words,
+                     "png file", "png scratch", [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) {
+                         launch_png_encode(st, src, w, h, channels, bits, flags, seg, scratch, dst, cap);
+                     });
+}
+
+int fl_png_encode_f(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags, void *host_out, uint64_t dev_out,
+                    size_t cap)
+{
+    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "png: null source pixels");
+    if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return png_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, host_out, dev_out, cap);
 }
 
 int fl_png_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
 {
+    return fl_png_encode_f(c, w, h, src_dev, channels, 8, 0u, host_out, dev_out, cap);
+}
+
+int fl_output_png_f(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, void *host_out, uint64_t dev_out, size_t cap)
+{
     if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "png: null source pixels");
+    if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    return png_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, host_out, dev_out, cap);
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
 }
 
 int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return fl_output_png_f(c, w, h, channels, 8, 0u, host_out, dev_out, cap);
 }
 
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,

@@ -116,14 +116,15 @@ JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling);
 void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling, bool optimize,
                         uint32_t *scratch, unsigned char *out, size_t cap);
 
-// png.hip: 8-bit truecolour PNG from u8 [h][w][4] (channels 3: the alpha byte is left out).  `scratch` holds png_layout().words words; the
-// 16-byte record, signature + IHDR, one IDAT per segment and IEND go to `out`, of which nothing at or beyond `cap`
-// (>= 16 + FL_PNG_HEADER_BYTES) is touched.  seg: filtered bytes per segment, a multiple of 16 in [8192, 32768].
+// png.hip: truecolour PNG of 8 or 16 bits a sample from u8 or u16 [h][w][4] (channels 3: the alpha sample is left out).  `scratch` holds
+// png_layout().words words; the 16-byte record, signature + IHDR, one IDAT per segment and IEND go to `out`, of which nothing at or
+// beyond `cap` (>= 16 + FL_PNG_HEADER_BYTES) is touched.  seg: filtered bytes per segment, a multiple of 16 in [8192, 32768].
+// flags: FL_PNG_ADAPTIVE chooses every row's filter type (the table of types is the layout's last part); without it every row is Paeth.
 #define FL_PNG_SEG 32768u      // the default: the largest whose bit buffer leaves a workgroup under 64 KiB of LDS
-struct PngLayout { uint32_t rowlen, nseg, stride, per; uint64_t F; size_t filt, segbuf, offs, lens, adl, info, words; };      // bytes per filtered row, segments, bytes between coded segments, bytes per lane, filtered bytes; word offsets into the scratch
+struct PngLayout { uint32_t rowlen, nseg, stride, per; uint64_t F; size_t filt, segbuf, offs, lens, adl, info, types, words; };      // bytes per filtered row, segments, bytes between coded segments, bytes per lane, filtered bytes; word offsets into the scratch
 uint32_t png_segment_bytes();      // FL_PNG_SEG, or FLAME_PNG_SEG (measurements only)
-PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg);
-void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, uint32_t seg,
+PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg, int bits, unsigned flags);
+void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
                        uint32_t *scratch, unsigned char *out, size_t cap);
 
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)

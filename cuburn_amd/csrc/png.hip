@@ -1,6 +1,8 @@
-// png.hip — 8-bit truecolour PNG (colour type 2 or 6, not interlaced) from u8 [h][w][4] on the device.  DESIGN.md §4.9.
-// Four launches per frame, no host wait between them:
-//   k_png_filter    the Paeth filter on every row: pixels -> the filtered byte stream (a filter byte 4, then w * channels residuals per row)
+// png.hip — truecolour PNG (colour type 2 or 6, not interlaced; 8 or 16 bits a sample) from u8 or u16 [h][w][4] on the device.  DESIGN.md §4.9.
+// Four launches per frame (five with FL_PNG_ADAPTIVE), no host wait between them:
+//   k_png_choose    FL_PNG_ADAPTIVE only, one workgroup per row: the row's cost under each of the five filter types -> its type
+//   k_png_filter    the Paeth filter on every row: pixels -> the filtered byte stream (a filter byte 4, then w * channels residuals per row);
+//   k_png_filter_x  the same for 16-bit samples (most significant byte first) and for rows of chosen types
 //   k_png_segment   one workgroup per segment of `seg` filtered bytes, coded with no reference before its start: tokens (literal / run
 //                   of distance 1) -> histogram -> length-limited Huffman code -> one dynamic block packed in LDS, or one stored block
 //                   when that is no smaller (decided from the counted bits, before anything is emitted); the segment's Adler-32 parts
@@ -50,6 +52,102 @@ k_png_filter(const unsigned char *__restrict__ src, uint32_t w, uint32_t rowlen,
         }
         out |= v << (8u * k);
         if (++col == rowlen) { col = 0; ++row; }
+    }
+    filt[p0 >> 2] = out;
+}
+
+// ---- 16-bit samples and the per-row filter choice (FL_PNG_ADAPTIVE) -----------------------------------------------------
+// Byte cp (0 .. CH * BITS / 8 - 1) of the pixel at pix (u8 or u16 [4], native byte order): the file holds a 16-bit sample most
+// significant byte first.
+template <int BITS>
+__device__ __forceinline__ int sample_byte(const unsigned char *pix, uint32_t cp)
+{
+    if (BITS == 8) return pix[cp];
+    return ((const unsigned short *)pix)[cp >> 1] >> (8u * (1u - (cp & 1u))) & 0xffu;
+}
+
+// What filter type ft (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) predicts from the bytes to the left, above and above left
+__device__ __forceinline__ uint32_t predict(uint32_t ft, int a, int b, int c)
+{
+    return ft == 0 ? 0u : ft == 1 ? (uint32_t)a : ft == 2 ? (uint32_t)b : ft == 3 ? (uint32_t)(a + b) >> 1 : paeth(a, b, c);
+}
+
+// One workgroup per row, a thread per pixel (and per 256th pixel behind it): cost[t] = the sum over the row's residual bytes r under
+// filter type t of min(r, 256 - r), exact in 32 bits (at most 65535 * 8 * 128); types[row] = the smallest t of minimal cost.
+template <int CH, int BITS>
+__global__ void __launch_bounds__(256)
+k_png_choose(const unsigned char *__restrict__ src, uint32_t w, unsigned char *__restrict__ types)
+{
+    constexpr uint32_t BPP = CH * BITS / 8, PIX = 4 * BITS / 8;
+    __shared__ uint32_t s_cost[4][5];
+    const uint32_t t = threadIdx.x, row = blockIdx.x;
+    const size_t pitch = (size_t)w * PIX;
+    const unsigned char *line = src + (size_t)row * pitch;
+    uint32_t cost[5] = {0, 0, 0, 0, 0};
+    for (uint32_t px = t; px < w; px += 256u) {
+        const unsigned char *s = line + (size_t)px * PIX;
+#pragma unroll
+        for (uint32_t cp = 0; cp < BPP; ++cp) {
+            const int x = sample_byte<BITS>(s, cp);
+            const int a = px ? sample_byte<BITS>(s - PIX, cp) : 0, b = row ? sample_byte<BITS>(s - pitch, cp) : 0;
+            const int c = px && row ? sample_byte<BITS>(s - pitch - PIX, cp) : 0;
+#pragma unroll
+            for (uint32_t ft = 0; ft < 5; ++ft) {
+                const uint32_t r = ((uint32_t)x - predict(ft, a, b, c)) & 0xffu;
+                cost[ft] += min(r, 256u - r);
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t ft = 0; ft < 5; ++ft) {
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) cost[ft] += __shfl_xor(cost[ft], d, 64);
+    }
+    if ((t & 63u) == 0) {
+#pragma unroll
+        for (uint32_t ft = 0; ft < 5; ++ft) s_cost[t >> 6][ft] = cost[ft];
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t best = 0, least = 0xffffffffu;
+        for (uint32_t ft = 0; ft < 5; ++ft) {
+            const uint32_t v = s_cost[0][ft] + s_cost[1][ft] + s_cost[2][ft] + s_cost[3][ft];
+            if (v < least) { least = v; best = ft; }          // (a tie keeps the lower type)
+        }
+        types[row] = (unsigned char)best;
+    }
+}
+
+// k_png_filter for the other forms: 16-bit samples, and rows whose type comes from `types` (ADAPT) instead of being Paeth.
+// The same thread per four bytes of the stream; rowlen = 1 + w * CH * BITS / 8.
+template <int CH, int BITS, bool ADAPT>
+__global__ void __launch_bounds__(256)
+k_png_filter_x(const unsigned char *__restrict__ src, uint32_t w, uint32_t rowlen, uint32_t F, const unsigned char *__restrict__ types,
+               uint32_t *__restrict__ filt)
+{
+    constexpr uint32_t BPP = CH * BITS / 8, PIX = 4 * BITS / 8;
+    const u64 p64 = ((u64)blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (p64 >= F) return;
+    const uint32_t p0 = (uint32_t)p64;
+    uint32_t row = p0 / rowlen, col = p0 - row * rowlen, out = 0;
+    const size_t pitch = (size_t)w * PIX;
+    uint32_t ft = ADAPT ? types[row] : 4u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (p64 + k >= F) break;
+        uint32_t v = ft;                                      // the row's filter byte
+        if (col) {
+            const uint32_t x = col - 1u, px = x / BPP, cp = x - px * BPP;
+            const unsigned char *s = src + (size_t)row * pitch + (size_t)px * PIX;
+            const int a = px ? sample_byte<BITS>(s - PIX, cp) : 0, b = row ? sample_byte<BITS>(s - pitch, cp) : 0;
+            const int c = px && row ? sample_byte<BITS>(s - pitch - PIX, cp) : 0;
+            v = ((uint32_t)sample_byte<BITS>(s, cp) - (ADAPT ? predict(ft, a, b, c) : paeth(a, b, c))) & 0xffu;
+        }
+        out |= v << (8u * k);
+        if (++col == rowlen) {
+            col = 0; ++row;
+            if (ADAPT && p64 + k + 1u < F) ft = types[row];   // (row < h while a byte of the stream is left)
+        }
     }
     filt[p0 >> 2] = out;
 }
@@ -454,15 +552,15 @@ uint32_t png_segment_bytes()
     return seg;
 }
 
-PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg)
+PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg, int bits, unsigned flags)
 {
     PngLayout l;
-    l.rowlen = 1u + w * (uint32_t)channels;
+    l.rowlen = 1u + w * (uint32_t)(channels * bits / 8);
     l.F = (uint64_t)l.rowlen * h;
     l.nseg = (uint32_t)((l.F + seg - 1u) / seg);
     l.stride = seg + 16u;                                     // a stored segment is seg + 5 bytes; rows of the scratch stay 16-byte aligned
     l.per = 16u * ((seg + 4095u) / 4096u);
-    // words: the filtered stream (read in 16-byte pieces) | the coded segments | offsets (u64) | lengths | Adler parts | info
+    // words: the filtered stream (read in 16-byte pieces) | the coded segments | offsets (u64) | lengths | Adler parts | info | the rows' filter types (FL_PNG_ADAPTIVE)
     l.filt = 0;
     l.segbuf = l.filt + (size_t)((l.F + 15u) / 16u) * 4u + 4u;
     l.offs = l.segbuf + (size_t)l.nseg * (l.stride / 4u);
@@ -470,18 +568,29 @@ PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg)
     l.lens = l.offs + 2u * (size_t)l.nseg;
     l.adl = l.lens + l.nseg;
     l.info = l.adl + l.nseg;
-    l.words = l.info + 4u;
+    l.types = l.info + 4u;
+    l.words = l.types + (flags & FL_PNG_ADAPTIVE ? (h + 3u) / 4u : 0u);
     return l;
 }
 
-void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, uint32_t seg,
+// The filter stage with FL_PNG_ADAPTIVE: the choice of every row's type, then the filter that reads it.
+template <int CH, int BITS>
+static void launch_png_adaptive(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, const PngLayout &l, dim3 fgrid,
+                                unsigned char *types, uint32_t *filt)
+{
+    hipLaunchKernelGGL((k_png_choose<CH, BITS>), dim3(h), dim3(256), 0, st, src, w, types);
+    hipLaunchKernelGGL((k_png_filter_x<CH, BITS, true>), fgrid, dim3(256), 0, st, src, w, l.rowlen, (uint32_t)l.F, (const unsigned char *)types, filt);
+}
+
+void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
                        uint32_t *scratch, unsigned char *out, size_t cap)
 {
-    const PngLayout l = png_layout(w, h, channels, seg);
+    const PngLayout l = png_layout(w, h, channels, seg, bits, flags);
     const uint32_t F = (uint32_t)l.F;                         // (the callers refuse frames whose stream passes 2^32 - 1 bytes)
     uint32_t *filt = scratch + l.filt, *lens = scratch + l.lens, *adl = scratch + l.adl, *info = scratch + l.info;
-    unsigned char *segbuf = (unsigned char *)(scratch + l.segbuf);
+    unsigned char *segbuf = (unsigned char *)(scratch + l.segbuf), *types = (unsigned char *)(scratch + l.types);
     u64 *offs = (u64 *)(scratch + l.offs);
+    const bool adaptive = flags & FL_PNG_ADAPTIVE;
     PngHeaderArg hdr = {};
     unsigned char *p = hdr.b;
     const unsigned char sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
@@ -490,13 +599,23 @@ void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uin
     unsigned char *ihdr = p;
     for (const unsigned char c : {'I', 'H', 'D', 'R'}) *p++ = c;
     put32(p, w); put32(p, h);
-    *p++ = 8; *p++ = channels == 4 ? 6 : 2; *p++ = 0; *p++ = 0; *p++ = 0;      // 8 bit, truecolour (with alpha), deflate, adaptive filtering, not interlaced
+    *p++ = (unsigned char)bits; *p++ = channels == 4 ? 6 : 2; *p++ = 0; *p++ = 0; *p++ = 0;      // 8 or 16 bit, truecolour (with alpha), deflate, adaptive filtering, not interlaced
     put32(p, crc32_host(ihdr, 17));
     static_assert(FL_PNG_HEADER_BYTES == 8 + 12 + 13, "header layout");
     const uint32_t nthreads4 = (uint32_t)((l.F + 3u) / 4u);
     const dim3 fgrid((nthreads4 + 255u) / 256u);
-    if (channels == 4) hipLaunchKernelGGL(k_png_filter<4>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
-    else hipLaunchKernelGGL(k_png_filter<3>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
+    if (adaptive) {
+        if (bits == 8 && channels == 4) launch_png_adaptive<4, 8>(st, src, w, h, l, fgrid, types, filt);
+        else if (bits == 8) launch_png_adaptive<3, 8>(st, src, w, h, l, fgrid, types, filt);
+        else if (channels == 4) launch_png_adaptive<4, 16>(st, src, w, h, l, fgrid, types, filt);
+        else launch_png_adaptive<3, 16>(st, src, w, h, l, fgrid, types, filt);
+    } else if (bits == 8) {                                   // the form every file had before there were others: its own kernels
+        if (channels == 4) hipLaunchKernelGGL(k_png_filter<4>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
+        else hipLaunchKernelGGL(k_png_filter<3>, fgrid, dim3(256), 0, st, src, w, l.rowlen, F, filt);
+    } else {
+        if (channels == 4) hipLaunchKernelGGL((k_png_filter_x<4, 16, false>), fgrid, dim3(256), 0, st, src, w, l.rowlen, F, (const unsigned char *)nullptr, filt);
+        else hipLaunchKernelGGL((k_png_filter_x<3, 16, false>), fgrid, dim3(256), 0, st, src, w, l.rowlen, F, (const unsigned char *)nullptr, filt);
+    }
     hipLaunchKernelGGL(k_png_segment, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 8u) / 4u + 2u), st, (const unsigned char *)filt, F, seg,
                        l.nseg, l.per, segbuf, l.stride, lens, adl);
     hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(1024), 0, st, lens, adl, l.nseg, seg, F, offs, info, out, (u64)cap, hdr);

@@ -203,21 +203,37 @@ class DeviceJPEGOutput(DeviceEncodedOutput):
 
 
 class DevicePNGOutput(DeviceEncodedOutput):
-    """PNG stills encoded on the device (``output: {"type": "png", "encoder": "device", "alpha": bool}``): an 8-bit truecolour
-    file, Paeth-filtered and deflated in independent segments (include/flame_hip.h, fl_output_png).  The record's parameter is
-    the segment's bytes."""
+    """PNG stills encoded on the device (``output: {"type": "png", "encoder": "device", "alpha": bool, "bits": 8 | 16,
+    "filter": "paeth" | "adaptive"}``): a truecolour file, filtered and deflated in independent segments (include/flame_hip.h,
+    fl_output_png and fl_output_png_f).  ``bits``: 16 writes the samples of the 16-bit outputs (tiff, raw16) losslessly.
+    ``filter``: every row Paeth, or each row the type of least cost (libpng's minimum sum of absolute differences).  The
+    record's parameter is the segment's bytes."""
     suffix, entry, noun = '.png', 'fl_output_png', 'PNG file'
 
-    def __init__(self, alpha=False):
+    def __init__(self, alpha=False, bits=8, filter='paeth'):
         if not isinstance(alpha, bool):
             raise ValueError('output.alpha must be true or false')
-        self.alpha, self.channels = alpha, 4 if alpha else 3
+        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
+            raise ValueError('output.bits must be 8 or 16')
+        if not isinstance(filter, str) or filter not in _lib.PNG_FILTERS:
+            raise ValueError('output.filter must be "paeth" or "adaptive", not "%s"' % (filter,))
+        self.alpha, self.channels, self.bits, self.filter = alpha, 4 if alpha else 3, bits, filter
+        self.extended = bits != 8 or filter != 'paeth'          # (the defaults stay on the entry points they have always used)
+        if self.extended:
+            self.entry = 'fl_output_png_f'
 
     def argument(self):
         return self.channels
 
+    def arguments(self):
+        if self.extended:
+            return (self.channels, self.bits, _lib.PNG_FILTERS[self.filter])
+        return (self.channels,)
+
     def capacity(self, dim):
         """The library's bound: no frame needs more (noise is stored, at 17 bytes per segment above its own size)."""
+        if self.extended:
+            return int(_lib.load().fl_png_bound_f(dim.w, dim.h, self.channels, self.bits, _lib.PNG_FILTERS[self.filter]))
         return int(_lib.load().fl_png_bound(dim.w, dim.h, self.channels))
 
 
@@ -270,6 +286,10 @@ def get_output_for_profile(gprof):
     """Output module for the profile's ``output`` block (cuburn/output.py:421-436)."""
     opts = dict(gprof.output.raw())
     handler = opts.pop('type', 'jpeg')
+    if not (handler == 'png' and opts.get('encoder') == 'device'):
+        for key in ('bits', 'filter'):
+            if key in opts:
+                raise ValueError('output.%s: only the device PNG encoder takes it: set "encoder": "device" on a png output' % key)
     if opts.pop('device', False):
         if handler != 'jpeg':
             raise ValueError('output.device: only jpeg is encoded on the device, not "%s"' % handler)
@@ -280,8 +300,9 @@ def get_output_for_profile(gprof):
             raise ValueError('output.encoder: "device" is the only encoder to choose, not "%s"' % (encoder,))
         if handler != 'png':
             raise ValueError('output.encoder: selects the device PNG encoder ("device": true is the JPEG switch), not "%s"' % handler)
-        if set(opts) - {'alpha'}:
-            raise ValueError('the device PNG encoder takes "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha'})))
+        if set(opts) - {'alpha', 'bits', 'filter'}:
+            raise ValueError('the device PNG encoder takes "alpha", "bits" and "filter" only, not %s'
+                             % ', '.join(sorted(set(opts) - {'alpha', 'bits', 'filter'})))
         return DevicePNGOutput(**opts)
     if 'optimize' in opts and handler != 'mjpeg':
         raise ValueError('output.optimize: only the device JPEG encoder optimises its Huffman tables: '

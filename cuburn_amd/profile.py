@@ -59,6 +59,11 @@ def add_args(parser=None):
     out.add_argument('--optimize', action='store_true', default=None,
                      help='Huffman tables from each frame\'s own statistics in device-encoded jpeg stills and mjpeg animations: '
                           'smaller files of the same pixels (sets output.optimize)')
+    out.add_argument('--bits', type=int, choices=[8, 16],
+                     help='Sample depth of device-encoded png stills; 16 keeps what tiff and raw16 hold (sets output.bits)')
+    out.add_argument('--png-filter', choices=['paeth', 'adaptive'],
+                     help='Row filter of device-encoded png stills: Paeth on every row, or per row the type of least '
+                          'sum of absolute residuals (sets output.filter)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -92,6 +97,10 @@ def get_from_args(args):
         prof['output'] = dict(prof.get('output') or {}, quality=ns['quality'])
     if ns.get('optimize'):
         prof['output'] = dict(prof.get('output') or {}, optimize=True)
+    if ns.get('bits') is not None:
+        prof['output'] = dict(prof.get('output') or {}, bits=ns['bits'])
+    if ns.get('png_filter') is not None:
+        prof['output'] = dict(prof.get('output') or {}, filter=ns['png_filter'])
     return name, prof
 
 

@@ -324,7 +324,8 @@ int fl_jpeg_encode_f(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int 
 int fl_output_jpeg_f(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, int sampling, unsigned flags,
                      void *host_out, uint64_t dev_out, size_t cap);
 
-/* PNG stills encoded on the device: 8-bit truecolour, colour type 2 (channels 3) or 6 (channels 4), not interlaced:
+/* PNG stills encoded on the device: 8-bit truecolour (16-bit, and a filter type per row: the _f entry points
+ * below), colour type 2 (channels 3) or 6 (channels 4), not interlaced:
  * the signature, IHDR, one IDAT per segment, IEND; no ancillary chunk.  The IDATs hold one zlib stream (header 78 01, deflate
  * blocks, Adler-32).  Every row is filtered with Paeth (filter byte 4).  The filtered bytes are cut into segments of segment_bytes
  * bytes (the library's choice; the last may be shorter), each coded with no reference before its own start as one block: dynamic
@@ -349,6 +350,29 @@ int fl_output_jpeg_f(fl_ctx *ctx, uint32_t w, uint32_t h, int quality, int sampl
 size_t fl_png_bound(uint32_t w, uint32_t h, int channels);
 int fl_png_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_png(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap);
+
+/* The same with a sample depth and flags.  bits = 8, flags = 0: the three entry points above, byte for byte.
+ * With bpp = channels * bits / 8 (3, 4, 6 or 8): IHDR's bit depth is `bits`; a row of the filtered stream is one filter byte
+ * and w * bpp residual bytes; all five PNG filters work on bytes at distance bpp (a and c are 0 for a row's first bpp bytes, b
+ * and c are 0 in row 0).  Everything else of the file is as above.
+ * bits = 16: the source is u16 [h][w][4] as FL_OUT_RGBA16 writes them, in native byte order (channels 3 leaves the alpha
+ * sample out); the file holds each sample most significant byte first.
+ * FL_PNG_ADAPTIVE: every row takes the filter type t in 0..4 (None, Sub, Up, Average with floor((a + b) / 2), Paeth) whose
+ * cost — the sum over the row's residual bytes r of min(r, 256 - r) — is least, the smallest such t on a tie (libpng's
+ * minimum sum of absolute differences).  Without the flag every row is type 4.
+ * The same pixels, size, channels, bits and flags give the same bytes.  The record is the same.
+ * fl_png_bound_f: fl_png_bound with rows of 1 + w * bpp bytes; 0 as fl_png_bound, for bits other than 8 or 16, for an unknown
+ * flag bit and for a result beyond 2^32 - 1.
+ * fl_output_png_f with bits = 16: fl_output(FL_OUT_RGBA16) into the lane's pixel buffer (same draws, same dither states
+ * afterwards), then the encode; closes the frame as fl_output does.
+ * Any other call is FL_E_INVAL for bits other than 8 or 16, an unknown flag bit or a frame whose fl_png_bound_f is 0, after
+ * every refusal of the entry points above and before anything is queued. */
+enum { FL_PNG_ADAPTIVE = 1 };
+size_t fl_png_bound_f(uint32_t w, uint32_t h, int channels, int bits, unsigned flags);
+int fl_png_encode_f(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags,
+                    void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_png_f(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, unsigned flags,
+                    void *host_out, uint64_t dev_out, size_t cap);
 
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their

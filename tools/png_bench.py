@@ -12,7 +12,12 @@ Prints and writes:
     segment_bytes over the device's own filtered bytes — the same tokens and the same segmentation, so that the difference is the
     device's length limiting and block headers;
   * per kernel, from a child run under `rocprofv3 --kernel-trace --stats` with one stream lane;
-  * --sweep: the device loop at other segment lengths (FLAME_PNG_SEG).
+  * --sweep: the device loop at other segment lengths (FLAME_PNG_SEG);
+  * --forms (instead of the above): the loop, the encode slot, the file's bytes, the rows per filter type and the share of stored
+    segments for the four forms of the device file — 8 / 16 bits x all-Paeth / a type per row — and the loop of the 16-bit TIFF;
+  * --ab DIR (instead of the above): the default form in this tree and in the built checkout of another commit at DIR (its own
+    copy of this tool and its own library), alternated --ab-rounds times.
+    With --out these two add their keys to the file the plain run wrote and leave the rest of it as it is.
 Each figure is from one run.  There is no fallback: without a GPU the tool fails.
 """
 import argparse
@@ -34,7 +39,11 @@ sys.path.insert(0, REPO)
 import numpy as np                                                    # noqa: E402
 
 BLOCKS = dict(none={'type': 'raw'}, host={'type': 'png'}, device={'type': 'png', 'encoder': 'device'},
-              device_alpha={'type': 'png', 'encoder': 'device', 'alpha': True})
+              device_alpha={'type': 'png', 'encoder': 'device', 'alpha': True}, tiff={'type': 'tiff'},
+              device_adaptive={'type': 'png', 'encoder': 'device', 'filter': 'adaptive'},
+              device16={'type': 'png', 'encoder': 'device', 'bits': 16},
+              device16_adaptive={'type': 'png', 'encoder': 'device', 'bits': 16, 'filter': 'adaptive'})
+FORMS = ('device', 'device_adaptive', 'device16', 'device16_adaptive')
 
 
 def setup(block, host_seed=42):
@@ -45,14 +54,29 @@ def setup(block, host_seed=42):
     return mgr, render.Renderer(gnm, gprof), gnm, gprof
 
 
-def idat_stream(data):
+def idat_bodies(data):
     out, p = [], 8
     while p < len(data):
         n, = struct.unpack('>I', data[p:p + 4])
         if data[p + 4:p + 8] == b'IDAT':
             out.append(data[p + 8:p + 8 + n])
         p += 12 + n
-    return b''.join(out)
+    return out
+
+
+def idat_stream(data):
+    return b''.join(idat_bodies(data))
+
+
+def form_stats(data):
+    """Of a device file of any depth: how many rows took each filter type, and how many segments (one IDAT each) are stored blocks."""
+    w, h, bits, ctype = struct.unpack('>IIBB', data[16:26])
+    rowlen = 1 + w * (3 if ctype == 2 else 4) * bits // 8
+    filtered = np.frombuffer(zlib.decompress(idat_stream(data)), np.uint8)
+    bodies = idat_bodies(data)
+    stored = sum(1 for i, b in enumerate(bodies) if (b[2 if i == 0 else 0] >> 1 & 3) == 0)      # BTYPE of the segment's first block
+    return dict(bits=bits, rows_per_filter_type=[int(v) for v in np.bincount(filtered[::rowlen], minlength=5)], segments=len(bodies),
+                stored_segments=stored, stored_share=stored / float(len(bodies)), file_bytes=len(data))
 
 
 def sizes(data, seg):
@@ -94,7 +118,9 @@ def loop(kind, nframes, warmup=3):
         data = next(iter(media.values())).getvalue()
         res['bytes'] = len(data)
         if kind.startswith('device'):
-            res['sizes'] = sizes(data, int(np.frombuffer(frame[8:12], '<u4')[0]))
+            res['form'] = form_stats(data)
+            if res['form']['bits'] == 8:                              # (Pillow reads the high bytes of a 16-bit file only)
+                res['sizes'] = sizes(data, int(np.frombuffer(frame[8:12], '<u4')[0]))
     mgr.fb.free()
     return res
 
@@ -108,10 +134,10 @@ def kernels_only(nframes):
     mgr.fb.free()
 
 
-def child(args, limit, env=None):
-    """One step in a process of its own; its last line is the step's JSON."""
-    cmd = [sys.executable, os.path.abspath(__file__)] + args
-    r = subprocess.run(cmd, env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE, timeout=limit)
+def child(args, limit, env=None, tree=None):
+    """One step in a process of its own; its last line is the step's JSON.  tree: another built checkout, whose own copy of this tool runs."""
+    cmd = [sys.executable, os.path.join(os.path.abspath(tree), 'tools', 'png_bench.py') if tree else os.path.abspath(__file__)] + args
+    r = subprocess.run(cmd, env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE, timeout=limit, cwd=tree)
     if r.returncode:
         raise SystemExit('step %s ended with status %d: nothing more is started' % (' '.join(args), r.returncode))
     return json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -135,6 +161,16 @@ def profiled_kernels(nframes):
     return rows
 
 
+def merge_out(path, res):
+    """--forms and --ab add their keys (sorted, behind what is there) to the JSON file the plain run wrote, and leave the rest of it as it is."""
+    old = json.load(open(path)) if os.path.exists(path) else {}
+    for k in sorted(res):
+        old.pop(k, None)
+        old[k] = res[k]
+    with open(path, 'w') as f:
+        f.write(json.dumps(old, indent=1) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=200)
@@ -142,12 +178,34 @@ def main():
     ap.add_argument('--out', default=None, help='also write the figures to this JSON file')
     ap.add_argument('--sweep', action='store_true', help='device loop at segment lengths 8192 .. 32768')
     ap.add_argument('--no-profile', action='store_true', help='skip the rocprofv3 child')
+    ap.add_argument('--forms', action='store_true', help='only the four forms of the device file (8 / 16 bits x paeth / adaptive) and the tiff loop')
+    ap.add_argument('--ab', default=None, metavar='DIR', help='only the default form, this tree alternated with the built checkout of another commit at DIR')
+    ap.add_argument('--ab-rounds', type=int, default=3)
     ap.add_argument('--step', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.step == 'kernels':
         return kernels_only(args.frames)
     if args.step:
         print(json.dumps(loop(args.step, args.frames)))
+        return
+    if args.forms or args.ab:
+        res = {}
+        if args.forms:
+            res['forms'] = dict((k, child(['--step', k, '--frames', str(args.frames)], 120)) for k in FORMS)
+            res['forms_frames'] = args.frames
+            res['loop_tiff'] = child(['--step', 'tiff', '--frames', str(args.frames)], 240)
+            res['tiff_file_bytes'] = res['loop_tiff']['bytes']
+        if args.ab:                                                   # the default form: this tree and another commit's, alternated
+            runs = []
+            for _ in range(args.ab_rounds):
+                for name, tree in (('this', None), ('other', args.ab)):
+                    r = child(['--step', 'device', '--frames', str(args.frames)], 120, tree=tree)
+                    runs.append(dict(tree=name, encode_slot_ms_per_frame=r['encode_slot_ms_per_frame'], fps=r['fps'], bytes=r['bytes']))
+            res['default_form_a_b'] = runs
+            res['default_form_a_b_frames'] = args.frames
+        print(json.dumps(res, indent=1, sort_keys=True))
+        if args.out:
+            merge_out(args.out, res)
         return
     res = dict(config='cfg2 1920x1080 2^28 samples', frames=args.frames, runs='every figure is from one run')
     res['loop_no_encode'] = child(['--step', 'none', '--frames', str(args.frames)], 120)
