@@ -1,11 +1,13 @@
 """
-Command line renderer: ``python -m cuburn_amd ID [-d GENOMEDB] [profile options]``.
+Command line renderer: ``python -m cuburn_amd ID [ID ...] [-d GENOMEDB] [profile options]``.
 
 Same arguments and frame loop as the reference's main.py:29-137 (double-buffered: frame k+1
 is queued before frame k is waited for and written), over the HIP path.  ``--list-devices``
 lists the HIP devices; ``--print`` prints the blended animation and exits.  Started once per GPU
 (``python -m torch.distributed.run --nproc-per-node N -m cuburn_amd ...``) the processes share the
-output files between them — the role of the reference's distribute.py (see jobs.py).
+output files between them — the role of the reference's distribute.py (see jobs.py).  Several IDs are
+rendered one after the other; with ``--async-compile`` the kernel of the next one is compiled while
+this one's frames render.  ``--kernel-cache DIR`` keeps compiled kernels for later runs and other ranks.
 """
 import argparse
 import os
@@ -55,10 +57,14 @@ def _one_ahead(queue, times):
         yield len(times), inflight
 
 
-def render(args, prof):
-    """Render every output file of the run; under a one-process-per-GPU launcher (WORLD_SIZE > 1) this
-    process takes its share of the files on its own GPU (jobs.py).  Returns the number of files lost."""
-    gnm, basename = store.connect(args.genomedb).animation(args.flame, args.half)
+def render(args, prof, flame=None, ahead=None):
+    """Render every output file of one genome (``flame``; default: the first ID of the command line); under a
+    one-process-per-GPU launcher (WORLD_SIZE > 1) this process takes its share of the files on its own GPU
+    (jobs.py).  ``ahead``: the ID rendered next — with FLAME_RTC_ASYNC=1 its kernel is asked for before this
+    genome's frames are waited for.  Returns the number of files lost."""
+    if flame is None:
+        flame = args.flame[0] if isinstance(args.flame, list) else args.flame
+    gnm, basename = store.connect(args.genomedb).animation(flame, args.half)
     if getattr(args, 'print'):
         print(convert.to_json(gnm))
         return 0
@@ -74,6 +80,17 @@ def render(args, prof):
     device = args.device if args.device is not None and args.device >= 0 else (local if world > 1 else 0)
     rmgr = R.RenderManager(device=device)
     rdr = R.Renderer(gnm, gprof, keep=args.keep)
+    if R.async_compile():
+        rmgr.prepare(rdr, gprof, todo[0][1][0] if len(todo[0][1]) else 0.0)      # the compile starts now, beside the upload and the first frames
+        if ahead is not None:
+            # the next genome's kernel: the job belongs to the process, not to this throw-away handle — the next
+            # genome's own handle finds it finished, or waits on the interpreter kernel for the rest of it
+            try:
+                gnm2, _ = store.connect(args.genomedb).animation(ahead, args.half)
+                gprof2 = profile.wrap(prof, gnm2)
+                rmgr.prepare(R.Renderer(gnm2, gprof2, keep=args.keep), gprof2, 0.0)
+            except Exception:
+                print('Could not prepare %s ahead: %s' % (ahead, traceback.format_exc()), file=sys.stderr)
     tag = ('%d: ' % device) if world > 1 or (args.device is not None and args.device >= 0) else ''
     took = [0]
 
@@ -111,7 +128,7 @@ def render(args, prof):
 
 def build_parser():
     parser = argparse.ArgumentParser(prog='python -m cuburn_amd', description='Render fractal flames.')
-    parser.add_argument('flame', metavar='ID', type=str, nargs='?', help='Filename or flame ID of genome to render')
+    parser.add_argument('flame', metavar='ID', type=str, nargs='*', help='Filename or flame ID of genome to render (several: one after the other)')
     parser.add_argument('-d', '--genomedb', metavar='PATH', type=str, default='.',
                         help="Path to genome database (file or directory, default '.')")
     parser.add_argument('--raw', metavar='PATH', type=str, dest='rawfn',
@@ -121,6 +138,10 @@ def build_parser():
     parser.add_argument('--list-devices', action='store_true', help='List devices and exit.')
     parser.add_argument('--device', metavar='NUM', type=int, help='GPU device number to use.')
     parser.add_argument('--keep', action='store_true', help='Accepted for compatibility (kernels are precompiled).')
+    parser.add_argument('--kernel-cache', metavar='DIR', type=str,
+                        help='Keep compiled per-genome kernels in DIR and load them from there (FLAME_RTC_CACHE).')
+    parser.add_argument('--async-compile', action='store_true',
+                        help='Compile per-genome kernels beside the frame loop; frames run the interpreter kernel until then (FLAME_RTC_ASYNC=1).')
     profile.add_args(parser)
     return parser
 
@@ -132,8 +153,16 @@ def main(argv=None):
         return 0
     if not args.flame:
         build_parser().error('a flame ID or file is required')
+    # not profile keys — they change no picture; the library reads them when the context is created / a kernel is first needed
+    if args.kernel_cache:
+        os.environ['FLAME_RTC_CACHE'] = args.kernel_cache
+    if args.async_compile:
+        os.environ['FLAME_RTC_ASYNC'] = '1'
     pname, prof = profile.get_from_args(args)
-    return 1 if render(args, prof) else 0
+    lost = 0
+    for k, flame in enumerate(args.flame):
+        lost += render(args, prof, flame, args.flame[k + 1] if k + 1 < len(args.flame) else None)
+    return 1 if lost else 0
 
 
 if __name__ == '__main__':

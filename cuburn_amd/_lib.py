@@ -90,6 +90,10 @@ _SIGS = {
     'fl_debug_shuffle': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     'fl_debug_counters': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fl_rtc_compile_check': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    'fl_genome_prepare': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
+    'fl_rtc_wait': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'fl_rtc_stats': (C.c_int, [C.POINTER(C.c_uint64 * 8)]),
+    'fl_debug_rtc_hold': (C.c_int, [C.c_int]),
     'fl_debug_apply_xf': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
     'fl_debug_math': (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

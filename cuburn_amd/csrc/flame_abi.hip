@@ -189,6 +189,7 @@ struct fl_ctx {
     // environment switches, read once when the context is created (listed in include/flame_hip.h)
     bool env_bin_wide = false, env_no_intra = false;
     bool use_rtc = true;                    // FLAME_RTC=0: always the interpreter kernel
+    bool rtc_async = false;                 // FLAME_RTC_ASYNC=1: per-genome kernels are compiled by a worker thread; the interpreter kernel runs until they are there
     uint32_t jpeg_ri = FL_JPEG_RI;          // FLAME_JPEG_RI (1..21): MCUs per JPEG restart interval
     uint32_t jpeg_ri_420 = FL_JPEG_RI_420;  // ... in 4:2:0, where a value above 10 means 10
     uint32_t n_spec_launch = 0, n_interp_launch = 0;      // iterate launches by kernel since fl_timings_reset (fl_launch_stats)
@@ -202,6 +203,7 @@ struct fl_genome {
     hipFunction_t rtc_fn[5][2][4] = {};     // [nw 4 / 8 / 16 / 8 in halves / 16 in quarters][count][acc] once compiled
     unsigned rtc_epoch = 0;                 // module-cache epoch the handles above belong to
     bool rtc_failed = false;                // compile / load failed once: stay on the interpreter kernel
+    bool rtc_want[5][2][4] = {};            // variants asked for while their job was unfinished (FLAME_RTC_ASYNC): what fl_rtc_wait waits for
     uint32_t nops = 0, nrows = 0, pstride = 0;
     int32_t *d_prog = nullptr, *d_ops = nullptr;
     float *d_times = nullptr, *d_knots = nullptr, *d_ptimes = nullptr;
@@ -320,6 +322,7 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
     if (const char *e = getenv("FLAME_BIN_PARTS")) { int v = atoi(e); if (v >= 1 && v <= 64) c->bin_parts = (uint32_t)v; }
     c->env_bin_wide = env_on("FLAME_BIN_WIDE");
     if (const char *e = getenv("FLAME_RTC")) c->use_rtc = strcmp(e, "0") != 0;
+    c->rtc_async = env_on("FLAME_RTC_ASYNC");
     if (const char *e = getenv("FLAME_JPEG_RI")) { const int v = atoi(e); if (v >= 1 && v <= 21) { c->jpeg_ri = (uint32_t)v; c->jpeg_ri_420 = std::min((uint32_t)v, FL_JPEG_RI_420_MAX); } }
     c->env_no_intra = env_on("FLAME_NO_INTRA_OVERLAP");      // launches of a frame strictly in series on one stream
     if (const char *e = getenv("FLAME_LAUNCH_ROUNDS")) { int v = atoi(e); if (v >= 16 && v <= 4096) c->launch_rounds = (uint32_t)(v / 16 * 16); }
@@ -660,6 +663,34 @@ static int ensure_binned(fl_ctx *c, Lane &ln, const fl_dim &d, uint32_t write_ro
     return ln.d_dir[buf].reserve(s.dir_words, "sample log directory", quiesce);
 }
 
+// The per-genome kernel of one variant (count, kernel accumulate mode) in the context's walker geometry, or null: the interpreter
+// kernel runs.  `mode` (kernels.h): RTC_SYNC compiles a missing variant now; RTC_POLL queues it for the worker thread and
+// reports *pending while its job is unfinished; RTC_WAIT waits for it.
+static hipFunction_t rtc_variant(fl_ctx *c, fl_genome *g, bool count, int kacc, int mode, bool *pending)
+{
+    *pending = false;
+    if (!c->use_rtc || g->rtc_failed || kacc == 2) return nullptr;
+    const unsigned ep = rtc_epoch();
+    if (g->rtc_epoch != ep) { memset(g->rtc_fn, 0, sizeof g->rtc_fn); g->rtc_epoch = ep; }     // the module cache was flushed
+    // the walker geometry's row of rtc_fn: 4 / 8 / 16 waves, 8 in halves, 16 in quarters
+    const int geom = c->sub_log2 ? 2 + (int)c->sub_log2 : c->nw == 16 ? 2 : c->nw == 8 ? 1 : 0;
+    hipFunction_t &slot = g->rtc_fn[geom][count ? 1 : 0][kacc];
+    if (!slot) {
+        std::string err;
+        const int rc = rtc_iter_kernel(c->device, g->spec, c->nw, c->nslots, count, kacc, &slot, &err, c->sub_log2, mode);
+        if (rc < 0) {
+            g->rtc_failed = true;
+            slot = nullptr;
+            fprintf(stderr, "libflame_hip: per-genome kernel not available (%s); using the interpreter kernel\n", err.c_str());
+        } else if (rc > 0) {
+            slot = nullptr;
+            *pending = true;
+        }
+        g->rtc_want[geom][count ? 1 : 0][kacc] = rc > 0;
+    }
+    return slot;
+}
+
 // One iterate launch and (binned mode) its tile accumulate.  `buf` selects the log / directory set;
 // `drain` is the stream the accumulate runs on: the lane's own stream, or its aux stream when the
 // launches of a frame are pipelined (then the accumulate waits for this iterate through ev_it[buf]).
@@ -677,25 +708,11 @@ static int do_iter_launch(fl_ctx *c, Lane &ln, fl_genome *g, const fl_dim &d, ui
     EvPair *e = ev_acquire(c, c->iter_ev);      // recorded by the kernel launch itself (hipExtLaunchKernelGGL)
     const int kacc = acc == FL_ACCUM_BINNED && bl.wide ? 3 : acc;
     // the kernel specialised for this genome's structure (compiled on first use, rtc.hip); the
-    // interpreter kernel if hipRTC is unavailable, switched off, or the compile failed
-    hipFunction_t fn = nullptr;
-    if (c->use_rtc && !g->rtc_failed && kacc != 2) {
-        const unsigned ep = rtc_epoch();
-        if (g->rtc_epoch != ep) { memset(g->rtc_fn, 0, sizeof g->rtc_fn); g->rtc_epoch = ep; }     // the module cache was flushed
-        // the walker geometry's row of rtc_fn: 4 / 8 / 16 waves, 8 in halves, 16 in quarters
-        const int geom = c->sub_log2 ? 2 + (int)c->sub_log2 : c->nw == 16 ? 2 : c->nw == 8 ? 1 : 0;
-        hipFunction_t &slot = g->rtc_fn[geom][count ? 1 : 0][kacc];
-        if (!slot) {
-            std::string err;
-            if (rtc_iter_kernel(c->device, g->spec, c->nw, c->nslots, count, kacc, &slot, &err, c->sub_log2)) {
-                g->rtc_failed = true;
-                slot = nullptr;
-                fprintf(stderr, "libflame_hip: per-genome kernel not available (%s); using the interpreter kernel\n", err.c_str());
-            }
-        }
-        fn = slot;
-    }
+    // interpreter kernel if hipRTC is unavailable, switched off, the compile failed — or is still under way (FLAME_RTC_ASYNC)
+    bool pending = false;
+    const hipFunction_t fn = rtc_variant(c, g, count, kacc, c->rtc_async ? RTC_POLL : RTC_SYNC, &pending);
     (fn ? c->n_spec_launch : c->n_interp_launch) += 1;
+    rtc_count_launch(fn != nullptr, pending);
     const IterLaunch il = {c->nw, count, kacc, c->nslots, g->d_prog, ln.d_params, ln.d_palette, c->rng_walk(), c->d_points,
                            ln.d_hot, ln.d_atom, (float *)ln.d_front.p, c->d_counters, d.astride, d.ah, c->round_counter, nrounds, fuse,
                            bl.tiles_x, bl.nbins, c->bin_rounds, nbatch_total, ln.d_log[buf], ln.d_dir[buf],
@@ -1491,6 +1508,43 @@ int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops
     if (rc) return fail(rtc_available() ? FL_E_HIP : FL_E_UNSUPPORTED, "per-genome kernel did not compile", __FILE__, __LINE__);
     return (int)(code.size() > 0 ? FL_OK : FL_E_HIP);
 }
+
+int fl_genome_prepare(fl_ctx *c, fl_genome *g, uint32_t w, uint32_t h, int accum_mode)
+{
+    REQUIRE(c && g, "null argument");
+    REQUIRE(accum_mode == FL_ACCUM_ATOMIC || accum_mode == FL_ACCUM_BINNED || accum_mode == 2, "bad accumulation mode");
+    HIPCHK(hipSetDevice(c->device));
+    // the one variant fl_iterate launches for this size and mode (do_iter_launch): no counters; a binned frame of more tiles than
+    // the 128x64 layout holds takes the wide kernel
+    const int kacc = accum_mode == FL_ACCUM_BINNED && c->layout(calc_dim(w, h)).wide ? 3 : accum_mode;
+    bool pending = false;
+    (void)rtc_variant(c, g, false, kacc, c->rtc_async ? RTC_POLL : RTC_SYNC, &pending);
+    return FL_OK;
+}
+
+int fl_rtc_wait(fl_ctx *c, fl_genome *g)
+{
+    REQUIRE(c && g, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    const int geom = c->sub_log2 ? 2 + (int)c->sub_log2 : c->nw == 16 ? 2 : c->nw == 8 ? 1 : 0;
+    for (int count = 0; count < 2; ++count)
+        for (int kacc = 0; kacc < 4; ++kacc) {
+            if (!g->rtc_want[geom][count][kacc]) continue;
+            REQUIRE(!rtc_held(), "the worker is held (fl_debug_rtc_hold): its jobs cannot finish");
+            bool pending = false;
+            (void)rtc_variant(c, g, count != 0, kacc, RTC_WAIT, &pending);
+        }
+    return FL_OK;
+}
+
+int fl_rtc_stats(uint64_t out[8])
+{
+    REQUIRE(out, "null argument");
+    rtc_stats(out);
+    return FL_OK;
+}
+
+int fl_debug_rtc_hold(int on) { rtc_hold(on != 0); return FL_OK; }
 
 int fl_debug_counters(fl_ctx *c, uint64_t out4[4])
 {

@@ -52,7 +52,16 @@ struct IterSpec {
 bool rtc_available();
 unsigned rtc_epoch();      // changes when cached modules were unloaded: function handles obtained before are void
 int rtc_compile(const IterSpec &spec, int nw, bool count, int acc, std::vector<char> *code, std::string *err, const char *extra_opt = nullptr, uint32_t sub_log2 = 0);
-int rtc_iter_kernel(int device, const IterSpec &spec, int nw, uint32_t nslots, bool count, int acc, hipFunction_t *fn, std::string *err, uint32_t sub_log2 = 0);
+// How rtc_iter_kernel gets a variant that is not in the process cache: compile it now (0 or -1); or have the worker thread compile
+// it (FLAME_RTC_ASYNC) and return 1 while a job of the variant is unfinished — RTC_WAIT instead waits for it.  Module load, function
+// lookup and the register check happen on the calling thread in every mode.
+enum { RTC_SYNC = 0, RTC_POLL = 1, RTC_WAIT = 2 };
+int rtc_iter_kernel(int device, const IterSpec &spec, int nw, uint32_t nslots, bool count, int acc, hipFunction_t *fn, std::string *err, uint32_t sub_log2 = 0,
+                    int mode = RTC_SYNC);
+void rtc_stats(uint64_t out[8]);                    // fl_rtc_stats
+void rtc_count_launch(bool spec, bool pending);     // an iterate launch: on a per-genome kernel / on the interpreter while a job of its variant was pending
+void rtc_hold(bool on);                             // fl_debug_rtc_hold: the worker leaves queued jobs alone while held
+bool rtc_held();
 
 // binned.hip
 void launch_accum_tiles(hipStream_t st, const uint32_t *log, const uint32_t *dir, const u64 *palette,

@@ -316,6 +316,24 @@ class Renderer(object):
             pass
 
 
+RTC_STATS = ('compiles', 'disk_hits', 'disk_misses', 'disk_writes', 'disk_rejects', 'jobs_queued',
+             'interp_launches_pending', 'spec_launches')
+
+
+def rtc_stats():
+    """Process-wide counters of the per-genome kernels (fl_rtc_stats; needs no device): compiler runs, the disk cache's hits,
+    misses, writes and rejected files (FLAME_RTC_CACHE), jobs queued for the compile thread (FLAME_RTC_ASYNC), iterate launches
+    on the interpreter kernel while their kernel was being compiled, iterate launches on a per-genome kernel."""
+    st = (C.c_uint64 * 8)()
+    _lib.check(_lib.load().fl_rtc_stats(C.byref(st)))
+    return dict(zip(RTC_STATS, (int(v) for v in st)))
+
+
+def async_compile():
+    """FLAME_RTC_ASYNC as the library reads it: per-genome kernels are compiled beside the frame loop."""
+    return os.environ.get('FLAME_RTC_ASYNC', '0') not in ('', '0')
+
+
 class RenderManager(object):
     """Frame queue (cuburn/render.py:253-434)."""
 
@@ -362,6 +380,16 @@ class RenderManager(object):
             mode = _lib.ACCUM_BINNED if ntiles <= 8191 else _lib.ACCUM_ATOMIC
         return mode
 
+    def prepare(self, rdr, gprof, tc=0.0):
+        """Ask for the per-genome kernel of this Renderer's frames now (fl_genome_prepare): queued for the compile thread with
+        FLAME_RTC_ASYNC=1, compiled at once without.  queue_frame does this when it first meets a genome in asynchronous mode;
+        a caller that walks several genomes calls it for the next one before it waits for this one's frames."""
+        ss = filters.supersample_of(gprof)
+        acc = self.fb.set_dim(ss * gprof.width, ss * gprof.height, nsamples=gprof.spp(tc) * gprof.width * gprof.height)
+        g = rdr._handle(self.fb)
+        _lib.check(_lib.load().fl_genome_prepare(self.fb.ctx, g, acc.w, acc.h, self.resolve_accum_mode(acc)))
+        rdr._prepared = (rdr._mod_key, acc.w, acc.h)
+
     def queue_frame(self, rdr, gnm, gprof, tc, copy=True, dev_out=0, host=True):
         """
         Queue one frame at centre time ``tc``; returns ``(evt, h_out)`` (render.py:374-434).
@@ -376,6 +404,9 @@ class RenderManager(object):
         td = gprof.frame_width(tc) / round(gprof.fps * gprof.duration)
         ts = tc - 0.5 * td
         g = rdr._handle(self.fb)
+        if async_compile() and getattr(rdr, '_prepared', None) != (rdr._mod_key, acc.w, acc.h):      # a genome met for the first time
+            _lib.check(lib.fl_genome_prepare(self.fb.ctx, g, acc.w, acc.h, self.resolve_accum_mode(acc)))
+            rdr._prepared = (rdr._mod_key, acc.w, acc.h)
         fid = C.c_uint32()
         _lib.check(lib.fl_frame_begin(self.fb.ctx, C.byref(fid)))
         if copy:

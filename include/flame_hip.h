@@ -490,6 +490,22 @@ int fl_debug_math(fl_ctx *ctx, int fn, uint32_t n, const float *a, const float *
  * count: bit 0 = the sample counters, bit 1 = a temporal sample per four waves (nw = 8 / 16: two / four per workgroup). */
 int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops, int nw, int count, int acc,
                          char *log, size_t log_bytes);
+/* Get the per-genome kernel that fl_iterate would launch for a w x h frame in `accum_mode` before the frame needs it.  With
+ * FLAME_RTC_ASYNC=1 the compile is queued for the library's worker thread and the call returns at once; otherwise the kernel is
+ * compiled now.  Nothing happens with FLAME_RTC=0.  A failed compile is reported as fl_iterate reports it: one line on stderr,
+ * and the genome stays on the interpreter kernel.  The reference compiles in Renderer's constructor (cuburn/render.py:232-236). */
+int fl_genome_prepare(fl_ctx *ctx, fl_genome *g, uint32_t w, uint32_t h, int accum_mode);
+/* Return when no compile job of a kernel this genome asked for (fl_genome_prepare, fl_iterate) is unfinished and the finished
+ * kernels are loaded: the genome's next launches run them.  FL_E_INVAL while the worker is held and a job is outstanding. */
+int fl_rtc_wait(fl_ctx *ctx, fl_genome *g);
+/* Process-wide counters of the per-genome kernels; needs no device.  out[0] compiler runs; the disk cache (FLAME_RTC_CACHE):
+ * out[1] hits, out[2] misses (no file), out[3] files written, out[4] files rejected (short, damaged, another key's); out[5] jobs
+ * queued for the worker thread; iterate launches: out[6] on the interpreter kernel while a job of their kernel was unfinished,
+ * out[7] on a per-genome kernel. */
+int fl_rtc_stats(uint64_t out[8]);
+/* Tests only: while held (on != 0) the worker thread leaves queued jobs alone, so a test decides which kernel runs a frame
+ * instead of racing the compiler.  A job that is already running finishes. */
+int fl_debug_rtc_hold(int on);
 /* Counters of the last iterate: accepted (written) samples, out-of-frame, dropped, spills.  "Dropped" are the samples thinned
  * by the hot-pixel roulette (atomic accumulate) and the samples hidden by their xform's opacity; a hidden sample is counted
  * there and nowhere else (it is tested before the frame bounds), so accepted + out-of-frame + dropped is the number of
@@ -503,6 +519,9 @@ int fl_debug_counters(fl_ctx *ctx, uint64_t out4[4]);
  *   FLAME_NO_INTRA_OVERLAP=1 the launches of a multi-launch frame strictly in series on one stream
  *   FLAME_RTC=0              always the precompiled interpreter iterate kernel (no hipRTC per-genome kernel)
  *   FLAME_RTC_FLAGS=...      extra options for the hipRTC compile; FLAME_RTC_DUMP=<dir> keeps its source / assembly
+ *   FLAME_RTC_CACHE=<dir>    keep the compiled per-genome kernels in <dir> (made if missing) and load them from there: a process
+ *                            compiles only what no earlier process has (csrc/rtc_cache.h; never evicted)
+ *   FLAME_RTC_ASYNC=1        compile per-genome kernels on a worker thread; launches run the interpreter kernel until theirs is there
  *   FLAME_BIN_ROUNDS=n       rounds per sorted batch of the sample log (default 16)
  *   FLAME_BIN_PARTS=n        workgroups per tile of the tile accumulate (default: by image size)
  *   FLAME_BIN_GANG=n         adjacent tiles per XCD gang of the tile accumulate (default 32 above 512 tiles, else 0 = off)
