@@ -64,6 +64,9 @@ _SIGS = {
     'fl_png_bound_f': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint]),
     'fl_png_encode_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_png_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_tiff_bound': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    'fl_tiff_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_output_tiff': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_sort_u32': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     'fl_frame_begin': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     'fl_frame_ms': (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),

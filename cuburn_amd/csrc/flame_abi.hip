@@ -108,7 +108,7 @@ struct Lane {
     DevBuf<float> d_de_sinv;                        // FL_FILT_DE: 1 / S(m / 16) for m = 0 .. 16 * FL_DE_MAX_RADIUS (de_adaptive_norms)
     // The still encoders (encode_on) share one scratch and one staging buffer: their kernels are queued on `stream`, which orders one
     // encode's use behind the other's, and a regrow first waits for the stream (quiesce).
-    DevBuf<uint32_t> d_enc;                         // the encoder's working set (jpeg_layout / png_layout)
+    DevBuf<uint32_t> d_enc;                         // the encoder's working set (jpeg_layout / png_layout / tiff_layout)
     DevBuf<unsigned char> d_enc_out;                // the file on its way to host memory that is not pinned
     size_t nbins() const { return d_front.cap; }
     // binned accumulate: sample log + directory.  Two sets: in a frame of several launches the tile
@@ -995,8 +995,8 @@ int fl_output(fl_ctx *c, uint32_t w, uint32_t h, int fmt, void *host_out, uint64
     return close_frame(c, ln);
 }
 
-// ---- stills encoded on the device (jpeg.hip, png.hip) ----
-// What both encoders ask of a call: a context, a frame whose sides fit the formats' 16 bits, room for the record and the
+// ---- stills encoded on the device (jpeg.hip, png.hip, tiff.hip) ----
+// What every encoder asks of a call: a context, a frame whose sides fit the formats' 16 bits, room for the record and the
 // header (the placement kernel stores them whatever the status), and somewhere to put the file.
 static int check_encode(const fl_ctx *c, const char *enc, uint32_t w, uint32_t h, size_t header, const void *host_out, uint64_t dev_out, size_t cap)
 {
@@ -1032,7 +1032,7 @@ static int encode_on(fl_ctx *c, Lane &ln, void *host_out, uint64_t dev_out, size
         }
     }
     if (int rc = ln.d_enc.reserve(scratch_words, what_scratch, quiesce)) return rc;
-    EvPair *e = ev_begin_on(c, c->enc_ev, ln.stream);           // (slot 5 of fl_timings_detail: both device encoders)
+    EvPair *e = ev_begin_on(c, c->enc_ev, ln.stream);           // (slot 5 of fl_timings_detail: every device encoder)
     launch(ln.d_enc.p, dst);
     ev_end_on(e, ln.stream);
     HIPCHK(hipGetLastError());
@@ -1204,6 +1204,55 @@ int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_ou
     return fl_output_png_f(c, w, h, channels, 8, 0u, host_out, dev_out, cap);
 }
 
+// ---- TIFF ----
+// No file can be longer: every tile stored is its bytes and 5 of block header between the 2 bytes of its zlib header and the 4 of its
+// Adler-32, and a pad byte; in front of them the header, the IFD, BitsPerSample and — with more than one tile — both arrays.
+size_t fl_tiff_bound(uint32_t w, uint32_t h, int channels, int bits)
+{
+    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4) || (bits != 8 && bits != 16)) return 0;
+    const TiffLayout l = tiff_layout(w, h, channels, bits);
+    const uint64_t n = 16u + l.H + (uint64_t)l.nt * (l.tile_bytes + 5u + 6u + 1u);
+    return n > 0xffffffffull ? 0 : (size_t)n;
+}
+
+static int check_tiff(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    REQUIRE(c, "null ctx");
+    REQUIRE(channels == 3 || channels == 4, "tiff: channels must be 3 or 4");
+    REQUIRE(bits == 8 || bits == 16, "tiff: bits must be 8 or 16");
+    const bool sides = w >= 1 && h >= 1 && w <= 65535u && h <= 65535u;      // (check_encode refuses the others before it looks at the header)
+    if (int rc = check_encode(c, "tiff", w, h, sides ? (size_t)tiff_layout(w, h, channels, bits).H : 0, host_out, dev_out, cap)) return rc;
+    REQUIRE(fl_tiff_bound(w, h, channels, bits) != 0, "tiff: the file could pass 2^32 - 1 bytes");
+    return FL_OK;
+}
+
+static int tiff_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels, int bits, void *host_out,
+                          uint64_t dev_out, size_t cap)
+{
+    return encode_on(c, ln, host_out, dev_out, cap, fl_tiff_bound(w, h, channels, bits), tiff_layout(w, h, channels, bits).words, "tiff file",
+                     "tiff scratch", [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) {
+                         launch_tiff_encode(st, src, w, h, channels, bits, scratch, dst, cap);
+                     });
+}
+
+int fl_tiff_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_tiff(c, w, h, channels, bits, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "tiff: null source pixels");
+    HIPCHK(hipSetDevice(c->device));
+    return tiff_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, host_out, dev_out, cap);
+}
+
+int fl_output_tiff(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_tiff(c, w, h, channels, bits, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = tiff_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
+}
+
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
                 uint32_t *nvalid)
 {
@@ -1279,7 +1328,7 @@ int fl_timings_detail(fl_ctx *c, float ms[6])
     REQUIRE(c && ms, "null argument");
     sync_all(c);
     ms[0] = sum_ms(c->iter_ev); ms[1] = sum_ms(c->accum_ev); ms[2] = sum_ms(c->flush_ev);
-    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->enc_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG and PNG encodes
+    ms[3] = sum_ms(c->filt_ev); ms[4] = sum_ms(c->de_ev); ms[5] = sum_ms(c->enc_ev);      // [4]: the DE's eight launches (fused ends included), recorded where they are queued; [5]: the JPEG, PNG and TIFF encodes
     return FL_OK;
 }
 

@@ -136,6 +136,21 @@ PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg, int bit
 void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
                        uint32_t *scratch, unsigned char *out, size_t cap);
 
+// The same coder for streams that stand alone (tiff.hip): ntiles pieces of tile_bytes bytes (a multiple of 16 in [8192, 32768]) at `bytes`,
+// each one final block — dynamic, or stored when that is no smaller — at segbuf + i * stride; lens[i] its bytes (at most tile_bytes + 5),
+// adl[i] the Adler-32 of the piece.
+void launch_deflate_tiles(hipStream_t st, const unsigned char *bytes, uint32_t tile_bytes, uint32_t ntiles, unsigned char *segbuf, uint32_t stride,
+                          uint32_t *lens, uint32_t *adl);
+
+// tiff.hip: tiled little-endian TIFF, Adobe deflate with the horizontal predictor, from the same sources as the PNG.
+// `scratch` holds tiff_layout().words words; the 16-byte record, header + IFD + arrays and the tiles go to `out`, of which nothing at or
+// beyond `cap` (>= 16 + tiff_layout().H) is touched.  The tile's size is the format's (64 rows of 128 or 64 pixels), not FLAME_PNG_SEG's.
+#define FL_TIFF_TILE_LENGTH 64u
+struct TiffLayout { uint32_t tw, tiles_x, nt, tile_bytes, stride, entries, fixed; uint64_t H, F; size_t tiled, segbuf, offs, lens, adl, info, words; };      // tile width, tiles per row / in all, bytes per tile, bytes between coded tiles, IFD entries, bytes before the arrays, before the tiles, of the tiled stream; word offsets into the scratch
+TiffLayout tiff_layout(uint32_t w, uint32_t h, int channels, int bits);
+void launch_tiff_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, uint32_t *scratch,
+                        unsigned char *out, size_t cap);
+
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)
 
 // sort.hip: one stable radix pass (nbits <= 10 at lo_bit) over n keys; hist = scratch of

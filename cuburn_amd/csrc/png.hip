@@ -6,6 +6,7 @@
 //   k_png_segment   one workgroup per segment of `seg` filtered bytes, coded with no reference before its start: tokens (literal / run
 //                   of distance 1) -> histogram -> length-limited Huffman code -> one dynamic block packed in LDS, or one stored block
 //                   when that is no smaller (decided from the counted bits, before anything is emitted); the segment's Adler-32 parts
+//                   (its TILES form, launch_deflate_tiles, codes the tiles of tiff.hip: every segment a final block of its own)
 //   k_png_scan      one workgroup: the segments' places in the file, the Adler-32 of the whole stream, the 16-byte record and the header
 //   k_png_gather    one workgroup per segment: the finished IDAT (length, tag, bytes, CRC-32) copied to its place, IEND behind the last
 // The segments are byte aligned (an empty stored block behind a dynamic one) and share no history, which is what makes them parallel.
@@ -265,6 +266,8 @@ __device__ void canonical_codes(const unsigned char *lens, uint32_t nsym, uint32
 // Lane t owns the bytes [t * per, (t + 1) * per) of the segment (per a multiple of 16, 256 * per >= seg).  The segment's bytes
 // (lens[it] of them, at most n + 5: the stored form) go to segbuf + it * stride; adl[it] = its own Adler-32 (a | b << 16).
 // Dynamic LDS: the bit buffer, (seg + 8) / 4 + 2 words.
+// TILES (tiff.hip): every segment is a stream of its own, so each one ends like the last — BFINAL set, no empty stored block behind it.
+template <bool TILES>
 __global__ void __launch_bounds__(256)
 k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, uint32_t nseg, uint32_t per,
               unsigned char *__restrict__ segbuf, uint32_t stride, uint32_t *__restrict__ lens, uint32_t *__restrict__ adl)
@@ -277,7 +280,7 @@ k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, 
     enum { kMatches = 0, kSum1, kSum2, kNseq, kHdrBits, kHclen, kHlit };
     const uint32_t t = threadIdx.x, it = blockIdx.x;
     const uint32_t base = it * seg, n = min(seg, F - base);
-    const bool last = it + 1u == nseg;
+    const bool last = TILES || it + 1u == nseg;
     const unsigned char *sp = filt + base;
     const uint32_t lo = min(t * per, n), hi = min(lo + per, n);
     for (uint32_t i = t; i < kSymPad; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;      // one end-of-block
@@ -616,9 +619,16 @@ void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uin
         if (channels == 4) hipLaunchKernelGGL((k_png_filter_x<4, 16, false>), fgrid, dim3(256), 0, st, src, w, l.rowlen, F, (const unsigned char *)nullptr, filt);
         else hipLaunchKernelGGL((k_png_filter_x<3, 16, false>), fgrid, dim3(256), 0, st, src, w, l.rowlen, F, (const unsigned char *)nullptr, filt);
     }
-    hipLaunchKernelGGL(k_png_segment, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 8u) / 4u + 2u), st, (const unsigned char *)filt, F, seg,
+    hipLaunchKernelGGL(k_png_segment<false>, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 8u) / 4u + 2u), st, (const unsigned char *)filt, F, seg,
                        l.nseg, l.per, segbuf, l.stride, lens, adl);
     hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(1024), 0, st, lens, adl, l.nseg, seg, F, offs, info, out, (u64)cap, hdr);
     hipLaunchKernelGGL(k_png_gather, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 5u + 38u + 3u) / 4u + 2u), st, segbuf, l.stride, lens, offs, info,
                        l.nseg, out);
+}
+
+void launch_deflate_tiles(hipStream_t st, const unsigned char *bytes, uint32_t tile_bytes, uint32_t ntiles, unsigned char *segbuf, uint32_t stride,
+                          uint32_t *lens, uint32_t *adl)
+{
+    hipLaunchKernelGGL(k_png_segment<true>, dim3(ntiles), dim3(256), 4 * (size_t)((tile_bytes + 8u) / 4u + 2u), st, bytes, ntiles * tile_bytes, tile_bytes,
+                       ntiles, 16u * ((tile_bytes + 4095u) / 4096u), segbuf, stride, lens, adl);
 }

@@ -2,8 +2,8 @@
 Output modules: pixel-format conversion on device, copy to host, encode.
 
 Role of cuburn/output.py:21-136,411-434: 8-bit RGBA (jpeg / png / raw) and 16-bit RGBA (tiff /
-raw16) stills here; the outputs that pipe frames into a video encoder (x264, vpxenc, ffmpeg) are
-in encoders.py.
+raw16) stills here, on the host or encoded on the device; the outputs that pipe frames into a
+video encoder (x264, vpxenc, ffmpeg) are in encoders.py.
 """
 import io
 import struct
@@ -263,6 +263,27 @@ class TiffOutput(Output):
         return {'.tiff': io.BytesIO(_tiff_bytes(buf if self.alpha else buf[:, :, :3]))}, []
 
 
+class DeviceTIFFOutput(DeviceEncodedOutput):
+    """TIFF stills encoded on the device (``output: {"type": "tiff", "compression": "deflate", "alpha": bool}``): the samples of
+    ``TiffOutput`` in a tiled file, Adobe deflate with the horizontal predictor (include/flame_hip.h, fl_output_tiff).  A profile
+    gives 16 bits; ``bits=8`` writes the samples of the 8-bit outputs.  The record's parameter is a tile's bytes."""
+    suffix, entry, noun = '.tiff', 'fl_output_tiff', 'TIFF file'
+
+    def __init__(self, alpha=False, bits=16):
+        if not isinstance(alpha, bool):
+            raise ValueError('output.alpha must be true or false')
+        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
+            raise ValueError('bits must be 8 or 16')
+        self.alpha, self.channels, self.bits = alpha, 4 if alpha else 3, bits
+
+    def arguments(self):
+        return (self.channels, self.bits)
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (noise is stored, at 12 bytes per tile above its own size)."""
+        return int(_lib.load().fl_tiff_bound(dim.w, dim.h, self.channels, self.bits))
+
+
 class RawOutput(Output):
     suffix = '.rgba8'
 
@@ -290,6 +311,12 @@ def get_output_for_profile(gprof):
         for key in ('bits', 'filter'):
             if key in opts:
                 raise ValueError('output.%s: only the device PNG encoder takes it: set "encoder": "device" on a png output' % key)
+    compression = opts.pop('compression', None)
+    if compression is not None:
+        if handler != 'tiff':
+            raise ValueError('output.compression: only tiff takes it, not "%s"' % handler)
+        if not isinstance(compression, str) or compression not in ('none', 'deflate'):
+            raise ValueError('output.compression must be "none" or "deflate", not "%s"' % (compression,))
     if opts.pop('device', False):
         if handler != 'jpeg':
             raise ValueError('output.device: only jpeg is encoded on the device, not "%s"' % handler)
@@ -310,6 +337,10 @@ def get_output_for_profile(gprof):
     if handler in ('jpeg', 'png'):
         return PILOutput(codec=handler, **opts)
     if handler == 'tiff':
+        if compression == 'deflate':                     # the device's file; "none", or no key: the host writer, as before
+            if set(opts) - {'alpha'}:
+                raise ValueError('output.compression: the device TIFF encoder takes "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha'})))
+            return DeviceTIFFOutput(**opts)
         return TiffOutput(**opts)
     if handler == 'raw':
         return RawOutput()

@@ -64,6 +64,9 @@ def add_args(parser=None):
     out.add_argument('--png-filter', choices=['paeth', 'adaptive'],
                      help='Row filter of device-encoded png stills: Paeth on every row, or per row the type of least '
                           'sum of absolute residuals (sets output.filter)')
+    out.add_argument('--tiff-compression', choices=['none', 'deflate'],
+                     help='tiff stills: "deflate" encodes them on the GPU (tiled, Adobe deflate, horizontal predictor), "none" is '
+                          'the uncompressed file the host writes (sets output.compression)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -101,6 +104,8 @@ def get_from_args(args):
         prof['output'] = dict(prof.get('output') or {}, bits=ns['bits'])
     if ns.get('png_filter') is not None:
         prof['output'] = dict(prof.get('output') or {}, filter=ns['png_filter'])
+    if ns.get('tiff_compression') is not None:
+        prof['output'] = dict(prof.get('output') or {}, compression=ns['tiff_compression'])
     return name, prof
 
 

@@ -374,6 +374,38 @@ int fl_png_encode_f(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int c
 int fl_output_png_f(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, unsigned flags,
                     void *host_out, uint64_t dev_out, size_t cap);
 
+/* TIFF stills encoded on the device: classic little-endian TIFF with one IFD, tiled; Compression 8 (Adobe
+ * deflate), Predictor 2, PlanarConfiguration 1, Photometric 2; samples of `bits` = 8 or 16, `channels` = 3 or 4 (4 adds
+ * ExtraSamples = 2, unassociated alpha).  TileLength is 64, TileWidth 128 at 8 bits and 64 at 16: a tile holds
+ * TileWidth * 64 * channels * bits / 8 = 24576 or 32768 bytes.  Tiles run row-major, nt = ceil(w / TileWidth) * ceil(h / 64)
+ * of them; a tile sample at (x, y) outside the image is the source sample at (min(x, w - 1), min(y, h - 1)).  Within a tile
+ * row the first pixel is stored as is and every later sample is (s[x] - s[x - 1]) mod 2^bits against the same channel of the pixel
+ * to its left in the tile (16-bit word arithmetic at 16 bits); 16-bit values are stored low byte first.
+ * The source is u8 / u16 [h][w][4] as FL_OUT_RGBA8 / FL_OUT_RGBA16 write them (channels 3 leaves the alpha sample out).
+ * A tile's data: 78 01, one deflate block with BFINAL set — dynamic Huffman holding literals and matches of distance 1, coded as
+ * the PNG encoder codes a last segment, or stored when the dynamic form would not be smaller —, then the Adler-32 of the tile's
+ * predicted bytes, most significant byte first.  Tiles share no history.
+ * The file: bytes 0..7 (II, 42, 8); the entry count, the entries in ascending tag order (256 ImageWidth, 257 ImageLength,
+ * 258 BitsPerSample, 259 Compression, 262 Photometric, 277 SamplesPerPixel, 284 PlanarConfiguration, 317 Predictor, 322 TileWidth,
+ * 323 TileLength, 324 TileOffsets, 325 TileByteCounts, and 338 ExtraSamples with channels 4; widths, lengths, offsets and counts
+ * are LONGs, the rest SHORTs) and a next-IFD of 0; the BitsPerSample array; only when nt > 1 TileOffsets and TileByteCounts, nt
+ * LONGs each (with nt = 1 both values sit in their entries); the tiles in order, each at an even offset: one zero byte follows
+ * a tile of odd length, except the last.  The same pixels, size, channels and bits give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status, u32 the
+ * bytes of a tile, u32 0, and behind it the file; status, the capacity rule and the destinations are the PNG encoder's.
+ * fl_tiff_bound: the all-stored worst case — 16 for the record, H, and nt * (tile bytes + 5 + 6 + 1), where the header H is
+ * 8 + 2 + 12 * entries + 4 + 2 * channels, plus 8 * nt when nt > 1; 0 for w or h of 0 or above 65535, channels other than 3 or
+ * 4, bits other than 8 or 16, or a result beyond 2^32 - 1.
+ * fl_tiff_encode: queued on the current lane's stream.
+ * fl_output_tiff: fl_output(FL_OUT_RGBA16), or FL_OUT_RGBA8 for bits = 8, into the lane's pixel buffer (same draws, same dither
+ * states afterwards), then the encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: any case in which fl_tiff_bound is 0, a null src_dev, host_out and dev_out both null,
+ * cap < 16 + H. */
+size_t fl_tiff_bound(uint32_t w, uint32_t h, int channels, int bits);
+int fl_tiff_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits,
+                   void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_tiff(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -407,8 +439,8 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
 /* The same, split further: ms[0] iterate kernels, [1] tile accumulate, [2] flush, [3] all fl_filter calls,
  * [4] the DE proper — the eight direction kernels, the first normalising the accumulator, the last un-normalising it with a
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
- * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of both device encoders (fl_jpeg_encode,
- * fl_output_jpeg, fl_png_encode, fl_output_png; 0 when none ran). */
+ * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of the device encoders (fl_jpeg_encode,
+ * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
