@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('FLAME_HIP_LIB', LIB_PATH)
 (FL_OK, FL_E_INVAL, FL_E_NOMEM, FL_E_HIP, FL_E_NODEV, FL_E_UNSUPPORTED) = (0, -1, -2, -3, -4, -5)
 
 FILT = dict(yuv=0, bilateral=1, logscale=2, colorclip=3, smearclip=4, haloclip=5, plainclip=6, logencode=7, de=8)
-BUF = dict(front=0, back=1, params=2, palette=3, points=4, seeds=5, atom=6, hot=7, side=8)
+BUF = dict(front=0, back=1, params=2, palette=3, points=4, seeds=5, atom=6, hot=7, side=8, log=9, dir=10)
 ACCUM_ATOMIC, ACCUM_BINNED = 0, 1
 FL_OP_CHAOS_CDF = 11                # include/flame_hip.h (6): dst[0..nxf-1] <- row of the chaos matrix (xaos)
 FL_OP_OPACITY = 10                  # include/flame_hip.h (6): dst <- plot probability of the xform's samples
@@ -90,6 +90,10 @@ _SIGS = {
     'fl_debug_flush': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     'fl_debug_clear': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
     'fl_debug_clear_hot': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    'fl_debug_accum': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+    'fl_debug_accum_check': (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
     'fl_debug_shuffle': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     'fl_debug_counters': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fl_rtc_compile_check': (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),

@@ -290,7 +290,7 @@ static bool env_on(const char *name) { const char *e = getenv(name); return e &&
 int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds, uint32_t nslots, fl_ctx **out)
 {
     REQUIRE(out && seeds, "null argument");
-    REQUIRE((nslots >= FL_NTEMPORAL || nslots == FL_NTEMPORAL / 2 || nslots == FL_NTEMPORAL / 4) && nslots % 256 == 0 && nslots <= 16384,
+    REQUIRE(nslots_valid(nslots),
             "nslots must be a multiple of 256 in [1024, 16384] (or 512 slots of 8 waves / 256 of 16: two / four temporal samples per workgroup)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FL_E_NODEV, "no HIP device", __FILE__, __LINE__);
@@ -1374,6 +1374,8 @@ static int buf_ptr(fl_ctx *c, int which, void **p, size_t *cap)
     case FL_BUF_SEEDS: is(c->d_rng); break;
     case FL_BUF_ATOM: is(ln.d_atom); break;
     case FL_BUF_HOT: is(ln.d_hot); break;
+    case FL_BUF_LOG: is(ln.d_log[0]); break;
+    case FL_BUF_DIR: is(ln.d_dir[0]); break;
     default: return fail(FL_E_INVAL, "unknown buffer", __FILE__, __LINE__);
     }
     if (!*p) return fail(FL_E_INVAL, "buffer not allocated yet", __FILE__, __LINE__);
@@ -1482,6 +1484,42 @@ int fl_debug_flush(fl_ctx *c, uint32_t w, uint32_t h)
     if (rc) return rc;
     if ((rc = flush_pending(c, ln))) return rc;
     return do_flush(c, ln, d);
+}
+
+int fl_debug_accum_check(uint32_t w, uint32_t h, const uint32_t *log, size_t log_words, const uint32_t *dir, size_t dir_words,
+                          uint32_t nbatch_total, uint32_t batch_records, uint32_t nslots, uint32_t nparts, int wide)
+{
+    fl_dim d;
+    BinLayout b;
+    const char *why = accum_log_check(w, h, log, log_words, dir, dir_words, nbatch_total, batch_records, nslots, nparts, wide, &d, &b);
+    return why ? fail(FL_E_INVAL, why, __FILE__, __LINE__) : (int)FL_OK;
+}
+
+int fl_debug_accum(fl_ctx *c, uint32_t w, uint32_t h, const uint32_t *log, size_t log_words, const uint32_t *dir, size_t dir_words,
+                   uint32_t nbatch_total, uint32_t batch_records, uint32_t nslots, uint32_t nparts, int wide)
+{
+    REQUIRE(c, "null ctx");
+    // nothing reaches the device unless the kernels are written for it (launch_plan.h)
+    fl_dim d;
+    BinLayout bl;
+    if (const char *why = accum_log_check(w, h, log, log_words, dir, dir_words, nbatch_total, batch_records, nslots, nparts, wide, &d, &bl))
+        return fail(FL_E_INVAL, why, __FILE__, __LINE__);
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    int rc = ensure_fb(ln, w, h, &d);
+    if (rc) return rc;
+    if ((rc = flush_pending(c, ln))) return rc;
+    const auto quiesce = [&ln] { return ln.quiesce(true); };
+    if ((rc = ln.d_log[0].reserve(log_words, "sample log", quiesce))) return rc;
+    if ((rc = ln.d_dir[0].reserve(dir_words, "sample log directory", quiesce))) return rc;
+    if ((rc = quiesce())) return rc;                        // whatever still reads set 0
+    HIPCHK(hipMemcpy(ln.d_log[0], log, 4 * log_words, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ln.d_dir[0], dir, 4 * dir_words, hipMemcpyHostToDevice));
+    // do_iter_launch's call: the lane's palette, packed cells and front buffer; no clear in front of it, no flush behind it
+    launch_accum_tiles(ln.stream, ln.d_log[0], ln.d_dir[0], ln.d_palette, ln.d_atom, (float *)ln.d_front.p, bl.tiles_x, bl.nbins,
+                       nparts, nbatch_total, batch_records, nslots, d.astride, d.ah, bl.wide);
+    HIPCHK(hipGetLastError());
+    return FL_OK;
 }
 
 int fl_debug_clear_hot(fl_ctx *c, uint32_t w, uint32_t h)

@@ -53,6 +53,68 @@ static inline BinSet bin_set(const BinLayout &b, uint64_t write_rounds, uint32_t
     return s;
 }
 
+// Slot counts a context can be created with: a multiple of 256 from 1024 up, or 512 / 256 slots whose 8- / 16-wave workgroups walk
+// two / four temporal samples each
+static inline bool nslots_valid(uint32_t nslots)
+{
+    return (nslots >= FL_NTEMPORAL || nslots == FL_NTEMPORAL / 2 || nslots == FL_NTEMPORAL / 4) && nslots % 256 == 0 && nslots <= 16384;
+}
+
+// fl_debug_accum's gate: may the tile accumulate (binned.hip) be launched on this log + directory?  Null if so, else the reason.
+// The kernels trust their input — the run lookup, the LDS tile and the spills of full and hot cells take every index as it comes
+// (only the tile add tests px < astride, py < aheight) — so everything they rely on is established here, on the host, record by
+// record: sizes as bin_set gives them, runs of a batch contiguous and ascending by tile and inside the batch, every record a run
+// owns in a cell of the accumulator (256x64 tiles: nothing above the record's 22 bits, which would index past the LDS tile).
+// Slots no run owns may hold anything.  `d` and `b` receive the frame and tile geometry the launch is to use.
+static inline const char *accum_log_check(uint32_t w, uint32_t h, const uint32_t *log, size_t log_words, const uint32_t *dir, size_t dir_words,
+                                          uint32_t nbatch_total, uint32_t batch_records, uint32_t nslots, uint32_t nparts, int wide,
+                                          fl_dim *d, BinLayout *b)
+{
+    if (!log || !dir) return "null log or directory";
+    if (!w || !h || w > 32768u || h > 32768u) return "image size out of range";
+    if (!nslots_valid(nslots)) return "nslots is not a slot count of fl_ctx_create";
+    if (!nbatch_total || nbatch_total % nslots) return "nbatch_total must be a positive multiple of nslots";
+    if (nbatch_total / nslots > 16384u) return "more than 16384 batches per slot";
+    if (batch_records < 1u || batch_records > 16384u) return "batch_records outside 1..16384";
+    if (nparts < 1u || nparts > 64u) return "nparts outside 1..64";
+    *d = calc_dim(w, h);
+    *b = bin_layout(*d, 1, 1, wide != 0);
+    if (b->wide != (wide != 0)) return "more 128x64 tiles than a record can name: the image needs 256x64 tiles";
+    if (b->nbins > FL_MAX_BINS_WIDE) return "image too large for the binned accumulate (> 8191 tiles of 256x64)";
+    const uint32_t bw = fl_pack3_words(batch_records);
+    b->region = !b->wide && FL_LOG_PACK3 ? 2 * (size_t)bw : (size_t)batch_records;
+    // (a step of the packed accumulate whose lanes lie past the group's end reads the 64 words that follow the group's first: they
+    // must lie inside the log, the 8 spare words included, for a group that starts in the last batch too)
+    if (!b->wide && FL_LOG_PACK3 && bw + 4u < 64u) return "packed batch regions shorter than 60 words";
+    const BinSet s = bin_set(*b, nbatch_total / nslots, 1, nslots);
+    if (s.nbatch != nbatch_total || log_words != s.log_words || dir_words != s.dir_words) return "log or directory size is not what bin_set gives";
+    const uint32_t twl = b->wide ? FL_TILE_W_WIDE_LOG2 : 7u;
+    for (uint32_t batch = 0; batch < nbatch_total; ++batch) {
+        const uint32_t *reg = log + (size_t)batch * b->region;
+        uint32_t expect = 0;
+        for (uint32_t t = 0; t < b->nbins; ++t) {
+            const uint32_t e = dir[(size_t)t * nbatch_total + batch], first = e >> 16, count = e & 0xffffu;
+            if (t && first != expect) return "runs of a batch are not contiguous and ascending by tile";
+            if (first + count > batch_records) return "a run ends outside its batch";
+            expect = first + count;
+            const uint32_t x0 = (t % b->tiles_x) << twl, y0 = (t / b->tiles_x) * FL_TILE_H;
+            for (uint32_t i = first; i < first + count; ++i) {
+                uint32_t rec;
+                if (!b->wide && FL_LOG_PACK3) {
+                    const uint64_t word = reg[2 * (i / 3u)] | (uint64_t)reg[2 * (i / 3u) + 1u] << 32;
+                    rec = (uint32_t)(word >> (FL_REC_BITS * (i % 3u))) & ((1u << FL_REC_BITS) - 1u);
+                } else {
+                    rec = reg[i];
+                    if (rec >> (8u + twl + FL_TILE_H_LOG2)) return "a record has bits above its cell";
+                }
+                const uint32_t off = rec >> 8, px = x0 + (off & ((1u << twl) - 1u)), py = y0 + (off >> twl);
+                if (px >= d->astride || py >= d->ah) return "a record's cell lies outside the accumulator";
+            }
+        }
+    }
+    return nullptr;
+}
+
 // Workgroups per tile of the accumulate: enough of them to fill the chip several times over (~8192 in all),
 // no more — every workgroup zeroes and drains a whole LDS tile whatever its share of records
 // (256x64 tiles, one workgroup per CU: twice as many — a dense region then spreads over more

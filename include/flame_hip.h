@@ -462,7 +462,9 @@ enum {
     FL_BUF_SEEDS = 5,   /* fl_mwc[nwalkers]                                                */
     FL_BUF_ATOM = 6,    /* u64[nbins] packed integer accumulator of the current side      */
     FL_BUF_HOT = 7,     /* u32[nbins/16] hot-pixel flags of the current side               */
-    FL_BUF_SIDE = 8     /* float4[nbins] side buffer                                       */
+    FL_BUF_SIDE = 8,    /* float4[nbins] side buffer                                       */
+    FL_BUF_LOG = 9,     /* u32[] sample log, set 0 of the lane (the set of a frame's first binned launch; csrc/binned.hip) */
+    FL_BUF_DIR = 10     /* u32[tiles][batches] its directory: (first record << 16) | count; both "not allocated yet" before a binned launch */
 };
 int fl_read_buffer(fl_ctx *ctx, fl_genome *g, int which, void *host_dst, size_t nbytes);
 int fl_write_buffer(fl_ctx *ctx, fl_genome *g, int which, const void *host_src, size_t nbytes);
@@ -498,6 +500,23 @@ int fl_debug_iter_launch(fl_ctx *ctx, fl_genome *g, uint32_t w, uint32_t h, uint
 int fl_debug_flush(fl_ctx *ctx, uint32_t w, uint32_t h);
 int fl_debug_clear(fl_ctx *ctx, uint32_t w, uint32_t h, int reset_points);
 int fl_debug_clear_hot(fl_ctx *ctx, uint32_t w, uint32_t h);
+/* Accumulate tap: run the tile accumulate of the binned mode (csrc/binned.hip) on a sample log and directory the caller built, exactly
+ * as a binned iterate launch runs it on its own — the lane's palette (FL_BUF_PALETTE), packed cells and front buffer; no clear
+ * before, no flush after.  The log goes into set 0 (FL_BUF_LOG / FL_BUF_DIR).  Geometry: the w x h frame in 128x64 tiles (wide = 0)
+ * or 256x64 tiles (wide = 1); nbatch_total batches (slot-major: batch / (nbatch_total / nslots) is the slot, its palette row
+ * slot * 64 / nslots) of batch_records records — three 21-bit records per 64-bit word in regions of fl_pack3_words words (128x64
+ * tiles), one 22-bit record per 32-bit word (256x64) —, log_words = nbatch_total * region + 8, dir_words = tiles * nbatch_total;
+ * nparts workgroups per tile.  Slots of the log no run owns may hold anything.
+ * The kernels trust their input, so the call refuses with FL_E_INVAL, on the host and before anything reaches the device: an
+ * nslots fl_ctx_create refuses; nbatch_total that is zero or no multiple of nslots; batch_records outside 1..16384 (or, 128x64
+ * tiles, regions of fewer than 60 words); nparts outside 1..64; wide = 0 for a frame of more than 2047 narrow tiles; sizes other
+ * than the above; a run with first + count > batch_records; runs of a batch that are not contiguous and ascending by tile
+ * (first[t + 1] == first[t] + count[t]); a record owned by a run whose cell lies outside astride x aheight (256x64 tiles: or with
+ * bits above its 22).  fl_debug_accum_check is the gate alone: it needs no context and no device. */
+int fl_debug_accum(fl_ctx *ctx, uint32_t w, uint32_t h, const uint32_t *log, size_t log_words, const uint32_t *dir, size_t dir_words,
+                   uint32_t nbatch_total, uint32_t batch_records, uint32_t nslots, uint32_t nparts, int wide);
+int fl_debug_accum_check(uint32_t w, uint32_t h, const uint32_t *log, size_t log_words, const uint32_t *dir, size_t dir_words,
+                         uint32_t nbatch_total, uint32_t batch_records, uint32_t nslots, uint32_t nparts, int wide);
 /* Point-shuffle tap: out[dst_thread] = src_thread after one swap with round counter `round`. */
 int fl_debug_shuffle(fl_ctx *ctx, uint32_t round, uint32_t *out256);
 /* Xform tap: apply xform `xfi` (nxf = the final xform) of temporal sample `ts` once to n points
