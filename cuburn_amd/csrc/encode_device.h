@@ -1,4 +1,4 @@
-// encode_device.h — device helpers the still encoders share (jpeg.hip, png.hip, tiff.hip).  DESIGN.md §4.8 "What the encoders share".
+// encode_device.h — device helpers the still encoders share (jpeg.hip, png.hip, tiff.hip, exr.hip).  DESIGN.md §4.8 "What the encoders share".
 #pragma once
 #include "kernels.h"
 

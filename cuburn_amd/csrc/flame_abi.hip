@@ -1253,6 +1253,61 @@ int fl_output_tiff(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, vo
     return close_frame(c, ln);
 }
 
+// ---- OpenEXR ----
+// No file can be longer, and a file of noise is exactly this long: every tile raw behind the 20 bytes of its chunk's head and the
+// 8 of its place in the offset table.  A zlib stream is only chosen where it is smaller.
+size_t fl_exr_bound(uint32_t w, uint32_t h, int channels, int pixel)
+{
+    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4) || (pixel != FL_EXR_HALF && pixel != FL_EXR_FLOAT)) return 0;
+    const ExrLayout l = exr_layout(w, h, channels, pixel);
+    const uint64_t n = 16u + l.H + 20ull * l.nt + l.raw;
+    return n > 0xffffffffull ? 0 : (size_t)n;
+}
+
+static int check_exr(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int pixel, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    REQUIRE(c, "null ctx");
+    REQUIRE(channels == 3 || channels == 4, "exr: channels must be 3 or 4");
+    REQUIRE(pixel == FL_EXR_HALF || pixel == FL_EXR_FLOAT, "exr: pixel must be FL_EXR_HALF or FL_EXR_FLOAT");
+    const bool sides = w >= 1 && h >= 1 && w <= 65535u && h <= 65535u;      // (check_encode refuses the others before it looks at the header)
+    if (int rc = check_encode(c, "exr", w, h, sides ? (size_t)exr_layout(w, h, channels, pixel).H : 0, host_out, dev_out, cap)) return rc;
+    REQUIRE(fl_exr_bound(w, h, channels, pixel) != 0, "exr: the file could pass 2^32 - 1 bytes");
+    return FL_OK;
+}
+
+static int exr_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const float4 *src, uint32_t src_stride, int channels, int pixel,
+                         void *host_out, uint64_t dev_out, size_t cap)
+{
+    return encode_on(c, ln, host_out, dev_out, cap, fl_exr_bound(w, h, channels, pixel), exr_layout(w, h, channels, pixel).words, "exr file",
+                     "exr scratch", [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) {
+                         launch_exr_encode(st, src, src_stride, w, h, channels, pixel, scratch, dst, cap);
+                     });
+}
+
+int fl_exr_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, uint32_t src_stride, int channels, int pixel, void *host_out,
+                  uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_exr(c, w, h, channels, pixel, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "exr: null source pixels");
+    REQUIRE(src_stride >= w, "exr: the source's stride is below the width");
+    HIPCHK(hipSetDevice(c->device));
+    return exr_encode_on(c, c->lane(), w, h, (const float4 *)(uintptr_t)src_dev, src_stride, channels, pixel, host_out, dev_out, cap);
+}
+
+// The front buffer itself is the source: no conversion pass, no dither draw, so nothing of the state the lanes share is touched.
+int fl_output_exr(fl_ctx *c, uint32_t w, uint32_t h, int channels, int pixel, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_exr(c, w, h, channels, pixel, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim d;
+    if (int rc = ensure_fb(ln, w, h, &d)) return rc;
+    if (int rc = flush_pending(c, ln)) return rc;             // deferred ends of the filter chain
+    const float4 *src = (const float4 *)ln.d_front.p + (size_t)d.astride * FL_GUTTER + FL_GUTTER;
+    if (int rc = exr_encode_on(c, ln, w, h, src, d.astride, channels, pixel, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
+}
+
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
                 uint32_t *nvalid)
 {

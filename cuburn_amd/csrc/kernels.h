@@ -151,6 +151,22 @@ TiffLayout tiff_layout(uint32_t w, uint32_t h, int channels, int bits);
 void launch_tiff_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, uint32_t *scratch,
                         unsigned char *out, size_t cap);
 
+// The coder once more for pieces of unequal length (exr.hip): piece i is the lens[i] bytes (1 .. tile_bytes) at bytes + i * tile_bytes;
+// lens[i] comes back as the block's bytes (at most the piece's + 5).
+void launch_deflate_pieces(hipStream_t st, const unsigned char *bytes, uint32_t tile_bytes, uint32_t ntiles, unsigned char *segbuf, uint32_t stride,
+                           uint32_t *lens, uint32_t *adl);
+
+// exr.hip: tiled OpenEXR, ZIP, HALF or FLOAT samples, from f32 [h][src_stride][4].  `scratch` holds exr_layout().words
+// words; the 16-byte record, the header, the offset table and the chunks go to `out`, of which nothing at or beyond `cap`
+// (>= 16 + exr_layout().H) is touched.  Tiles are 64 pixels wide and 64 (HALF) or 32 (FLOAT) rows high, cropped to the image.
+#define FL_EXR_TILE_WIDTH 64u
+#define FL_EXR_TILE_ROWS_HALF 64u
+#define FL_EXR_TILE_ROWS_FLOAT 32u
+struct ExrLayout { uint32_t th, tiles_x, nt, tile_bytes, stride, header; uint64_t H, raw; size_t staged, segbuf, offs, lens, adl, info, words; };      // tile rows, tiles per row / in all, bytes of a full tile, bytes between coded tiles, bytes of the header; bytes before the chunks, of all samples; word offsets into the scratch
+ExrLayout exr_layout(uint32_t w, uint32_t h, int channels, int pixel);
+void launch_exr_encode(hipStream_t st, const float4 *src, uint32_t src_stride, uint32_t w, uint32_t h, int channels, int pixel, uint32_t *scratch,
+                       unsigned char *out, size_t cap);
+
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)
 
 // sort.hip: one stable radix pass (nbits <= 10 at lo_bit) over n keys; hist = scratch of

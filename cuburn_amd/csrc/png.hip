@@ -6,7 +6,8 @@
 //   k_png_segment   one workgroup per segment of `seg` filtered bytes, coded with no reference before its start: tokens (literal / run
 //                   of distance 1) -> histogram -> length-limited Huffman code -> one dynamic block packed in LDS, or one stored block
 //                   when that is no smaller (decided from the counted bits, before anything is emitted); the segment's Adler-32 parts
-//                   (its TILES form, launch_deflate_tiles, codes the tiles of tiff.hip: every segment a final block of its own)
+//                   (its TILES form, launch_deflate_tiles, codes the tiles of tiff.hip: every segment a final block of its own;
+//                   with LENS, launch_deflate_pieces, the cropped tiles of exr.hip, each of its own length)
 //   k_png_scan      one workgroup: the segments' places in the file, the Adler-32 of the whole stream, the 16-byte record and the header
 //   k_png_gather    one workgroup per segment: the finished IDAT (length, tag, bytes, CRC-32) copied to its place, IEND behind the last
 // The segments are byte aligned (an empty stored block behind a dynamic one) and share no history, which is what makes them parallel.
@@ -267,7 +268,8 @@ __device__ void canonical_codes(const unsigned char *lens, uint32_t nsym, uint32
 // (lens[it] of them, at most n + 5: the stored form) go to segbuf + it * stride; adl[it] = its own Adler-32 (a | b << 16).
 // Dynamic LDS: the bit buffer, (seg + 8) / 4 + 2 words.
 // TILES (tiff.hip): every segment is a stream of its own, so each one ends like the last — BFINAL set, no empty stored block behind it.
-template <bool TILES>
+// LENS (exr.hip, with TILES): segment `it` holds lens[it] bytes (1 .. seg) where the kernel starts, not min(seg, F - base).
+template <bool TILES, bool LENS = false>
 __global__ void __launch_bounds__(256)
 k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, uint32_t nseg, uint32_t per,
               unsigned char *__restrict__ segbuf, uint32_t stride, uint32_t *__restrict__ lens, uint32_t *__restrict__ adl)
@@ -279,9 +281,9 @@ k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, 
     __shared__ HuffTmp T;
     enum { kMatches = 0, kSum1, kSum2, kNseq, kHdrBits, kHclen, kHlit };
     const uint32_t t = threadIdx.x, it = blockIdx.x;
-    const uint32_t base = it * seg, n = min(seg, F - base);
+    const uint32_t base = it * seg, n = LENS ? lens[it] : min(seg, F - base);
     const bool last = TILES || it + 1u == nseg;
-    const unsigned char *sp = filt + base;
+    const unsigned char *sp = LENS ? filt + (size_t)it * seg : filt + base;
     const uint32_t lo = min(t * per, n), hi = min(lo + per, n);
     for (uint32_t i = t; i < kSymPad; i += 256u) s_hist[i] = i == 256u ? 1u : 0u;      // one end-of-block
     if (t < kClSyms) s_clfreq[t] = 0;
@@ -630,5 +632,12 @@ void launch_deflate_tiles(hipStream_t st, const unsigned char *bytes, uint32_t t
                           uint32_t *lens, uint32_t *adl)
 {
     hipLaunchKernelGGL(k_png_segment<true>, dim3(ntiles), dim3(256), 4 * (size_t)((tile_bytes + 8u) / 4u + 2u), st, bytes, ntiles * tile_bytes, tile_bytes,
+                       ntiles, 16u * ((tile_bytes + 4095u) / 4096u), segbuf, stride, lens, adl);
+}
+
+void launch_deflate_pieces(hipStream_t st, const unsigned char *bytes, uint32_t tile_bytes, uint32_t ntiles, unsigned char *segbuf, uint32_t stride,
+                           uint32_t *lens, uint32_t *adl)
+{
+    hipLaunchKernelGGL((k_png_segment<true, true>), dim3(ntiles), dim3(256), 4 * (size_t)((tile_bytes + 8u) / 4u + 2u), st, bytes, 0u, tile_bytes,
                        ntiles, 16u * ((tile_bytes + 4095u) / 4096u), segbuf, stride, lens, adl);
 }

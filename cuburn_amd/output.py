@@ -284,6 +284,27 @@ class DeviceTIFFOutput(DeviceEncodedOutput):
         return int(_lib.load().fl_tiff_bound(dim.w, dim.h, self.channels, self.bits))
 
 
+class DeviceEXROutput(DeviceEncodedOutput):
+    """OpenEXR stills encoded on the device (``output: {"type": "exr", "pixel": "half" | "float", "alpha": bool}``): the float
+    picture as the filter chain left it, with no dither and no clamp, in a tiled ZIP file (include/flame_hip.h, fl_output_exr).
+    There is no host writer behind it.  The record's parameter is a full tile's bytes."""
+    suffix, entry, noun = '.exr', 'fl_output_exr', 'OpenEXR file'
+
+    def __init__(self, alpha=False, pixel='half'):
+        if not isinstance(alpha, bool):
+            raise ValueError('output.alpha must be true or false')
+        if not isinstance(pixel, str) or pixel not in _lib.EXR_PIXELS:
+            raise ValueError('output.pixel must be "half" or "float", not "%s"' % (pixel,))
+        self.alpha, self.channels, self.pixel = alpha, 4 if alpha else 3, pixel
+
+    def arguments(self):
+        return (self.channels, _lib.EXR_PIXELS[self.pixel])
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (a file of noise is exactly that long)."""
+        return int(_lib.load().fl_exr_bound(dim.w, dim.h, self.channels, _lib.EXR_PIXELS[self.pixel]))
+
+
 class RawOutput(Output):
     suffix = '.rgba8'
 
@@ -298,7 +319,7 @@ _VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg')
 
 
 def get_suffix(codec, alpha=False):
-    ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', raw='.rgba8', raw16='.rgba16', x264='.h264',
+    ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', exr='.exr', raw='.rgba8', raw16='.rgba16', x264='.h264',
                prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi')[codec]
     return ('_color' + ext) if alpha else ext
 
@@ -307,6 +328,12 @@ def get_output_for_profile(gprof):
     """Output module for the profile's ``output`` block (cuburn/output.py:421-436)."""
     opts = dict(gprof.output.raw())
     handler = opts.pop('type', 'jpeg')
+    if handler == 'exr':                                 # the device's file and nothing else: no key of another encoder means anything here
+        if set(opts) - {'alpha', 'pixel'}:
+            raise ValueError('the device OpenEXR encoder takes "pixel" and "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha', 'pixel'})))
+        return DeviceEXROutput(**opts)
+    if 'pixel' in opts:
+        raise ValueError('output.pixel: only exr takes it, not "%s"' % handler)
     if not (handler == 'png' and opts.get('encoder') == 'device'):
         for key in ('bits', 'filter'):
             if key in opts:

@@ -51,7 +51,7 @@ def add_args(parser=None):
                      help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
-    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'raw'])
+    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')
@@ -67,6 +67,9 @@ def add_args(parser=None):
     out.add_argument('--tiff-compression', choices=['none', 'deflate'],
                      help='tiff stills: "deflate" encodes them on the GPU (tiled, Adobe deflate, horizontal predictor), "none" is '
                           'the uncompressed file the host writes (sets output.compression)')
+    out.add_argument('--exr-pixel', choices=['half', 'float'],
+                     help='exr stills (always encoded on the GPU: tiled, ZIP): 16-bit half samples, the default, or the '
+                          'accumulator\'s own 32-bit floats (sets output.pixel)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -106,6 +109,8 @@ def get_from_args(args):
         prof['output'] = dict(prof.get('output') or {}, filter=ns['png_filter'])
     if ns.get('tiff_compression') is not None:
         prof['output'] = dict(prof.get('output') or {}, compression=ns['tiff_compression'])
+    if ns.get('exr_pixel') is not None:
+        prof['output'] = dict(prof.get('output') or {}, pixel=ns['exr_pixel'])
     return name, prof
 
 

@@ -406,6 +406,46 @@ int fl_tiff_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int ch
                    void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_tiff(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap);
 
+/* OpenEXR stills encoded on the device: the float picture itself, not a display integer.  Single part, tiled,
+ * one level, little-endian throughout; integers are 32-bit unless stated.
+ * Bytes 0..7: 76 2f 31 01, then the version word 0x00000202 (version 2, the tiled bit 0x200).
+ * The header: attributes `name\0 type\0 size value` in this order, then a single 00:
+ *   channels / chlist: per channel in alphabetical order (A only with channels = 4, then B, G, R) name\0, the pixel type (1 HALF,
+ *     2 FLOAT), pLinear u8 = 0, three zero bytes, xSampling 1, ySampling 1; a 00 ends the list (18 bytes a channel, and 1);
+ *   compression / compression: one byte, 3 (ZIP);  dataWindow / box2i: 0, 0, w - 1, h - 1;  displayWindow / box2i: the same;
+ *   lineOrder / lineOrder: one byte, 0 (increasing Y);  pixelAspectRatio / float: 1.0;  screenWindowCenter / v2f: 0.0, 0.0;
+ *   screenWindowWidth / float: 1.0;  tiles / tiledesc: xSize u32 = 64, ySize u32 = TH, a mode byte 0 (one level, round down).
+ *   That is 341 bytes with 3 channels and 359 with 4.
+ * Tiles are 64 pixels wide and TH = 64 (HALF) or 32 (FLOAT) rows high: a full tile is 8192 * channels bytes at either depth.
+ * nx = ceil(w / 64), ny = ceil(h / TH), nt = nx * ny.  Tile (tx, ty) covers columns 64 tx .. and rows TH ty .., cropped to the
+ * image: tw = min(64, w - 64 tx) wide, th = min(TH, h - TH ty) high.  Nothing is padded.
+ * Behind the header the offset table: nt u64, ty-major, the position in the file of each tile's chunk.  Then the chunks in the
+ * same order with nothing between them: tileX, tileY, levelX = 0, levelY = 0, dataSize, and dataSize bytes.
+ * A tile's raw bytes (n = th * tw * channels * bytes per sample): row by row; within a row channel by channel in the chlist's
+ * order; within a channel the tw samples, low byte first.  R, G, B, A are .x, .y, .z, .w of the source's float4.
+ * A tile's data is the smaller of (a) a zlib stream 78 01, one final deflate block coded as the TIFF encoder codes a tile, and the
+ * Adler-32 of the block's input, most significant byte first, where that input d is the raw bytes after OpenEXR's two steps —
+ * t = the even-indexed raw bytes followed by the odd-indexed ones; d[0] = t[0], d[i] = (t[i] - t[i-1] + 128) mod 256 — and (b),
+ * whenever 2 + block + 4 >= n, the n raw bytes as they are.  A reader tells them apart by dataSize < n.
+ * Samples.  FLOAT: the source's 32 bits (NaN, infinities and denormals kept).  HALF: finite values rounded to nearest, ties to
+ * even, with gradual underflow; |x| >= 65520 and the infinities become +-65504 (7bff / fbff); NaN becomes 0000; -0 stays 8000.
+ * The same samples, size, channels and pixel type give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status, u32
+ * 8192 * channels, u32 0, and behind it the file; status, the capacity rule and the destinations are the PNG encoder's.
+ * fl_exr_bound: every tile raw, which is exact for such a file — 16 + the header + 28 * nt + w * h * channels * bytes per
+ * sample; 0 for w or h of 0 or above 65535, channels other than 3 or 4, an unknown pixel type, or a result beyond 2^32 - 1.
+ * fl_exr_encode: src_dev = f32 [h][src_stride][4], src_stride in pixels and at least w; queued on the current lane's stream.
+ * fl_output_exr: the lane's front buffer as the filter chain left it, read in place (FL_GUTTER rows and columns in), after the
+ * deferred ends of the chain have run.  It draws no dither: the output RNG states stay as they are.  Closes the frame as
+ * fl_output does.
+ * FL_E_INVAL, before anything is queued: any case in which fl_exr_bound is 0, a null src_dev, src_stride < w, host_out and
+ * dev_out both null, cap < 16 + the header + 8 * nt. */
+enum { FL_EXR_HALF = 1, FL_EXR_FLOAT = 2 };
+size_t fl_exr_bound(uint32_t w, uint32_t h, int channels, int pixel);
+int fl_exr_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, uint32_t src_stride, int channels, int pixel,
+                  void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_exr(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int pixel, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -440,7 +480,7 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
  * [4] the DE proper — the eight direction kernels, the first normalising the accumulator, the last un-normalising it with a
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
  * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of the device encoders (fl_jpeg_encode,
- * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff; 0 when none ran). */
+ * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff, fl_exr_encode, fl_output_exr; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
