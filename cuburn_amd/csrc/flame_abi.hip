@@ -192,6 +192,7 @@ struct fl_ctx {
     bool rtc_async = false;                 // FLAME_RTC_ASYNC=1: per-genome kernels are compiled by a worker thread; the interpreter kernel runs until they are there
     uint32_t jpeg_ri = FL_JPEG_RI;          // FLAME_JPEG_RI (1..21): MCUs per JPEG restart interval
     uint32_t jpeg_ri_420 = FL_JPEG_RI_420;  // ... in 4:2:0, where a value above 10 means 10
+    uint32_t gif_seg = FL_GIF_SEG;          // FLAME_GIF_SEG (256..3584): pixels per LZW segment of the GIF encoder
     uint32_t n_spec_launch = 0, n_interp_launch = 0;      // iterate launches by kernel since fl_timings_reset (fl_launch_stats)
     BinLayout layout(const fl_dim &d) const { return bin_layout(d, nw, bin_rounds, env_bin_wide); }
 };
@@ -323,6 +324,7 @@ int fl_ctx_create(int device, void *stream, const fl_mwc *seeds, uint32_t nseeds
     c->env_bin_wide = env_on("FLAME_BIN_WIDE");
     if (const char *e = getenv("FLAME_RTC")) c->use_rtc = strcmp(e, "0") != 0;
     c->rtc_async = env_on("FLAME_RTC_ASYNC");
+    c->gif_seg = gif_segment_pixels();
     if (const char *e = getenv("FLAME_JPEG_RI")) { const int v = atoi(e); if (v >= 1 && v <= 21) { c->jpeg_ri = (uint32_t)v; c->jpeg_ri_420 = std::min((uint32_t)v, FL_JPEG_RI_420_MAX); } }
     c->env_no_intra = env_on("FLAME_NO_INTRA_OVERLAP");      // launches of a frame strictly in series on one stream
     if (const char *e = getenv("FLAME_LAUNCH_ROUNDS")) { int v = atoi(e); if (v >= 16 && v <= 4096) c->launch_rounds = (uint32_t)(v / 16 * 16); }
@@ -1305,6 +1307,51 @@ int fl_output_exr(fl_ctx *c, uint32_t w, uint32_t h, int channels, int pixel, vo
     if (int rc = flush_pending(c, ln)) return rc;             // deferred ends of the filter chain
     const float4 *src = (const float4 *)ln.d_front.p + (size_t)d.astride * FL_GUTTER + FL_GUTTER;
     if (int rc = exr_encode_on(c, ln, w, h, src, d.astride, channels, pixel, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
+}
+
+// ---- GIF ----
+// No block can be longer: a segment of n pixels is CLEAR in 9 bits, at most n codes of at most 12, the closing code in 12 and at most
+// seven CLEARs of 9 as padding, 12 n + 84 bits, under 3 n / 2 + 11 bytes; segments are never shorter than 256 pixels but the last.
+size_t fl_gif_bound(uint32_t w, uint32_t h)
+{
+    if (!w || !h || w > 65535u || h > 65535u || (uint64_t)w * h > (1ull << 24)) return 0;
+    const uint64_t n = (uint64_t)w * h, T = (3u * n + 1u) / 2u + 11u * ((n + 255u) / 256u);
+    return (size_t)(16u + FL_GIF_HEADER_BYTES + T + (T + 254u) / 255u + 1u);
+}
+
+static int check_gif(const fl_ctx *c, uint32_t w, uint32_t h, int colors, int amp, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_encode(c, "gif", w, h, FL_GIF_HEADER_BYTES, host_out, dev_out, cap)) return rc;
+    REQUIRE(colors >= 2 && colors <= 256, "gif: colors must be 2..256");
+    REQUIRE(amp >= 0 && amp <= 64, "gif: dither_amp must be 0..64");
+    REQUIRE(fl_gif_bound(w, h) != 0, "gif: the frame has more than 2^24 pixels");
+    return FL_OK;
+}
+
+static int gif_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int colors, int amp, void *host_out,
+                         uint64_t dev_out, size_t cap)
+{
+    const uint32_t seg = c->gif_seg;
+    return encode_on(c, ln, host_out, dev_out, cap, fl_gif_bound(w, h), gif_layout(w, h, seg).words, "gif block", "gif scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_gif_encode(st, src, w, h, colors, amp, seg, scratch, dst, cap); });
+}
+
+int fl_gif_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "gif: null source pixels");
+    HIPCHK(hipSetDevice(c->device));
+    return gif_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, colors, dither_amp, host_out, dev_out, cap);
+}
+
+int fl_output_gif(fl_ctx *c, uint32_t w, uint32_t h, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = gif_encode_on(c, ln, w, h, ln.d_outpix, colors, dither_amp, host_out, dev_out, cap)) return rc;
     return close_frame(c, ln);
 }
 

@@ -167,6 +167,18 @@ ExrLayout exr_layout(uint32_t w, uint32_t h, int channels, int pixel);
 void launch_exr_encode(hipStream_t st, const float4 *src, uint32_t src_stride, uint32_t w, uint32_t h, int channels, int pixel, uint32_t *scratch,
                        unsigned char *out, size_t cap);
 
+// gif.hip: one GIF frame block — image descriptor, local colour table, LZW data — from u8 [h][w][4] (the alpha byte is ignored): median
+// cut by population over a histogram of 32768 cells, an inverse colour map, ordered dither, LZW in segments that each begin with a
+// clear code.  `scratch` holds gif_layout().words words; the 16-byte record and the block go to `out`, of which nothing
+// at or beyond `cap` (>= 16 + FL_GIF_HEADER_BYTES) is touched.  colors 2..256, amp 0..64, w * h <= 2^24; seg: pixels per segment, 256..3584.
+#define FL_GIF_SEG 1024u       // the default
+#define FL_GIF_LZW_TABLE_BYTES 32768u      // hash tables of one LZW workgroup: 4 segments a wave at the default, 16 at 256 pixels, 1 at 3584
+struct GifLayout { uint32_t npix, seg, nseg, stride, slots_log2, lanes; size_t hist, ccnt, pal, lut, idx, segbuf, offs, lens, info, words; };      // pixels, pixels per segment, segments, bytes between coded segments, log2 of a hash table's slots, segments per LZW workgroup; word offsets into the scratch
+uint32_t gif_segment_pixels();      // FL_GIF_SEG, or FLAME_GIF_SEG (measurements only)
+GifLayout gif_layout(uint32_t w, uint32_t h, uint32_t seg);
+void launch_gif_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int colors, int amp, uint32_t seg, uint32_t *scratch,
+                       unsigned char *out, size_t cap);
+
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)
 
 // sort.hip: one stable radix pass (nbits <= 10 at lo_bit) over n keys; hist = scratch of

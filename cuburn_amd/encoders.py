@@ -9,7 +9,8 @@ separate programs (x264, vpxenc, ffmpeg) found on PATH at the first frame — ``
 the program name, which is also how the tests drive the classes without them.
 
 MJPEGOutput needs no program: the device encodes every frame as a JPEG (output.DeviceJPEGOutput) and the host
-only puts the frames into an AVI file.
+only puts the frames into an AVI file.  GIFOutput needs none either: the device writes every frame's block, palette and
+LZW data included, and the host puts the blocks into a GIF89a file.
 """
 import fractions
 import struct
@@ -19,7 +20,7 @@ import tempfile
 import numpy as np
 
 from . import _lib
-from .output import DeviceJPEGOutput, Output
+from .output import DeviceEncodedOutput, DeviceJPEGOutput, Output
 
 
 class _EncoderPipe(object):
@@ -342,4 +343,78 @@ class MJPEGOutput(DeviceJPEGOutput):
             self._file.write(b'\0')
         self._sizes.append(n)
         self._movi += 8 + n + (n & 1)
+        return out
+
+
+def gif_delays(nframes, fps):
+    """Centiseconds of frames 0 .. nframes - 1: frame k lasts round(100 (k + 1) / fps) - round(100 k / fps), so the file keeps
+    the rate on average."""
+    return [int(round(100.0 * (k + 1) / fps)) - int(round(100.0 * k / fps)) for k in range(nframes)]
+
+
+class GIFOutput(DeviceEncodedOutput):
+    """Animations as a looping GIF89a file (``output: {"type": "gif", "colors": 2..256, "dither": "ordered" | "none",
+    "loop": 0..65535}``, ``--codec gif``): every frame leaves the GPU as a finished frame block with a palette of its own — median
+    cut, ordered dither, LZW (include/flame_hip.h, fl_output_gif) — and the host writes the header, the NETSCAPE2.0 loop
+    extension (``loop`` 0: forever), a graphic control extension with the frame's delay in front of every block, and the trailer.
+    ``encode(None)`` returns the file.  No external program.  A change of frame size flushes and starts a new file, as X264Output
+    does.  The record's parameter is the LZW segment's pixels."""
+    suffix, entry, noun = '.gif', 'fl_output_gif', 'GIF frame block'
+
+    def __init__(self, fps=24, colors=256, dither='ordered', loop=0):
+        if not fps > 0:
+            raise ValueError('gif needs fps above 0')
+        if fps > 50:
+            raise ValueError('gif: fps %g gives frames of less than 2 centiseconds, which browsers play at 10: use 50 or less' % fps)
+        if isinstance(colors, bool) or not isinstance(colors, int) or not 2 <= colors <= 256:
+            raise ValueError('output.colors must be an integer in 2..256')
+        if not isinstance(dither, str) or dither not in _lib.GIF_DITHER:
+            raise ValueError('output.dither must be "ordered" or "none", not "%s"' % (dither,))
+        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
+            raise ValueError('output.loop must be an integer in 0..65535')
+        self.fps, self.colors, self.dither, self.loop = fps, colors, dither, loop
+        self._file, self._nframes, self.framesize = None, 0, None
+
+    def arguments(self):
+        return (self.colors, _lib.GIF_DITHER[self.dither])
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (twelve bits a pixel and the segments' framing)."""
+        return int(_lib.load().fl_gif_bound(dim.w, dim.h))
+
+    def abort(self):
+        if self._file is not None:
+            self._file.close()
+        self._file, self._nframes = None, 0
+
+    def _flush(self):
+        if self._file is None:
+            return {}, []
+        f = self._file
+        f.write(b'\x3b')
+        f.seek(0)
+        self._file, self._nframes = None, 0
+        return {'.gif': f}, []
+
+    def encode(self, buf):
+        out = ({}, [])
+        if buf is None:
+            return self._flush()
+        data = self.file_bytes(buf, self.noun)
+        if len(data) < _lib.GIF_HEADER_BYTES + 2 or data[0] != 0x2c or data[9] != 0x87:
+            raise IOError('the frame is not a block of the device GIF encoder')
+        w, h = struct.unpack('<HH', bytes(data[5:9]))
+        if self.framesize != (h, w):
+            out = self._flush()
+            self.framesize = (h, w)
+        if self._file is None:
+            self._file = tempfile.TemporaryFile()
+            self._file.write(b'GIF89a' + struct.pack('<HH', w, h) + b'\x70\x00\x00')      # no global table, 8 bits a primary
+            self._file.write(b'\x21\xff\x0bNETSCAPE2.0\x03\x01' + struct.pack('<H', self.loop) + b'\x00')
+        k = self._nframes
+        delay = int(round(100.0 * (k + 1) / self.fps)) - int(round(100.0 * k / self.fps))
+        self._file.write(b'\x21\xf9\x04\x04' + struct.pack('<H', delay) + b'\x00\x00')      # disposal 1: leave the frame in place
+        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
+        self._file.write(memoryview(np.ascontiguousarray(data)))
+        self._nframes += 1
         return out

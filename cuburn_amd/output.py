@@ -315,12 +315,12 @@ class Raw16Output(Output):
     suffix = '.rgba16'
 
 
-_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg')
+_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif')
 
 
 def get_suffix(codec, alpha=False):
     ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', exr='.exr', raw='.rgba8', raw16='.rgba16', x264='.h264',
-               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi')[codec]
+               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi', gif='.gif')[codec]
     return ('_color' + ext) if alpha else ext
 
 
@@ -334,6 +334,15 @@ def get_output_for_profile(gprof):
         return DeviceEXROutput(**opts)
     if 'pixel' in opts:
         raise ValueError('output.pixel: only exr takes it, not "%s"' % handler)
+    if handler == 'gif':                                 # a format of its own: no key of another encoder means anything here
+        if set(opts) - {'colors', 'dither', 'loop'}:
+            raise ValueError('the device GIF encoder takes "colors", "dither" and "loop" only, not %s'
+                             % ', '.join(sorted(set(opts) - {'colors', 'dither', 'loop'})))
+        from . import encoders
+        return encoders.GIFOutput(fps=gprof.fps, **opts)
+    for key in ('colors', 'dither', 'loop'):
+        if key in opts:
+            raise ValueError('output.%s: only gif takes it, not "%s"' % (key, handler))
     if not (handler == 'png' and opts.get('encoder') == 'device'):
         for key in ('bits', 'filter'):
             if key in opts:

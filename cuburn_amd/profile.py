@@ -51,7 +51,7 @@ def add_args(parser=None):
                      help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
-    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'raw'])
+    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')
@@ -70,6 +70,10 @@ def add_args(parser=None):
     out.add_argument('--exr-pixel', choices=['half', 'float'],
                      help='exr stills (always encoded on the GPU: tiled, ZIP): 16-bit half samples, the default, or the '
                           'accumulator\'s own 32-bit floats (sets output.pixel)')
+    out.add_argument('--gif-colors', type=int, metavar='N',
+                     help='gif animations (always encoded on the GPU): palette entries per frame, 2..256, default 256 (sets output.colors)')
+    out.add_argument('--gif-dither', choices=['ordered', 'none'],
+                     help='gif animations: an 8 x 8 ordered dither of one palette step, the default, or none (sets output.dither)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -111,6 +115,10 @@ def get_from_args(args):
         prof['output'] = dict(prof.get('output') or {}, compression=ns['tiff_compression'])
     if ns.get('exr_pixel') is not None:
         prof['output'] = dict(prof.get('output') or {}, pixel=ns['exr_pixel'])
+    if ns.get('gif_colors') is not None:
+        prof['output'] = dict(prof.get('output') or {}, colors=ns['gif_colors'])
+    if ns.get('gif_dither') is not None:
+        prof['output'] = dict(prof.get('output') or {}, dither=ns['gif_dither'])
     return name, prof
 
 

@@ -446,6 +446,50 @@ int fl_exr_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, uint32_
                   void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_exr(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int pixel, void *host_out, uint64_t dev_out, size_t cap);
 
+/* GIF frames encoded on the device: one frame block with a palette of its own; the host writes the file around
+ * the blocks (cuburn_amd/encoders.py, GIFOutput).  All arithmetic is integer arithmetic.
+ * The source is u8 [h][w][4] as FL_OUT_RGBA8 writes them; the alpha byte is ignored.  w and h are 1..65535 and w * h <= 2^24, so
+ * that a cell's channel sum fits 32 bits.
+ * Histogram: a pixel's cell is (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3), 32768 cells; every cell keeps its pixel count and the
+ * exact sums of r, g and b.
+ * Median cut by population: box 0 holds every non-empty cell, nb = 1.  While nb < colors: among the boxes of more than one
+ * non-empty cell the one of most pixels (a tie: the lowest index; none: stop); its axis is the one of largest extent, max - min of
+ * the 5-bit coordinate over its non-empty cells (a tie: R, then G, then B); with pop the box's pixels and cum[c] those of
+ * coordinate <= c on that axis, c is the smallest coordinate with 2 * cum[c] >= pop, clamped into [min, max - 1]; the cells of
+ * coordinate > c become box nb, and nb += 1.
+ * Palette: entry b is (sum + count / 2) / count per channel over box b; entries nb..255 are 0, 0, 0.  The local colour table always
+ * has 256 entries and the LZW minimum code size is always 8.
+ * Lookup: a non-empty cell's point is its own rounded mean (sum + count / 2) / count, an empty cell's its centre 8 * coord + 4;
+ * the cell maps to the entry among 0..nb-1 of least squared distance to that point, the lowest index on a tie.
+ * Dither: with B the 8 x 8 Bayer matrix (rows 0 32 8 40 2 34 10 42 / 48 16 56 24 50 18 58 26 / 12 44 4 36 14 46 6 38 /
+ * 60 28 52 20 62 30 54 22 / 3 35 11 43 1 33 9 41 / 51 19 59 27 49 17 57 25 / 15 47 7 39 13 45 5 37 / 63 31 55 23 61 29 53 21)
+ * and d = 2 * B[y & 7][x & 7] + 1 - 64, every channel becomes clamp(p + ((d * dither_amp) >> 7), 0, 255), the shift arithmetic;
+ * the pixel's index is the lookup of the dithered value's cell.  Histogram and palette are taken from the undithered pixels.
+ * LZW: the indices in raster order in segments of S pixels (the library's choice, FL_GIF_SEG = 1024 unless FLAME_GIF_SEG = 256..3584
+ * was set when the context was created; the last may be shorter), codes packed least significant bit first.  Per segment:
+ * width = 9, next = 258, CLEAR (256) in 9 bits; p = the first index; for every later index c: if the string (p, c) is in the
+ * dictionary p becomes its code, otherwise p is emitted in width bits, (p, c) becomes code next, next += 1, width += 1 if
+ * next > 1 << width and width < 12, and p = c.  After the last index p is emitted, then next += 1 and the width step once more
+ * (the entry the decoder adds).  The last segment then emits END (257) in width bits and pads with zero bits to a byte; every
+ * other one emits CLEAR in width bits and then CLEARs of 9 bits until the bit count is a multiple of 8.
+ * The block: 2C, left 0, top 0, w, h as u16 little-endian, 87, the 768 palette bytes, 08 (FL_GIF_HEADER_BYTES so far), the
+ * segments' bytes in sub-blocks — stream byte j at j + j / 255 + 1 behind the 08, a length byte min(255, total - 255 g) in front
+ * of every 255 bytes —, 00.  The same pixels, size, colors, dither_amp and S give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status, u32 S, u32 0,
+ * and behind it the block; status, the capacity rule and the destinations are the PNG encoder's.
+ * fl_gif_bound: 16 + FL_GIF_HEADER_BYTES + T + ceil(T / 255) + 1 with T = ceil(3 n / 2) + 11 * ceil(n / 256), n = w * h: twelve
+ * bits a pixel and 84 bits of framing a segment at the shortest S; 0 for w or h of 0 or above 65535 and for w * h > 2^24.
+ * fl_gif_encode: queued on the current lane's stream.
+ * fl_output_gif: fl_output(FL_OUT_RGBA8) into the lane's pixel buffer (same draws, same dither states afterwards), then the
+ * encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: colors outside 2..256, dither_amp outside 0..64, a frame whose fl_gif_bound is 0, a null
+ * src_dev, host_out and dev_out both null, cap < 16 + FL_GIF_HEADER_BYTES. */
+#define FL_GIF_HEADER_BYTES 779           /* 2C, the descriptor, the colour table, the code size */
+size_t fl_gif_bound(uint32_t w, uint32_t h);
+int fl_gif_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int colors, int dither_amp,
+                  void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_gif(fl_ctx *ctx, uint32_t w, uint32_t h, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -480,7 +524,8 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
  * [4] the DE proper — the eight direction kernels, the first normalising the accumulator, the last un-normalising it with a
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
  * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of the device encoders (fl_jpeg_encode,
- * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff, fl_exr_encode, fl_output_exr; 0 when none ran). */
+ * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff, fl_exr_encode, fl_output_exr,
+ * fl_gif_encode, fl_output_gif; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
