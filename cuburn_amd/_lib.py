@@ -27,6 +27,7 @@ PNG_FILTERS = {'paeth': 0, 'adaptive': PNG_ADAPTIVE}        # output.filter -> t
 EXR_PIXELS = {'half': 1, 'float': 2}        # include/flame_hip.h FL_EXR_HALF, FL_EXR_FLOAT
 GIF_HEADER_BYTES = 779              # include/flame_hip.h FL_GIF_HEADER_BYTES
 GIF_DITHER = {'none': 0, 'ordered': 8}      # output.dither -> the dither_amp of fl_output_gif
+WEBP_PB, WEBP_EB = 4, 6              # include/flame_hip.h FL_WEBP_PB, FL_WEBP_EB: the record's parameter is PB | EB << 8
 OUT = dict(rgba8=0, rgba16=1, yuv444p=2, yuv444p10=3, yuv420p10=4, yuv444p12=5)     # include/flame_hip.h FL_OUT_*
 
 
@@ -76,6 +77,9 @@ _SIGS = {
     'fl_gif_bound': (C.c_size_t, [C.c_uint32, C.c_uint32]),
     'fl_gif_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_gif': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_webp_bound': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int]),
+    'fl_webp_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_output_webp': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_sort_u32': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     'fl_frame_begin': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     'fl_frame_ms': (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),

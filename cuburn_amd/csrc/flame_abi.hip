@@ -1355,6 +1355,50 @@ int fl_output_gif(fl_ctx *c, uint32_t w, uint32_t h, int colors, int dither_amp,
     return close_frame(c, ln);
 }
 
+// ---- WebP ----
+// No block can be longer: the proof is with the declaration in include/flame_hip.h.
+size_t fl_webp_bound(uint32_t w, uint32_t h, int channels)
+{
+    if (!w || !h || w > 16384u || h > 16384u || (channels != 3 && channels != 4)) return 0;
+    const uint64_t n = 16u + 8u + (webp_bound_bits(w, h) + 7u) / 8u + 1u;
+    return n > 0xffffffffull ? 0 : (size_t)n;
+}
+
+static int check_webp(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_encode(c, "webp", w, h, FL_WEBP_HEADER_BYTES, host_out, dev_out, cap)) return rc;
+    REQUIRE(channels == 3 || channels == 4, "webp: channels must be 3 or 4");
+    REQUIRE(w <= 16384u && h <= 16384u, "webp: width and height must be 1..16384");
+    REQUIRE(fl_webp_bound(w, h, channels) != 0, "webp: the block could pass 2^32 - 1 bytes");
+    return FL_OK;
+}
+
+static int webp_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels, void *host_out, uint64_t dev_out,
+                          size_t cap)
+{
+    const size_t bound = fl_webp_bound(w, h, channels);
+    return encode_on(c, ln, host_out, dev_out, cap, bound, webp_layout(w, h).words, "webp block", "webp scratch",
+                     [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) { launch_webp_encode(st, src, w, h, channels, scratch, dst, cap, bound); });
+}
+
+int fl_webp_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_webp(c, w, h, channels, host_out, dev_out, cap)) return rc;
+    REQUIRE(src_dev, "webp: null source pixels");
+    HIPCHK(hipSetDevice(c->device));
+    return webp_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, host_out, dev_out, cap);
+}
+
+int fl_output_webp(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_webp(c, w, h, channels, host_out, dev_out, cap)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = webp_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
+}
+
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
                 uint32_t *nvalid)
 {

@@ -179,6 +179,16 @@ GifLayout gif_layout(uint32_t w, uint32_t h, uint32_t seg);
 void launch_gif_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int colors, int amp, uint32_t seg, uint32_t *scratch,
                        unsigned char *out, size_t cap);
 
+// webp.hip: one lossless WebP frame block — a whole `VP8L` chunk — from u8 [h][w][4] (channels 3: every alpha reads 255): subtract green,
+// a predictor mode per 16 x 16 tile, five prefix codes per 64 x 64 tile, no back references.  `scratch` holds
+// webp_layout().words words; the 16-byte record and the block go to `out`, of which nothing at or beyond `cap` (>= 16 + FL_WEBP_HEADER_BYTES)
+// is touched.  bound: fl_webp_bound of the frame.  w and h are 1..16384.
+struct WebpLayout { uint32_t ptx, pty, gx, gy, G, NR, subwords; size_t asmwords, modes, codes, hdr, cnt, off, sub, subinfo, info, asmb, words; };      // predictor tiles, entropy tiles per row / column / in all, runs, words of the staged beginning and of the assembly buffer; word offsets into the scratch
+uint64_t webp_bound_bits(uint32_t w, uint32_t h);      // no payload has more bits (fl_webp_bound)
+WebpLayout webp_layout(uint32_t w, uint32_t h);
+void launch_webp_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, uint32_t *scratch, unsigned char *out,
+                        size_t cap, size_t bound);
+
 int launch_measure_copy(size_t nbytes, int iters, float *ms);      // the device's streaming copy rate (fl_measure_copy)
 
 // sort.hip: one stable radix pass (nbits <= 10 at lo_bit) over n keys; hist = scratch of

@@ -236,32 +236,8 @@ struct EmitSink {
     }
 };
 
-// ---- length-limited Huffman codes: build_lengths and its HuffTmp are in encode_device.h (the JPEG encoder builds its tables with them) ----
-// code[s] = the canonical code of RFC 1951 3.2.2, bit-reversed (deflate sends Huffman codes from their most significant bit) | length << 16
-__device__ void canonical_codes(const unsigned char *lens, uint32_t nsym, uint32_t *code, HuffTmp &T)
-{
-    const uint32_t t = threadIdx.x;
-    if (t < 32u) T.cnt[t] = 0;
-    __syncthreads();
-    for (uint32_t i = t; i < nsym; i += 256u) if (lens[i]) atomicAdd(&T.cnt[lens[i]], 1u);
-    __syncthreads();
-    if (t == 0) {
-        uint32_t c = 0;
-        T.next[0] = 0;
-        for (uint32_t b = 1; b < 16u; ++b) { c = (c + T.cnt[b - 1u]) << 1; T.next[b] = c; }
-    }
-    __syncthreads();
-    for (uint32_t i = t; i < nsym; i += 256u) {
-        const uint32_t l = lens[i];
-        uint32_t r = 0;
-        if (l) {
-#pragma unroll 8
-            for (uint32_t j = 0; j < i; ++j) r += lens[j] == l ? 1u : 0u;
-        }
-        code[i] = l ? __brev(T.next[l] + r) >> (32u - l) | l << 16 : 0u;
-    }
-    __syncthreads();
-}
+// ---- length-limited Huffman codes: build_lengths, canonical_codes and their HuffTmp are in encode_device.h (the JPEG encoder builds its tables with
+// the first, the WebP encoder its codes with both) ----
 
 // ---- one segment per workgroup -----------------------------------------------------------------------------------------
 // Lane t owns the bytes [t * per, (t + 1) * per) of the segment (per a multiple of 16, 256 * per >= seg).  The segment's bytes

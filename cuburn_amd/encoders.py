@@ -10,7 +10,8 @@ the program name, which is also how the tests drive the classes without them.
 
 MJPEGOutput needs no program: the device encodes every frame as a JPEG (output.DeviceJPEGOutput) and the host
 only puts the frames into an AVI file.  GIFOutput needs none either: the device writes every frame's block, palette and
-LZW data included, and the host puts the blocks into a GIF89a file.
+LZW data included, and the host puts the blocks into a GIF89a file.  WebPOutput likewise: the device writes every frame as a
+lossless `VP8L` chunk and the host puts the chunks into a RIFF file, a still's or an animation's.
 """
 import fractions
 import struct
@@ -417,4 +418,111 @@ class GIFOutput(DeviceEncodedOutput):
         # the pinned frame buffer is reused by the next frame: the bytes are copied out here
         self._file.write(memoryview(np.ascontiguousarray(data)))
         self._nframes += 1
+        return out
+
+
+def webp_duration(k, fps):
+    """Milliseconds of frame k: round(1000 (k + 1) / fps) - round(1000 k / fps), so the file keeps the rate on average."""
+    return int(round(1000.0 * (k + 1) / fps)) - int(round(1000.0 * k / fps))
+
+
+def webp_durations(nframes, fps):
+    return [webp_duration(k, fps) for k in range(nframes)]
+
+
+def _u24(v):
+    return struct.pack('<I', v)[:3]
+
+
+class WebPOutput(DeviceEncodedOutput):
+    """Stills and animations as lossless WebP (``output: {"type": "webp", "alpha": bool, "loop": 0..65535}``, ``--codec webp``):
+    every frame leaves the GPU as a finished `VP8L` chunk — subtract green, a predictor mode per 16 x 16 tile, prefix codes per
+    64 x 64 tile (include/flame_hip.h, fl_output_webp) — and the host writes the RIFF file around the chunks.  A file that ends
+    with one frame is the simple format (`RIFF`, size, `WEBP`, the chunk), so the first chunk is held back until a second frame or
+    the flush decides; a file of two or more is the extended format: `VP8X`, `ANIM` (background 0, ``loop``, 0: forever), one
+    `ANMF` per frame with its duration in milliseconds, not blended, not disposed.  ``encode(None)`` returns the file.  No
+    external program.  A change of frame size flushes and starts a new file, as GIFOutput does.  The record's parameter is
+    PB | EB << 8, the tiles' size bits."""
+    suffix, entry, noun = '.webp', 'fl_output_webp', 'WebP frame block'
+    LIMIT = (1 << 32) - 10                 # a RIFF size is 32 bits
+
+    def __init__(self, fps=24, alpha=False, loop=0):
+        if not fps > 0:
+            raise ValueError('webp needs fps above 0')
+        if fps > 90:
+            raise ValueError('webp: fps %g gives frames of 10 ms or less, which players show for 100 ms: use 90 or less' % fps)
+        if not isinstance(alpha, bool):
+            raise ValueError('output.alpha must be true or false')
+        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
+            raise ValueError('output.loop must be an integer in 0..65535')
+        self.fps, self.alpha, self.loop = fps, alpha, loop
+        self.channels = 4 if alpha else 3
+        self._file, self._first, self._nframes, self._size, self.framesize = None, None, 0, 0, None
+
+    def argument(self):
+        return self.channels
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (60 bits a pixel and the codes' headers)."""
+        return int(_lib.load().fl_webp_bound(dim.w, dim.h, self.channels))
+
+    def abort(self):
+        if self._file is not None:
+            self._file.close()
+        self._file, self._first, self._nframes, self._size = None, None, 0, 0
+
+    def _flush(self):
+        if self._nframes == 0:
+            return {}, []
+        if self._nframes == 1:
+            f = tempfile.TemporaryFile()
+            f.write(b'RIFF' + struct.pack('<I', 4 + len(self._first)) + b'WEBP')
+            f.write(self._first)
+        else:
+            f = self._file
+            f.seek(4)
+            f.write(struct.pack('<I', self._size - 8))
+        f.seek(0)
+        self._file, self._first, self._nframes, self._size = None, None, 0, 0
+        return {'.webp': f}, []
+
+    def _anmf(self, block):
+        h, w = self.framesize
+        dur = webp_duration(self._nframes, self.fps)
+        if self._size + 24 + len(block) > self.LIMIT:
+            self.abort()
+            raise IOError('the WebP file would pass 4 GiB: use shard to split the animation into several files')
+        self._file.write(b'ANMF' + struct.pack('<I', 16 + len(block)) + _u24(0) + _u24(0) + _u24(w - 1) + _u24(h - 1) + _u24(dur) + b'\x02')
+        self._file.write(block)
+        self._size += 24 + len(block)
+        self._nframes += 1
+
+    def encode(self, buf):
+        out = ({}, [])
+        if buf is None:
+            return self._flush()
+        data = self.file_bytes(buf, self.noun)
+        if len(data) < 8 + 5 or bytes(data[:4]) != b'VP8L' or data[8] != 0x2f or len(data) & 1:
+            raise IOError('the frame is not a block of the device WebP encoder')
+        bits, = struct.unpack('<I', bytes(data[9:13]))
+        w, h = (bits & 0x3fff) + 1, (bits >> 14 & 0x3fff) + 1
+        if self.framesize != (h, w):
+            out = self._flush()
+            self.framesize = (h, w)
+        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
+        block = bytes(memoryview(np.ascontiguousarray(data)))
+        if self._nframes == 0:
+            if 12 + len(block) > self.LIMIT:
+                raise IOError('the WebP file would pass 4 GiB: use shard to split the animation into several files')
+            self._first, self._nframes = block, 1
+            return out
+        if self._nframes == 1:                              # a second frame: the file is an animation
+            self._file = tempfile.TemporaryFile()
+            self._file.write(b'RIFF\0\0\0\0WEBP')
+            self._file.write(b'VP8X' + struct.pack('<I', 10) + bytes([0x12 if self.alpha else 0x02, 0, 0, 0]) + _u24(w - 1) + _u24(h - 1))
+            self._file.write(b'ANIM' + struct.pack('<IIH', 6, 0, self.loop))
+            self._size, self._nframes = 12 + 18 + 14, 0
+            first, self._first = self._first, None
+            self._anmf(first)
+        self._anmf(block)
         return out

@@ -315,12 +315,14 @@ class Raw16Output(Output):
     suffix = '.rgba16'
 
 
-_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif')
+_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp')
 
 
 def get_suffix(codec, alpha=False):
     ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', exr='.exr', raw='.rgba8', raw16='.rgba16', x264='.h264',
-               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi', gif='.gif')[codec]
+               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi', gif='.gif', webp='.webp')[codec]
+    if codec == 'webp':                                  # alpha travels inside the one file
+        return ext
     return ('_color' + ext) if alpha else ext
 
 
@@ -340,9 +342,14 @@ def get_output_for_profile(gprof):
                              % ', '.join(sorted(set(opts) - {'colors', 'dither', 'loop'})))
         from . import encoders
         return encoders.GIFOutput(fps=gprof.fps, **opts)
+    if handler == 'webp':                                # lossless, on the device only: no key of another encoder means anything here
+        if set(opts) - {'alpha', 'loop'}:
+            raise ValueError('the device WebP encoder takes "alpha" and "loop" only, not %s' % ', '.join(sorted(set(opts) - {'alpha', 'loop'})))
+        from . import encoders
+        return encoders.WebPOutput(fps=gprof.fps, **opts)
     for key in ('colors', 'dither', 'loop'):
         if key in opts:
-            raise ValueError('output.%s: only gif takes it, not "%s"' % (key, handler))
+            raise ValueError('output.%s: only gif %s, not "%s"' % (key, 'and webp take it' if key == 'loop' else 'takes it', handler))
     if not (handler == 'png' and opts.get('encoder') == 'device'):
         for key in ('bits', 'filter'):
             if key in opts:

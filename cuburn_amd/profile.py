@@ -51,7 +51,7 @@ def add_args(parser=None):
                      help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
-    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'raw'])
+    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')

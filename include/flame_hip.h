@@ -490,6 +490,63 @@ int fl_gif_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int col
                   void *host_out, uint64_t dev_out, size_t cap);
 int fl_output_gif(fl_ctx *ctx, uint32_t w, uint32_t h, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap);
 
+/* Lossless WebP frames encoded on the device: one frame block, a complete RIFF chunk `VP8L`, u32 payload length,
+ * the payload, one zero byte if the length is odd; the host writes it verbatim into a still's or an animation's container
+ * (cuburn_amd/encoders.py, WebPOutput).  All arithmetic is integer arithmetic.
+ * The source is u8 [h][w][4] as FL_OUT_RGBA8 writes them, src_dev 4-byte aligned (a pixel is read as one word).  w and h are
+ * 1..16384.  channels 3 reads every alpha as 255, channels 4 keeps alpha.  Bits are packed least significant first; prefix codes are canonical, as deflate's, and written bit-reversed.
+ * The payload, in order: byte 2F; w - 1 and h - 1 in 14 bits each; alpha_is_used = (channels == 4); version 0 in 3 bits.
+ * Transform present (1), type 2 (subtract green) in 2 bits: r and b become (r - g) mod 256 and (b - g) mod 256.  Transform present
+ * (1), type 0 (predictor), the size field PB - 2 in 3 bits with PB = FL_WEBP_PB = 4 (16 x 16 tiles), then the mode sub-image of
+ * ceil(w / 16) x ceil(h / 16) pixels, green = the tile's mode, red = blue = 0, alpha = 255.  No further transform (0), no colour
+ * cache (0).  Meta prefix codes present (1), the size field EB - 2 in 3 bits with EB = FL_WEBP_EB = 6 (64 x 64 tiles), then the
+ * entropy sub-image of ceil(w / 64) x ceil(h / 64) pixels: pixel i in raster order names group i, green = i & 255, red = i >> 8,
+ * blue 0, alpha 255 (G = ceil(w / 64) * ceil(h / 64) groups, at most 65536; the bit is written even when G = 1).  Per group, in
+ * order, five prefix codes: green (alphabet 280), red, blue, alpha (256 each), distance (40), built from the counts of that
+ * tile's residuals (the distance code from no counts).  Then the pixels in raster order, each as its green, red, blue and alpha
+ * symbol in the codes of its tile's group; a code of one symbol emits no bits.  Zero bits to the next byte.
+ * Each sub-image is an entropy-coded image of its own: cache bit 0, one group of five codes from its own counts, its pixels.
+ * Predictor: it works on the green-subtracted picture, never on residuals; the residual is (pixel - prediction) mod 256 per
+ * channel.  Whatever the mode, (0, 0) is predicted as r, g, b, a = 0, 0, 0, 255, the rest of row 0 as L and the rest of column 0
+ * as T.  TR of the last column is pixel (0, y) of the current row.  With avg2(a, b) = floor((a + b) / 2) per channel the modes
+ * are 1: L; 2: T; 7: avg2(L, T); 10: avg2(avg2(L, TL), avg2(T, TR)); 11 (select): with e = L + T - TL per channel, signed, and
+ * dL, dT the sums over the four channels of |e - L| and |e - T|, L if dL < dT, else T; 12: clamp(L + T - TL, 0, 255) per channel.
+ * A tile takes the mode among {1, 2, 7, 10, 11, 12} of least cost, the lowest on a tie; the cost is the sum over the tile's
+ * pixels inside the image and the four channels of min(r, 256 - r) of the residuals r the mode would give, fixed rules applied
+ * (the measure of FL_PNG_ADAPTIVE).
+ * Every prefix code, the sub-images' included: with at most one used symbol s (0 if none) the simple form, bits 1, 0,
+ * is_first_8bits = (s > 1), s in 1 or 8 bits.  Otherwise bit 0 and the normal form: lengths limited to 15 — Huffman's (ties: the
+ * lower count, then the lower symbol, leaves before inner nodes), depths cut at 15, Kraft's sum repaired by lengthening the
+ * deepest code that can be, the rarest symbols longest.  The lengths 0 .. last used become tokens: a non-zero length is a
+ * literal; a run of zeros takes 18 (11..138, 7 extra bits) while at least 11 remain, then 17 (3..10, 3 extra bits), then one or
+ * two literal 0s; 16 is never used.  The token kinds get lengths by the same rule with limit 7; a lone kind gets one bit and so
+ * does kind 0 (kind 1, if the lone kind is 0).  Written: num_code_lengths - 4 in 4 bits (at least 4, up to the last non-zero in
+ * the order 17 18 0 1 2 3 4 5 16 6 7 8 9 10 11 12 13 14 15), those lengths in 3 bits each, bit 1, k - 1 in 3 bits and
+ * ntokens - 2 in 2 k bits with k = max(1, ceil(bitlength(ntokens - 2) / 2)), then the tokens with their extra bits.
+ * The same pixels, size and channels give the same bytes.
+ * The result, in host_out and / or at dev_out (capacity `cap` bytes each): a 16-byte record u32 nbytes, u32 status,
+ * u32 PB | EB << 8, u32 0, and behind it the block; status, the capacity rule and the destinations are the PNG encoder's (with
+ * status 1 the record alone is written).
+ * fl_webp_bound: 16 + 8 + ceil(B / 8) + 1 with B = 49 + (1 + Hg + 60 pt) + 6 + (1 + Hg + 60 G) + G Hg + 60 w h,
+ * pt = ceil(w / 16) ceil(h / 16).  The proof: no code is longer than 15 bits, so a pixel of any image is at most 60; the fixed
+ * fields are 49 bits in front of the mode sub-image and 6 between the sub-images, and each sub-image begins with its cache bit.
+ * A normal code's header is 1 + 4 + 19 * 3 + 1 + 3 + 10 = 76 bits and its tokens: at most 256 of them (the last used symbol is
+ * at most 255 in every image here, and no token stands for less than one length), each a code of at most 7 bits and at most 7
+ * extra bits; the simple form is shorter; so Hc = 76 + 256 * 14 = 3660 and a group of four such codes and the distance code's
+ * 4 bits is Hg = 4 Hc + 4.  The padding (at most 7 bits) is in the ceil, the chunk's pad byte is the + 1.  0 for w or h of 0 or
+ * above 16384, channels other than 3 or 4, or a result beyond 2^32 - 1.
+ * fl_webp_encode: queued on the current lane's stream.
+ * fl_output_webp: fl_output(FL_OUT_RGBA8) into the lane's pixel buffer (same draws, same dither states afterwards), then the
+ * encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: channels other than 3 or 4, w or h above 16384, a null src_dev, host_out and dev_out
+ * both null, cap < 16 + FL_WEBP_HEADER_BYTES. */
+#define FL_WEBP_PB 4                      /* predictor tiles of 16 x 16 pixels */
+#define FL_WEBP_EB 6                      /* entropy tiles of 64 x 64 pixels */
+#define FL_WEBP_HEADER_BYTES 8            /* `VP8L` and the payload's length */
+size_t fl_webp_bound(uint32_t w, uint32_t h, int channels);
+int fl_webp_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_webp(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap);
+
 /* cuburn/code/sort.py:443-504 Sorter.sort: one radix pass over n 32-bit keys on the device —
  * dst = src ordered by the `nbits` (1..10) bits from lo_bit up, keys with equal digits in their
  * original order (stable: passes from the low digit up compose into a full sort; the reference's
@@ -525,7 +582,7 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
  * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of the device encoders (fl_jpeg_encode,
  * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff, fl_exr_encode, fl_output_exr,
- * fl_gif_encode, fl_output_gif; 0 when none ran). */
+ * fl_gif_encode, fl_output_gif, fl_webp_encode, fl_output_webp; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
