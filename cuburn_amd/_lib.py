@@ -24,6 +24,7 @@ JPEG_OPTIMIZE = 1                   # include/flame_hip.h FL_JPEG_OPTIMIZE
 PNG_HEADER_BYTES = 33               # include/flame_hip.h FL_PNG_HEADER_BYTES
 PNG_ADAPTIVE = 1                    # include/flame_hip.h FL_PNG_ADAPTIVE
 PNG_FILTERS = {'paeth': 0, 'adaptive': PNG_ADAPTIVE}        # output.filter -> the flags of fl_output_png_f
+APNG_IDAT = 0xffffffff               # include/flame_hip.h FL_APNG_IDAT: the seq that asks fl_output_apng for IDATs (frame 0)
 EXR_PIXELS = {'half': 1, 'float': 2}        # include/flame_hip.h FL_EXR_HALF, FL_EXR_FLOAT
 GIF_HEADER_BYTES = 779              # include/flame_hip.h FL_GIF_HEADER_BYTES
 GIF_DITHER = {'none': 0, 'ordered': 8}      # output.dither -> the dither_amp of fl_output_gif
@@ -68,6 +69,10 @@ _SIGS = {
     'fl_png_bound_f': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint]),
     'fl_png_encode_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_png_f': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_apng_chunks': (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    'fl_apng_bound': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint]),
+    'fl_apng_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.c_void_p, C.c_uint64, C.c_size_t]),
+    'fl_output_apng': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_tiff_bound': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
     'fl_tiff_encode': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),
     'fl_output_tiff': (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_size_t]),

@@ -1148,9 +1148,10 @@ size_t fl_png_bound_f(uint32_t w, uint32_t h, int channels, int bits, unsigned f
 
 size_t fl_png_bound(uint32_t w, uint32_t h, int channels) { return fl_png_bound_f(w, h, channels, 8, 0u); }
 
-static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap)
+static int check_png(const fl_ctx *c, uint32_t w, uint32_t h, int channels, const void *host_out, uint64_t dev_out, size_t cap,
+                     size_t header = FL_PNG_HEADER_BYTES)      // (a frame block of fl_apng_encode has none)
 {
-    if (int rc = check_encode(c, "png", w, h, FL_PNG_HEADER_BYTES, host_out, dev_out, cap)) return rc;
+    if (int rc = check_encode(c, "png", w, h, header, host_out, dev_out, cap)) return rc;
     REQUIRE(channels == 3 || channels == 4, "png: channels must be 3 or 4");
     REQUIRE(fl_png_bound(w, h, channels) != 0, "png: the file could pass 2^32 - 1 bytes");
     return FL_OK;
@@ -1204,6 +1205,61 @@ int fl_output_png_f(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, u
 int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
 {
     return fl_output_png_f(c, w, h, channels, 8, 0u, host_out, dev_out, cap);
+}
+
+// ---- APNG frame blocks ----
+// The PNG's chunks without the 33 bytes in front of them and the 12 of IEND, and 4 more per chunk where they are fdATs.
+uint32_t fl_apng_chunks(uint32_t w, uint32_t h, int channels, int bits)
+{
+    if (!fl_png_bound_f(w, h, channels, bits, 0u)) return 0;
+    const uint64_t F = (uint64_t)h * (1u + (uint64_t)w * (uint32_t)(channels * bits / 8)), seg = png_segment_bytes();
+    return (uint32_t)((F + seg - 1u) / seg);
+}
+
+size_t fl_apng_bound(uint32_t w, uint32_t h, int channels, int bits, unsigned flags)
+{
+    const size_t png = fl_png_bound_f(w, h, channels, bits, flags);
+    return png ? png - FL_PNG_HEADER_BYTES - 12u + 4u * (size_t)fl_apng_chunks(w, h, channels, bits) : 0;
+}
+
+static int check_apng(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq, const void *host_out,
+                      uint64_t dev_out, size_t cap, bool need_src, uint64_t src_dev)
+{
+    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap, 0)) return rc;
+    if (need_src) REQUIRE(src_dev, "png: null source pixels");
+    if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
+    // the last chunk's number is seq + chunks - 1, and 0xffffffff is no number: it asks for IDATs
+    REQUIRE(seq == FL_APNG_IDAT || fl_apng_chunks(w, h, channels, bits) - 1u <= 0xfffffffeu - seq, "apng: the frame's sequence numbers would pass 0xfffffffe");
+    return FL_OK;
+}
+
+static int apng_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsigned char *src, int channels, int bits, unsigned flags,
+                          uint32_t seq, void *host_out, uint64_t dev_out, size_t cap)
+{
+    const uint32_t seg = png_segment_bytes();
+    return encode_on(c, ln, host_out, dev_out, cap, fl_apng_bound(w, h, channels, bits, flags), png_layout(w, h, channels, seg, bits, flags).words,
+                     "apng frame block", "png scratch", [=, st = ln.stream](uint32_t *scratch, unsigned char *dst) {
+                         launch_apng_encode(st, src, w, h, channels, bits, flags, seg, seq, scratch, dst, cap);
+                     });
+}
+
+int fl_apng_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags, uint32_t seq, void *host_out,
+                   uint64_t dev_out, size_t cap)
+{
+    if (int rc = check_apng(c, w, h, channels, bits, flags, seq, host_out, dev_out, cap, true, src_dev)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return apng_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, seq, host_out, dev_out, cap);
+}
+
+int fl_output_apng(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq, void *host_out, uint64_t dev_out,
+                   size_t cap)
+{
+    if (int rc = check_apng(c, w, h, channels, bits, flags, seq, host_out, dev_out, cap, false, 0)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
+    if (int rc = apng_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, seq, host_out, dev_out, cap)) return rc;
+    return close_frame(c, ln);
 }
 
 // ---- TIFF ----

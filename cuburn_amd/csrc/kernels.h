@@ -135,6 +135,11 @@ uint32_t png_segment_bytes();      // FL_PNG_SEG, or FLAME_PNG_SEG (measurements
 PngLayout png_layout(uint32_t w, uint32_t h, int channels, uint32_t seg, int bits, unsigned flags);
 void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
                        uint32_t *scratch, unsigned char *out, size_t cap);
+// One frame of an APNG: the record (its fourth word the number of chunks) and the frame's chunks alone go to `out`
+// (cap >= 16), with no signature, IHDR or IEND.  seq == FL_APNG_IDAT: the IDATs of launch_png_encode, byte for byte; any other seq:
+// chunk i is an fdAT with seq + i in front of the same data (the caller refuses a seq whose last number would pass 0xfffffffe).
+void launch_apng_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
+                        uint32_t seq, uint32_t *scratch, unsigned char *out, size_t cap);
 
 // The same coder for streams that stand alone (tiff.hip): ntiles pieces of tile_bytes bytes (a multiple of 16 in [8192, 32768]) at `bytes`,
 // each one final block — dynamic, or stored when that is no smaller — at segbuf + i * stride; lens[i] its bytes (at most tile_bytes + 5),

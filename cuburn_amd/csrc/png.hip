@@ -10,6 +10,8 @@
 //                   with LENS, launch_deflate_pieces, the cropped tiles of exr.hip, each of its own length)
 //   k_png_scan      one workgroup: the segments' places in the file, the Adler-32 of the whole stream, the 16-byte record and the header
 //   k_png_gather    one workgroup per segment: the finished IDAT (length, tag, bytes, CRC-32) copied to its place, IEND behind the last
+// The frame-block form of the last two (launch_apng_encode) writes one frame of an APNG: the same chunks with no header
+// in front and no IEND behind, as IDATs (frame 0) or as fdATs, each with its sequence number in front of the data and under the CRC.
 // The segments are byte aligned (an empty stored block behind a dynamic one) and share no history, which is what makes them parallel.
 // Nothing is stored at or beyond `cap`: the gather stores nothing when the file does not fit.
 #include "kernels.h"
@@ -405,19 +407,23 @@ k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, 
 // ---- where the segments go ---------------------------------------------------------------------------------------------
 // IDAT i holds segment i; the first also the two bytes of the zlib header, the last also the Adler-32.  offs[i] = where IDAT i starts in
 // the file; info = {file bytes low, high, status, Adler-32}.  The record and the signature + IHDR go to `out`.
+// form (kPngFile, kApngIdat, kApngFdat; wave-uniform): a frame block has no header and no IEND, its record's fourth word is the number
+// of chunks, and an fdAT is 4 bytes longer than the IDAT of the same segment.
+enum : uint32_t { kPngFile = 0, kApngIdat = 1, kApngFdat = 2 };
 __device__ __forceinline__ uint32_t idat_data_bytes(uint32_t len, uint32_t i, uint32_t nseg) { return len + (i == 0 ? 2u : 0u) + (i + 1u == nseg ? 4u : 0u); }
 
 __global__ void __launch_bounds__(1024)
 k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, uint32_t nseg, uint32_t seg, uint32_t F,
-           u64 *__restrict__ offs, uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap, PngHeaderArg hdr)
+           u64 *__restrict__ offs, uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap, PngHeaderArg hdr, uint32_t form)
 {
     __shared__ u64 s_sum[1024];
     const uint32_t t = threadIdx.x, per = (nseg + 1023u) / 1024u, lo = min(t * per, nseg), hi = min(lo + per, nseg);
+    const uint32_t frame = 12u + (form == kApngFdat ? 4u : 0u), front = form == kPngFile ? FL_PNG_HEADER_BYTES : 0u;
     u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += 12u + idat_data_bytes(lens[i], i, nseg);
-    u64 run = (u64)FL_PNG_HEADER_BYTES + block_excl_scan_1024(s_sum, mine, t, total);
-    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += 12u + idat_data_bytes(lens[i], i, nseg); }
-    const u64 need = (u64)FL_PNG_HEADER_BYTES + total + 12u;               // bytes behind the record, IEND included
+    for (uint32_t i = lo; i < hi; ++i) mine += frame + idat_data_bytes(lens[i], i, nseg);
+    u64 run = (u64)front + block_excl_scan_1024(s_sum, mine, t, total);
+    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += frame + idat_data_bytes(lens[i], i, nseg); }
+    const u64 need = (u64)front + total + (form == kPngFile ? 12u : 0u);   // bytes behind the record, IEND included where there is one
     const uint32_t status = need > cap - 16u ? 1u : 0u;
     if (t == 0) {
         // Adler-32 of a concatenation: a = a1 + a2 - 1, b = b1 + b2 + len2 * (a1 - 1), mod 65521
@@ -430,7 +436,9 @@ k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, 
         info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = B << 16 | A;
     }
     write_record(out, need, status, seg, t);
-    if (t < FL_PNG_HEADER_BYTES) out[16u + t] = hdr.b[t];                  // (cap >= 16 + the header: the callers checked)
+    if (form == kPngFile) {
+        if (t < FL_PNG_HEADER_BYTES) out[16u + t] = hdr.b[t];              // (cap >= 16 + the header: the callers checked)
+    } else if (t >= 12u && t < 16u) out[t] = (unsigned char)(nseg >> (8u * (t - 12u)));      // (the thread that stored the record's zero there)
 }
 
 // ---- the finished chunks ---------------------------------------------------------------------------------------------
@@ -453,13 +461,14 @@ __device__ __forceinline__ uint32_t crc_pow(uint32_t x, uint32_t e)
 }
 
 // One workgroup per segment: length, "IDAT", the bytes, the CRC-32 (and IEND behind the last) assembled in LDS and stored at
-// out + 16 + offs[it].  The CRC: with a register that starts at zero the CRC is linear in the message and blind to leading zero
-// bytes, so every lane takes an equal share of the (front-padded) message and the shares combine as sum of crc_k * x^(8 * bytes
-// behind share k).  The initial 0xFFFFFFFF is the first four bytes — the tag — inverted; the final inversion is applied at the end.
-// Dynamic LDS: seg + 5 + 38 bytes, rounded up to words, and 2 words of padding.
+// out + 16 + offs[it].  form kApngFdat: the tag is "fdAT", seq + it (most significant byte first) stands between the tag and the data,
+// the length field and the CRC take those 4 bytes in; neither frame-block form has an IEND.
+// The CRC: with a register that starts at zero the CRC is linear in the message and blind to leading zero bytes, so every lane takes
+// an equal share of the (front-padded) message and the shares combine as sum of crc_k * x^(8 * bytes behind share k).  The initial 0xFFFFFFFF is the first four bytes — the tag — inverted; the final inversion is applied at the end.
+// Dynamic LDS: seg + 5 + 38 + 4 bytes, rounded up to words, and 2 words of padding.
 __global__ void __launch_bounds__(256)
 k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const uint32_t *__restrict__ lens, const u64 *__restrict__ offs,
-             const uint32_t *__restrict__ info, uint32_t nseg, unsigned char *__restrict__ out)
+             const uint32_t *__restrict__ info, uint32_t nseg, unsigned char *__restrict__ out, uint32_t form, uint32_t seq)
 {
     extern __shared__ uint32_t s_mem[];
     __shared__ uint32_t s_tab[256], s_crc;
@@ -467,7 +476,8 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     const uint32_t t = threadIdx.x, it = blockIdx.x;
     if (info[2]) return;
     const bool first = it == 0, last = it + 1u == nseg;
-    const uint32_t L = lens[it], dlen = idat_data_bytes(L, it, nseg), body = 8u + (first ? 2u : 0u);
+    const bool fdat = form == kApngFdat, iend = last && form == kPngFile;
+    const uint32_t L = lens[it], dlen = idat_data_bytes(L, it, nseg), sq = fdat ? 4u : 0u, data = 8u + sq, body = data + (first ? 2u : 0u);
     {
         uint32_t c = t;
 #pragma unroll
@@ -476,14 +486,19 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     }
     if (t == 0) {
         s_crc = 0;
-        const unsigned char head[10] = {(unsigned char)(dlen >> 24), (unsigned char)(dlen >> 16), (unsigned char)(dlen >> 8), (unsigned char)dlen,
-                                        'I', 'D', 'A', 'T', 0x78, 0x01};      // zlib: deflate, 32 KiB window, no dictionary, FCHECK
-        for (uint32_t i = 0; i < body; ++i) s_chunk[i] = head[i];
+        const uint32_t clen = dlen + sq, no = seq + it;       // the chunk's length field; an fdAT's sequence number
+        for (uint32_t i = 0; i < 4u; ++i) s_chunk[i] = (unsigned char)(clen >> (24u - 8u * i));
+        const uint32_t tag = fdat ? 0x54416466u : 0x54414449u;               // "fdAT", "IDAT"
+        for (uint32_t i = 0; i < 4u; ++i) s_chunk[4u + i] = (unsigned char)(tag >> (8u * i));
+        if (fdat) for (uint32_t i = 0; i < 4u; ++i) s_chunk[8u + i] = (unsigned char)(no >> (24u - 8u * i));
+        if (first) { s_chunk[data] = 0x78; s_chunk[data + 1u] = 0x01; }      // zlib: deflate, 32 KiB window, no dictionary, FCHECK
         if (last) {
             const uint32_t ad = info[3];
             for (uint32_t i = 0; i < 4u; ++i) s_chunk[body + L + i] = (unsigned char)(ad >> (24u - 8u * i));
-            const unsigned char iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
-            for (uint32_t i = 0; i < 12u; ++i) s_chunk[12u + dlen + i] = iend[i];
+        }
+        if (iend) {
+            const unsigned char tail[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
+            for (uint32_t i = 0; i < 12u; ++i) s_chunk[12u + dlen + i] = tail[i];
         }
     }
     const uint32_t *src = (const uint32_t *)(segbuf + (size_t)it * stride);
@@ -493,8 +508,8 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
         for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) s_chunk[body + 4u * i + k] = (unsigned char)(wd >> (8u * k));
     }
     __syncthreads();
-    // the CRC of tag + data: M bytes from s_chunk + 4, padded in front to 256 shares of S
-    const uint32_t M = 4u + dlen, S = (M + 255u) / 256u, pad = 256u * S - M;
+    // the CRC of tag (+ sequence number) + data: M bytes from s_chunk + 4, padded in front to 256 shares of S
+    const uint32_t M = 4u + sq + dlen, S = (M + 255u) / 256u, pad = 256u * S - M;
     uint32_t crc = 0;
     for (uint32_t v = t * S; v < (t + 1u) * S; ++v) {
         if (v < pad) continue;
@@ -505,9 +520,9 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     crc = crc_mul(crc, crc_pow(xs, 255u - t));
     if (crc) atomicXor(&s_crc, crc);
     __syncthreads();
-    if (t < 4u) s_chunk[8u + dlen + t] = (unsigned char)(~s_crc >> (24u - 8u * t));
+    if (t < 4u) s_chunk[data + dlen + t] = (unsigned char)(~s_crc >> (24u - 8u * t));
     __syncthreads();
-    store_bytes<256>(out + 16u + offs[it], s_mem, 12u + dlen + (last ? 12u : 0u), t);      // (s_chunk, with the 2 words of padding behind it)
+    store_bytes<256>(out + 16u + offs[it], s_mem, data + 4u + dlen + (iend ? 12u : 0u), t);      // (s_chunk, with the 2 words of padding behind it)
 }
 
 uint32_t crc32_host(const unsigned char *p, size_t n)
@@ -563,8 +578,9 @@ static void launch_png_adaptive(hipStream_t st, const unsigned char *src, uint32
     hipLaunchKernelGGL((k_png_filter_x<CH, BITS, true>), fgrid, dim3(256), 0, st, src, w, l.rowlen, (uint32_t)l.F, (const unsigned char *)types, filt);
 }
 
-void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
-                       uint32_t *scratch, unsigned char *out, size_t cap)
+// The file (form kPngFile) or one frame's block of an APNG (kApngIdat; kApngFdat with the first chunk's sequence number)
+static void launch_png_form(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
+                            uint32_t *scratch, unsigned char *out, size_t cap, uint32_t form, uint32_t seq)
 {
     const PngLayout l = png_layout(w, h, channels, seg, bits, flags);
     const uint32_t F = (uint32_t)l.F;                         // (the callers refuse frames whose stream passes 2^32 - 1 bytes)
@@ -599,9 +615,21 @@ void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uin
     }
     hipLaunchKernelGGL(k_png_segment<false>, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 8u) / 4u + 2u), st, (const unsigned char *)filt, F, seg,
                        l.nseg, l.per, segbuf, l.stride, lens, adl);
-    hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(1024), 0, st, lens, adl, l.nseg, seg, F, offs, info, out, (u64)cap, hdr);
-    hipLaunchKernelGGL(k_png_gather, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 5u + 38u + 3u) / 4u + 2u), st, segbuf, l.stride, lens, offs, info,
-                       l.nseg, out);
+    hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(1024), 0, st, lens, adl, l.nseg, seg, F, offs, info, out, (u64)cap, hdr, form);
+    hipLaunchKernelGGL(k_png_gather, dim3(l.nseg), dim3(256), 4 * (size_t)((seg + 5u + 38u + 4u + 3u) / 4u + 2u), st, segbuf, l.stride, lens, offs, info,
+                       l.nseg, out, form, seq);
+}
+
+void launch_png_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
+                       uint32_t *scratch, unsigned char *out, size_t cap)
+{
+    launch_png_form(st, src, w, h, channels, bits, flags, seg, scratch, out, cap, kPngFile, 0u);
+}
+
+void launch_apng_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seg,
+                        uint32_t seq, uint32_t *scratch, unsigned char *out, size_t cap)
+{
+    launch_png_form(st, src, w, h, channels, bits, flags, seg, scratch, out, cap, seq == FL_APNG_IDAT ? kApngIdat : kApngFdat, seq);
 }
 
 void launch_deflate_tiles(hipStream_t st, const unsigned char *bytes, uint32_t tile_bytes, uint32_t ntiles, unsigned char *segbuf, uint32_t stride,

@@ -12,11 +12,15 @@ MJPEGOutput needs no program: the device encodes every frame as a JPEG (output.D
 only puts the frames into an AVI file.  GIFOutput needs none either: the device writes every frame's block, palette and
 LZW data included, and the host puts the blocks into a GIF89a file.  WebPOutput likewise: the device writes every frame as a
 lossless `VP8L` chunk and the host puts the chunks into a RIFF file, a still's or an animation's.
+APNGOutput likewise: the device writes every frame's `IDAT` or `fdAT` chunks, numbered and checksummed, and the host puts
+`fcTL`s between them and the header chunks in front.
 """
+import collections
 import fractions
 import struct
 import subprocess
 import tempfile
+import zlib
 
 import numpy as np
 
@@ -525,4 +529,153 @@ class WebPOutput(DeviceEncodedOutput):
             first, self._first = self._first, None
             self._anmf(first)
         self._anmf(block)
+        return out
+
+
+def apng_delay(fps):
+    """(delay_num, delay_den) of every frame: 1 / fps as an exact fraction of seconds (24 -> 1/24, 30000/1001 -> 1001/30000).
+    Raises where the fraction does not fit the fcTL's two u16."""
+    f = fractions.Fraction(fps).limit_denominator(1001) if fps > 0 else fractions.Fraction(0)
+    if not 0 < f.numerator <= 65535:
+        raise ValueError('apng: fps %g gives a frame delay of %d/%d s, which does not fit 16 bits' % (fps, f.denominator, f.numerator))
+    return f.denominator, f.numerator
+
+
+def _png_chunk(tag, data):
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+
+
+class APNGOutput(DeviceEncodedOutput):
+    """Animations as APNG (``output: {"type": "apng", "bits": 8 | 16, "alpha": bool, "filter": "paeth" | "adaptive", "loop":
+    0..65535}``, ``--codec apng``): lossless, 8 or 16 bits a sample, and a PNG reader that knows no animation shows frame 0.
+    Every frame leaves the GPU as its finished chunks — the device PNG's zlib stream as `IDAT`s for frame 0 and as `fdAT`s, sequence
+    numbers and CRCs included, for every later one (include/flame_hip.h, fl_output_apng) — and the host writes the signature,
+    `IHDR`, `acTL` (``loop`` plays, 0: forever), an `fcTL` in front of every block (the whole frame, delay 1 / fps as an exact
+    fraction, no disposal, no blending) and `IEND`.  ``encode(None)`` patches the frame count into `acTL` and returns the file.
+    No external program.  A change of frame size flushes and starts a new file, as GIFOutput does.
+
+    Sequence numbers: with n chunks a frame (``fl_apng_chunks``), frame 0's `fcTL` is 0 and frame k >= 1 holds
+    1 + (k - 1)(n + 1) in its `fcTL` and the n numbers behind it in its `fdAT`s.  A frame is numbered when it is queued
+    (``number``, which ``copy`` calls), one frame ahead of ``encode``; ``encode`` takes a block only where it starts with the tag
+    and number the file needs next.  The record's parameter is the segment's bytes, its fourth word the number of chunks."""
+    suffix, entry, noun = '.apng', 'fl_output_apng', 'APNG frame block'
+    _ACTL = 8 + 25                          # where `acTL` lies: behind the signature and IHDR
+
+    def __init__(self, fps=24, alpha=False, bits=8, filter='paeth', loop=0):
+        if not fps > 0:
+            raise ValueError('apng needs fps above 0')
+        if fps > 90:                        # (webp's cap, taken over as a stated condition: DESIGN §4.17)
+            raise ValueError('apng: fps %g gives frames of 10 ms or less, which players show for 100 ms: use 90 or less' % fps)
+        self.delay = apng_delay(fps)
+        if not isinstance(alpha, bool):
+            raise ValueError('output.alpha must be true or false')
+        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
+            raise ValueError('output.bits must be 8 or 16')
+        if not isinstance(filter, str) or filter not in _lib.PNG_FILTERS:
+            raise ValueError('output.filter must be "paeth" or "adaptive", not "%s"' % (filter,))
+        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
+            raise ValueError('output.loop must be an integer in 0..65535')
+        self.fps, self.alpha, self.channels, self.bits, self.filter, self.loop = fps, alpha, 4 if alpha else 3, bits, filter, loop
+        self._file, self._nframes, self.framesize = None, 0, None
+        self._queued = collections.deque()      # (w, h, chunks a frame, first number) of the frames numbered and not yet encoded
+        self._qsize, self._qframes = None, 0    # the size and count of the frames numbered for the file being queued
+
+    def chunks(self, w, h):
+        return int(_lib.load().fl_apng_chunks(w, h, self.channels, self.bits))
+
+    @staticmethod
+    def first_number(k, n):
+        """What frame k's block starts with: FL_APNG_IDAT for the `IDAT`s of frame 0, else its first `fdAT`'s number."""
+        return _lib.APNG_IDAT if k == 0 else 2 + (k - 1) * (n + 1)
+
+    def number(self, w, h):
+        """Number the next frame to be queued (w x h; another size than the last starts a new file): returns the ``seq`` of
+        fl_output_apng.  ``encode`` expects the frames' blocks in the order of these calls."""
+        if self._qsize != (h, w):
+            self._qsize, self._qframes = (h, w), 0
+        n = self.chunks(w, h)
+        if n == 0:
+            raise ValueError('apng: no frame of %d x %d' % (w, h))
+        seq = self.first_number(self._qframes, n)
+        if seq != _lib.APNG_IDAT and seq + n - 1 > 0xfffffffe:
+            raise IOError('the APNG file would run out of sequence numbers at frame %d: render shorter files with "shard" (--shard SECS)'
+                          % self._qframes)
+        self._queued.append((w, h, n, seq))
+        self._qframes += 1
+        return seq
+
+    def arguments(self):
+        return (self.channels, self.bits, _lib.PNG_FILTERS[self.filter])
+
+    def capacity(self, dim):
+        """The library's bound: no frame needs more (the device PNG's, and 4 bytes a chunk)."""
+        return int(_lib.load().fl_apng_bound(dim.w, dim.h, self.channels, self.bits, _lib.PNG_FILTERS[self.filter]))
+
+    def copy(self, fb, dim, pool=None, stream=None, dev_out=0, host=True):
+        h_out = fb.host_buffer(self.shape(dim), self.dtype) if host else None
+        seq = self.number(dim.w, dim.h)
+        try:
+            _lib.check(_lib.load().fl_output_apng(*((fb.ctx, dim.w, dim.h) + self.arguments()
+                                                    + (seq, h_out.ctypes.data if host else None, int(dev_out), self.capacity(dim)))))
+        except Exception:
+            self._queued.pop()                  # nothing was queued: the number is free again
+            self._qframes -= 1
+            raise
+        return h_out
+
+    def abort(self):
+        if self._file is not None:
+            self._file.close()
+        self._file, self._nframes, self.framesize = None, 0, None
+        self._queued.clear()
+        self._qsize, self._qframes = None, 0
+
+    def _flush(self):
+        if self._file is None:
+            return {}, []
+        f = self._file
+        f.write(_png_chunk(b'IEND', b''))
+        f.seek(self._ACTL)
+        f.write(_png_chunk(b'acTL', struct.pack('>II', self._nframes, self.loop)))
+        f.seek(0)
+        self._file, self._nframes, self.framesize = None, 0, None
+        return {'.apng': f}, []
+
+    def encode(self, buf):
+        out = ({}, [])
+        if buf is None:
+            if self._queued:                    # frames numbered for this file that never arrived
+                self.abort()
+                raise IOError('the APNG file was flushed with numbered frames still to come')
+            self._qsize, self._qframes = None, 0
+            return self._flush()
+        if not self._queued:
+            raise IOError('an APNG frame block that was never numbered: number(w, h) comes before encode')
+        w, h, n, _ = self._queued.popleft()
+        try:
+            nchunks = int(np.frombuffer(buf[12:16], '<u4')[0])
+            data = self.file_bytes(buf, self.noun)
+        except Exception:
+            self.abort()                        # a frame is missing: the file cannot go on
+            raise
+        if self.framesize != (h, w):            # the first frame of a size: a new file
+            out = self._flush()
+            self.framesize = (h, w)
+        want = self.first_number(self._nframes, n)
+        tag = b'IDAT' if want == _lib.APNG_IDAT else b'fdAT'
+        head = bytes(data[4:8]) if want == _lib.APNG_IDAT else bytes(data[4:12])
+        if nchunks != n or len(data) < 12 or head != (tag if want == _lib.APNG_IDAT else tag + struct.pack('>I', want)):
+            what = ('frame %d of the APNG file needs a block of %d chunks that starts with %s%s; the block has %d and starts with %r'
+                    % (self._nframes, n, tag.decode(), '' if want == _lib.APNG_IDAT else ' %d' % want, nchunks, head))
+            self.abort()                        # no file with a gap: what was written goes
+            raise IOError(what)
+        if self._file is None:
+            self._file = tempfile.TemporaryFile()
+            self._file.write(b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, self.bits, 6 if self.alpha else 2, 0, 0, 0)))
+            self._file.write(_png_chunk(b'acTL', struct.pack('>II', 0, self.loop)))      # the frame count: patched at the flush
+        fctl = 0 if self._nframes == 0 else want - 1
+        self._file.write(_png_chunk(b'fcTL', struct.pack('>IIIIIHHBB', fctl, w, h, 0, 0, self.delay[0], self.delay[1], 0, 0)))
+        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
+        self._file.write(memoryview(np.ascontiguousarray(data)))
+        self._nframes += 1
         return out

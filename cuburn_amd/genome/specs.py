@@ -119,7 +119,7 @@ profile = {
     'supersample': Scalar(1, 'Accumulate at this many times the output size per axis (1..4) and filter down (flam3 supersample)'),
     'filter_order': list_(enum(list(filters.keys())), default_filters),
     'filters': prof_filters,
-    'output': {'type': enum('jpeg png tiff x264 gif webp', 'jpeg')},
+    'output': {'type': enum('jpeg png tiff x264 gif webp apng', 'jpeg')},
 }
 
 toplevels = dict(animation=anim, node=node, edge=edge, profile=profile)

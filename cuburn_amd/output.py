@@ -134,7 +134,7 @@ class PILOutput(Output):
 
 class DeviceEncodedOutput(Output):
     """Stills encoded on the device: the frame leaves the GPU as a finished file.  The host frame is a byte buffer: a 16-byte
-    record (u32 nbytes, status, a parameter of the encoder, 0), then the file.  A subclass names the library's entry point
+    record (u32 nbytes, status, a parameter of the encoder, 0 — an APNG frame block's number of chunks), then the file.  A subclass names the library's entry point
     (``entry``), gives its one argument beyond the frame and the destination (``argument``; ``arguments`` where there are
     more) and the buffer's size (``capacity``), and says what the file is (``suffix``, ``noun``)."""
 
@@ -315,13 +315,13 @@ class Raw16Output(Output):
     suffix = '.rgba16'
 
 
-_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp')
+_VIDEO = ('x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp', 'apng')
 
 
 def get_suffix(codec, alpha=False):
     ext = dict(jpeg='.jpg', png='.png', tiff='.tiff', exr='.exr', raw='.rgba8', raw16='.rgba16', x264='.h264',
-               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi', gif='.gif', webp='.webp')[codec]
-    if codec == 'webp':                                  # alpha travels inside the one file
+               prores='.mov', vp8='.webm', vp9='.webm', mjpeg='.avi', gif='.gif', webp='.webp', apng='.apng')[codec]
+    if codec in ('webp', 'apng'):                        # alpha travels inside the one file
         return ext
     return ('_color' + ext) if alpha else ext
 
@@ -347,9 +347,15 @@ def get_output_for_profile(gprof):
             raise ValueError('the device WebP encoder takes "alpha" and "loop" only, not %s' % ', '.join(sorted(set(opts) - {'alpha', 'loop'})))
         from . import encoders
         return encoders.WebPOutput(fps=gprof.fps, **opts)
+    if handler == 'apng':                                # lossless, on the device only: no key of another encoder means anything here
+        if set(opts) - {'alpha', 'bits', 'filter', 'loop'}:
+            raise ValueError('the device APNG encoder takes "alpha", "bits", "filter" and "loop" only, not %s'
+                             % ', '.join(sorted(set(opts) - {'alpha', 'bits', 'filter', 'loop'})))
+        from . import encoders
+        return encoders.APNGOutput(fps=gprof.fps, **opts)
     for key in ('colors', 'dither', 'loop'):
         if key in opts:
-            raise ValueError('output.%s: only gif %s, not "%s"' % (key, 'and webp take it' if key == 'loop' else 'takes it', handler))
+            raise ValueError('output.%s: only gif%s, not "%s"' % (key, ', webp and apng take it' if key == 'loop' else ' takes it', handler))
     if not (handler == 'png' and opts.get('encoder') == 'device'):
         for key in ('bits', 'filter'):
             if key in opts:

@@ -51,7 +51,7 @@ def add_args(parser=None):
                      help='Accumulate at N times the output size per axis (1..4) and filter down with the spatial filter')
 
     out = parser.add_argument_group('Output options')
-    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp', 'raw'])
+    out.add_argument('--codec', choices=['jpeg', 'png', 'tiff', 'exr', 'x264', 'vp8', 'vp9', 'prores', 'mjpeg', 'gif', 'webp', 'apng', 'raw'])
     out.add_argument('--device-encode', action='store_true', default=None,
                      help='Encode jpeg or png stills on the GPU (sets output.device; with a png output, '
                           'output.encoder to "device")')
@@ -60,9 +60,9 @@ def add_args(parser=None):
                      help='Huffman tables from each frame\'s own statistics in device-encoded jpeg stills and mjpeg animations: '
                           'smaller files of the same pixels (sets output.optimize)')
     out.add_argument('--bits', type=int, choices=[8, 16],
-                     help='Sample depth of device-encoded png stills; 16 keeps what tiff and raw16 hold (sets output.bits)')
+                     help='Sample depth of device-encoded png stills and of apng animations; 16 keeps what tiff and raw16 hold (sets output.bits)')
     out.add_argument('--png-filter', choices=['paeth', 'adaptive'],
-                     help='Row filter of device-encoded png stills: Paeth on every row, or per row the type of least '
+                     help='Row filter of device-encoded png stills and of apng animations: Paeth on every row, or per row the type of least '
                           'sum of absolute residuals (sets output.filter)')
     out.add_argument('--tiff-compression', choices=['none', 'deflate'],
                      help='tiff stills: "deflate" encodes them on the GPU (tiled, Adobe deflate, horizontal predictor), "none" is '

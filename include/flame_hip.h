@@ -374,6 +374,32 @@ int fl_png_encode_f(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int c
 int fl_output_png_f(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, unsigned flags,
                     void *host_out, uint64_t dev_out, size_t cap);
 
+/* Animations as APNG: one frame's chunks, encoded on the device.  A frame block is the chunks of one frame and
+ * nothing else — no signature, no IHDR, no IEND —, one chunk per segment of the frame's own zlib stream, as the PNG encoder above
+ * cuts, codes and checksums it for the same pixels, size, channels, bits and flags.
+ * seq == FL_APNG_IDAT: the chunks are the IDATs of fl_png_encode_f's file, byte for byte (its bytes from offset 33 up to the 12
+ * of IEND): the frame that a reader which knows no animation shows.
+ * Any other seq: chunk i (from 0) is an fdAT.  Its length field is dlen + 4 and its data is seq + i as four bytes, most significant
+ * first, then the dlen bytes of IDAT i (the first chunk holds the zlib header, the last the Adler-32); its CRC-32, computed on the
+ * device, covers the tag, the number and the data.
+ * The record is the PNG encoder's with its fourth word used: u32 nbytes, u32 status, u32 segment_bytes, u32 nchunks; status, the
+ * capacity rule and the destinations are the PNG encoder's, with cap >= 16.  The file around the blocks — signature, IHDR, acTL,
+ * an fcTL in front of every block, IEND — is the host's (cuburn_amd/encoders.py, APNGOutput).
+ * fl_apng_chunks: the chunks of a frame, ceil(h * (1 + w * channels * bits / 8) / segment_bytes): the same for every frame of a
+ * shape in a process, so the next frame's numbers are known before this one has finished; 0 where fl_png_bound_f is 0.
+ * fl_apng_bound: fl_png_bound_f - 33 - 12 + 4 * fl_apng_chunks (every chunk an fdAT); 0 where fl_png_bound_f is 0.
+ * fl_apng_encode: the source and flags of fl_png_encode_f; queued on the current lane's stream.
+ * fl_output_apng: the conversion, draws and dither states of fl_output_png_f, then the encode; closes the frame as fl_output does.
+ * FL_E_INVAL, before anything is queued: every refusal of fl_png_encode_f (with cap < 16 in place of its capacity rule), and a
+ * seq other than FL_APNG_IDAT whose last number, seq + fl_apng_chunks - 1, would pass 0xfffffffe. */
+enum { FL_APNG_IDAT = 0xffffffffu };
+uint32_t fl_apng_chunks(uint32_t w, uint32_t h, int channels, int bits);
+size_t fl_apng_bound(uint32_t w, uint32_t h, int channels, int bits, unsigned flags);
+int fl_apng_encode(fl_ctx *ctx, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags, uint32_t seq,
+                   void *host_out, uint64_t dev_out, size_t cap);
+int fl_output_apng(fl_ctx *ctx, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq,
+                   void *host_out, uint64_t dev_out, size_t cap);
+
 /* TIFF stills encoded on the device: classic little-endian TIFF with one IFD, tiled; Compression 8 (Adobe
  * deflate), Predictor 2, PlanarConfiguration 1, Photometric 2; samples of `bits` = 8 or 16, `channels` = 3 or 4 (4 adds
  * ExtraSamples = 2, unassociated alpha).  TileLength is 64, TileWidth 128 at 8 bits and 64 at 16: a tile holds
@@ -582,7 +608,7 @@ int fl_timings(fl_ctx *ctx, float *iter_ms, float *flush_ms, float *filter_ms, u
  * following logscale / colorclip riding along — recorded around the launches themselves, whichever call flushes them
  * (the colorclip that follows, another filter, fl_output, a debug tap); [5] the kernels of the device encoders (fl_jpeg_encode,
  * fl_output_jpeg, fl_png_encode, fl_output_png, fl_tiff_encode, fl_output_tiff, fl_exr_encode, fl_output_exr,
- * fl_gif_encode, fl_output_gif, fl_webp_encode, fl_output_webp; 0 when none ran). */
+ * fl_gif_encode, fl_output_gif, fl_webp_encode, fl_output_webp, fl_apng_encode, fl_output_apng; 0 when none ran). */
 int fl_timings_detail(fl_ctx *ctx, float ms[6]);
 /* Which iterate kernel actually ran since the last fl_timings_reset: out[0] launches of the kernel compiled for the
  * genome's structure (hipRTC; the counterpart of the module the reference compiles per genome, cuburn/render.py:232-236),
