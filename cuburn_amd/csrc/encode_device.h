@@ -1,4 +1,5 @@
-// encode_device.h — device helpers the still encoders share (jpeg.hip, png.hip, tiff.hip, exr.hip).  DESIGN.md §4.8 "What the encoders share".
+// encode_device.h — device helpers the seven encoders share (jpeg.hip, png.hip and its APNG frame blocks, tiff.hip, exr.hip, gif.hip,
+// webp.hip; Motion-JPEG is jpeg.hip's).  DESIGN.md §4.8 "What the encoders share".
 #pragma once
 #include "kernels.h"
 
@@ -25,12 +26,80 @@ __device__ __forceinline__ u64 block_excl_scan_1024(u64 *s_sum, u64 mine, uint32
     return s_sum[t] - mine;
 }
 
+// ---- placement: one workgroup of 1024 threads lays n pieces end to end ------------------------------------------------
+// Thread t takes the pieces [lo, hi), ceil(n / 1024) consecutive ones; run = where piece lo begins (`front` + the pieces before it);
+// total = the sum of all pieces, without `front`.
+struct Placement { uint32_t lo, hi; u64 run, total; };
+
+// len(i) = the bytes (or bits) piece i takes.  s_sum: 1024 u64 of LDS.
+template <class Len>
+__device__ __forceinline__ Placement place_pieces(u64 *s_sum, uint32_t n, uint32_t t, u64 front, Len &&len)
+{
+    const uint32_t per = (n + 1023u) / 1024u, lo = min(t * per, n), hi = min(lo + per, n);
+    u64 mine = 0, total;
+    for (uint32_t i = lo; i < hi; ++i) mine += len(i);
+    const u64 before = block_excl_scan_1024(s_sum, mine, t, total);
+    return {lo, hi, front + before, total};
+}
+
+// f(i, where piece i begins) for the thread's pieces; offs[i] = that, in the width of Off (a file below 2^32 bytes keeps u32)
+template <class Len, class Fn>
+__device__ __forceinline__ void for_placed(Placement p, Len &&len, Fn &&f)
+{
+    for (uint32_t i = p.lo; i < p.hi; ++i) { f(i, p.run); p.run += len(i); }
+}
+template <class Off, class Len>
+__device__ __forceinline__ void store_offsets(Off *offs, const Placement &p, Len &&len)
+{
+    for_placed(p, len, [&](uint32_t i, u64 at) { offs[i] = (Off)at; });
+}
+
+// What a placement kernel leaves for the kernels behind it, 4 words: the bytes behind the record, whether they do not fit, and one
+// word of the encoder's own (png: the file's Adler-32; gif: the stream's bytes; webp: the payload's bytes; else 0).
+enum : uint32_t { kInfoNeedLo = 0, kInfoNeedHi = 1, kInfoStatus = 2, kInfoExtra = 3 };
+
 // The 16-byte record in front of every encoded file: u32 min(need, 2^32 - 1), status, param, 0, little-endian, by threads 0..15.
 __device__ __forceinline__ void write_record(unsigned char *out, u64 need, uint32_t status, uint32_t param, uint32_t t)
 {
     if (t < 16) {
         const uint32_t rec[4] = {need > 0xffffffffull ? 0xffffffffu : (uint32_t)need, status, param, 0u};
         out[t] = (unsigned char)(rec[t >> 2] >> (8u * (t & 3u)));
+    }
+}
+
+// The end of every placement: status = whether `need` bytes behind the record pass cap; info by thread 0 (which alone needs a valid
+// `extra`) and the record.  Returns the status.
+__device__ __forceinline__ uint32_t finish_placement(uint32_t *info, unsigned char *out, u64 need, u64 cap, uint32_t param, uint32_t extra, uint32_t t)
+{
+    const uint32_t status = need > cap - 16u ? 1u : 0u;
+    if (t == 0) { info[kInfoNeedLo] = (uint32_t)need; info[kInfoNeedHi] = (uint32_t)(need >> 32); info[kInfoStatus] = status; info[kInfoExtra] = extra; }
+    write_record(out, need, status, param, t);
+    return status;
+}
+
+__device__ __forceinline__ void put_le32(unsigned char *p, uint32_t v)      // (p may have any alignment)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) p[k] = (unsigned char)(v >> (8u * k));
+}
+
+// A coded deflate block on its way into a file, by 256 threads: its L bytes from `row` (word aligned, readable through word
+// (L - 1) / 4) to the LDS bytes at dst, which may have any alignment.  zhead: the zlib header stands at dst and the block behind it;
+// adler (null: none): *adler — a | b << 16, read by thread 0 alone — follows the block, most significant byte first.  No barrier.
+__device__ __forceinline__ void stage_block(unsigned char *dst, const uint32_t *row, uint32_t L, uint32_t t, bool zhead, const uint32_t *adler)
+{
+    unsigned char *body = dst + (zhead ? 2u : 0u);
+    if (t == 0) {
+        if (zhead) { dst[0] = 0x78; dst[1] = 0x01; }          // zlib: deflate, 32 KiB window, no dictionary, FCHECK
+        if (adler) {
+            const uint32_t ad = *adler;
+            for (uint32_t i = 0; i < 4u; ++i) body[L + i] = (unsigned char)(ad >> (24u - 8u * i));
+        }
+    }
+    for (uint32_t i = t; i < (L + 3u) / 4u; i += 256u) {
+        const uint32_t wd = row[i];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) body[4u * i + k] = (unsigned char)(wd >> (8u * k));
     }
 }
 

@@ -102,41 +102,28 @@ k_exr_tiles(const float4 *__restrict__ src, ExrFrame f, uint32_t *__restrict__ s
 // bytes, else those.  A reader tells them apart by the size alone.
 __device__ __forceinline__ uint32_t data_bytes(uint32_t block, uint32_t n) { return block + 6u < n ? block + 6u : n; }
 
-__device__ __forceinline__ void put_le32(unsigned char *p, uint32_t v)      // (p may have any alignment)
-{
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) p[k] = (unsigned char)(v >> (8u * k));
-}
-
-// offs[i] = where chunk i starts in the file (the file stays below 2^32 bytes: the callers checked the bound); info = {file bytes low,
-// high, status, 0}.  The record, the header and the offset table go to `out` (cap >= 16 + the header and the table: the callers checked).
+// offs[i] = where chunk i starts in the file (the file stays below 2^32 bytes: the callers checked the bound).  The record, the header
+// and the offset table go to `out` (cap >= 16 + the header and the table: the callers checked).
 __global__ void __launch_bounds__(1024)
 k_exr_scan(const uint32_t *__restrict__ lens, ExrFrame f, uint32_t TH, uint32_t pixel_bytes, uint32_t tile_bytes, uint32_t *__restrict__ offs,
            uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap, ExrHeaderArg hdr)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, nt = f.nt, per = (nt + 1023u) / 1024u, lo = min(t * per, nt), hi = min(lo + per, nt);
+    const uint32_t t = threadIdx.x, nt = f.nt;
     const u64 H = (u64)hdr.n + 8ull * nt;
     const auto chunk = [&](uint32_t i) -> uint32_t {
         uint32_t tx, ty, tw, th;
         tile_of(f, i, TH, tx, ty, tw, th);
         return 20u + data_bytes(lens[i], tw * th * pixel_bytes);
     };
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += chunk(i);
-    u64 run = H + block_excl_scan_1024(s_sum, mine, t, total);
-    const u64 need = H + total;
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
-    if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = 0u; }
-    write_record(out, need, status, tile_bytes, t);
-    if (status) return;                                       // a file that does not fit leaves nothing behind the record
+    const Placement p = place_pieces(s_sum, nt, t, H, chunk);
+    if (finish_placement(info, out, H + p.total, cap, tile_bytes, 0u, t)) return;      // a file that does not fit leaves nothing behind the record
     if (t < hdr.n) out[16u + t] = hdr.b[t];
     unsigned char *table = out + 16u + hdr.n;
-    for (uint32_t i = lo; i < hi; ++i) {
-        offs[i] = (uint32_t)run;
-        put_le32(table + 8u * (size_t)i, (uint32_t)run); put_le32(table + 8u * (size_t)i + 4u, 0u);
-        run += chunk(i);
-    }
+    for_placed(p, chunk, [&](uint32_t i, u64 at) {
+        offs[i] = (uint32_t)at;
+        put_le32(table + 8u * (size_t)i, (uint32_t)at); put_le32(table + 8u * (size_t)i + 4u, 0u);
+    });
 }
 
 // ---- the finished chunks -----------------------------------------------------------------------------------------------
@@ -151,25 +138,13 @@ k_exr_gather(const float4 *__restrict__ src, ExrFrame f, const unsigned char *__
     extern __shared__ uint32_t s_mem[];
     unsigned char *s_data = (unsigned char *)(s_mem + 5);
     const uint32_t t = threadIdx.x, it = blockIdx.x;
-    if (info[2]) return;
+    if (info[kInfoStatus]) return;
     uint32_t tx, ty, tw, th;
     tile_of(f, it, Form<PIX>::TH, tx, ty, tw, th);
     const uint32_t n = tw * th * CH * Form<PIX>::BPS, L = lens[it], dsz = data_bytes(L, n);
     if (t < 5u) s_mem[t] = t == 0 ? tx : t == 1u ? ty : t == 4u ? dsz : 0u;      // tileX, tileY, levelX, levelY, dataSize
     if (dsz == n) fill_raw<CH, PIX>(s_mem + 5, src, f, tx, ty, tw, th, t);
-    else {
-        if (t == 0) {
-            s_data[0] = 0x78; s_data[1] = 0x01;               // zlib: deflate, 32 KiB window, no dictionary, FCHECK
-            const uint32_t ad = adl[it];                      // (a | b << 16: the Adler-32 as it is sent, most significant byte first)
-            for (uint32_t i = 0; i < 4u; ++i) s_data[2u + L + i] = (unsigned char)(ad >> (24u - 8u * i));
-        }
-        const uint32_t *blk = (const uint32_t *)(segbuf + (size_t)it * stride);
-        for (uint32_t i = t; i < (L + 3u) / 4u; i += 256u) {
-            const uint32_t wd = blk[i];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) s_data[2u + 4u * i + k] = (unsigned char)(wd >> (8u * k));
-        }
-    }
+    else stage_block(s_data, (const uint32_t *)(segbuf + (size_t)it * stride), L, t, true, adl + it);
     __syncthreads();
     store_bytes<256>(out + 16u + offs[it], s_mem, 20u + dsz, t);
 }

@@ -997,18 +997,55 @@ int fl_output(fl_ctx *c, uint32_t w, uint32_t h, int fmt, void *host_out, uint64
     return close_frame(c, ln);
 }
 
-// ---- stills encoded on the device (jpeg.hip, png.hip, tiff.hip) ----
+// ---- files and frame blocks encoded on the device (jpeg.hip, png.hip, tiff.hip, exr.hip, gif.hip, webp.hip; DESIGN.md §4.8 and
+// §4.9 .. §4.17): stills as JPEG, PNG, TIFF and OpenEXR, animations' frames as JPEG (Motion-JPEG), GIF, WebP and APNG blocks ----
+static bool sides_ok(uint32_t w, uint32_t h, uint32_t max = 65535u) { return w >= 1 && h >= 1 && w <= max && h <= max; }
+
 // What every encoder asks of a call: a context, a frame whose sides fit the formats' 16 bits, room for the record and the
-// header (the placement kernel stores them whatever the status), and somewhere to put the file.
+// header (the placement kernel stores them whatever the status), and somewhere to put the file.  An encoder whose header's size
+// comes from a layout (tiff, exr) calls check_sides itself before it asks for the layout: one of other sides means nothing.
+static int check_sides(const char *enc, uint32_t w, uint32_t h)
+{
+    if (sides_ok(w, h)) return FL_OK;
+    return fail(FL_E_INVAL, (std::string(enc) + ": width and height must be 1..65535").c_str(), __FILE__, __LINE__);
+}
 static int check_encode(const fl_ctx *c, const char *enc, uint32_t w, uint32_t h, size_t header, const void *host_out, uint64_t dev_out, size_t cap)
 {
     REQUIRE(c, "null ctx");
-    const char *bad = !(w >= 1 && h >= 1 && w <= 65535u && h <= 65535u) ? "width and height must be 1..65535"
-                      : cap < 16 + header                               ? "capacity below the record and the header"
-                      : !(host_out || dev_out)                          ? "no destination"
-                                                                        : nullptr;
+    if (int rc = check_sides(enc, w, h)) return rc;
+    const char *bad = cap < 16 + header ? "capacity below the record and the header" : !(host_out || dev_out) ? "no destination" : nullptr;
     if (!bad) return FL_OK;
     return fail(FL_E_INVAL, (std::string(enc) + ": " + bad).c_str(), __FILE__, __LINE__);
+}
+
+// The two shapes of an encoder's entry point.  check(): the encoder's own refusals, in its own order; encode(lane): its X_encode_on.
+// From the caller's source: a null source is refused behind `check`, and `late()` holds what the entry point refuses behind that.
+extern "C++" template <class Check, class Encode, class Late = int (*)()>
+static int encode_source(fl_ctx *c, uint64_t src_dev, const char *no_source, Check check, Encode encode, Late late = +[] { return (int)FL_OK; })
+{
+    if (int rc = check()) return rc;
+    REQUIRE(src_dev, no_source);
+    if (int rc = late()) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return encode(c->lane());
+}
+
+// From the front buffer: source(lane) makes the encoder's source ready, and the frame's end moves behind the encode.
+extern "C++" template <class Check, class Source, class Encode>
+static int encode_front(fl_ctx *c, Check check, Source source, Encode encode)
+{
+    if (int rc = check()) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    if (int rc = source(ln)) return rc;
+    if (int rc = encode(ln)) return rc;
+    return close_frame(c, ln);
+}
+// ... dithered and converted to `fmt` in the lane's pixel buffer, which is what encode(lane) then reads
+extern "C++" template <class Check, class Encode>
+static int encode_front(fl_ctx *c, uint32_t w, uint32_t h, int fmt, Check check, Encode encode)
+{
+    return encode_front(c, check, [=](Lane &ln) { return convert_front(c, ln, w, h, fmt, nullptr); }, encode);
 }
 
 // One encode, queued on the lane's stream (arguments checked).  Where the kernels store: the caller's device buffer; else the
@@ -1051,7 +1088,7 @@ static int encode_on(fl_ctx *c, Lane &ln, void *host_out, uint64_t dev_out, size
 // 4:2:0 by the same rule: an MCU of six blocks is 9960 bits, 1245 bytes, 2 * 1245 + 2 = 2492.
 size_t fl_jpeg_bound_s(uint32_t w, uint32_t h, int sampling)
 {
-    if (!w || !h || w > 65535u || h > 65535u || (sampling != FL_JPEG_444 && sampling != FL_JPEG_420)) return 0;
+    if (!sides_ok(w, h) || (sampling != FL_JPEG_444 && sampling != FL_JPEG_420)) return 0;
     if (sampling == FL_JPEG_420) return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 15u) / 16u) * ((h + 15u) / 16u) * 2492u;
     return 16 + FL_JPEG_HEADER_BYTES + (size_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 1248u;
 }
@@ -1097,10 +1134,8 @@ static int jpeg_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const uns
 int fl_jpeg_encode_f(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, unsigned flags, void *host_out, uint64_t dev_out,
                      size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "jpeg: null source planes");
-    HIPCHK(hipSetDevice(c->device));
-    return jpeg_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, quality, sampling, flags, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "jpeg: null source planes", [&] { return check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return jpeg_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, quality, sampling, flags, host_out, dev_out, cap); });
 }
 
 int fl_jpeg_encode_s(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
@@ -1115,12 +1150,8 @@ int fl_jpeg_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int qual
 
 int fl_output_jpeg_f(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, unsigned flags, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, FL_OUT_YUV444P, nullptr)) return rc;
-    if (int rc = jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, sampling, flags, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, FL_OUT_YUV444P, [&] { return check_jpeg(c, w, h, quality, sampling, flags, host_out, dev_out, cap); },
+                        [&](Lane &ln) { return jpeg_encode_on(c, ln, w, h, ln.d_outpix, quality, sampling, flags, host_out, dev_out, cap); });
 }
 
 int fl_output_jpeg_s(fl_ctx *c, uint32_t w, uint32_t h, int quality, int sampling, void *host_out, uint64_t dev_out, size_t cap)
@@ -1139,7 +1170,7 @@ int fl_output_jpeg(fl_ctx *c, uint32_t w, uint32_t h, int quality, void *host_ou
 // Rows of 1 + w * channels * bits / 8 bytes; the filter choice changes no size.  (A frame over the limit at 8 bits is over it at 16.)
 size_t fl_png_bound_f(uint32_t w, uint32_t h, int channels, int bits, unsigned flags)
 {
-    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4)) return 0;
+    if (!sides_ok(w, h) || (channels != 3 && channels != 4)) return 0;
     if ((bits != 8 && bits != 16) || (flags & ~(unsigned)FL_PNG_ADAPTIVE)) return 0;
     const uint64_t F = (uint64_t)h * (1u + (uint64_t)w * (uint32_t)(channels * bits / 8)), seg = png_segment_bytes();
     const uint64_t n = 16u + FL_PNG_HEADER_BYTES + 2u + F + 17u * ((F + seg - 1u) / seg) + 4u + 12u;
@@ -1179,11 +1210,9 @@ static int png_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsi
 int fl_png_encode_f(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags, void *host_out, uint64_t dev_out,
                     size_t cap)
 {
-    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "png: null source pixels");
-    if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    return png_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "png: null source pixels", [&] { return check_png(c, w, h, channels, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return png_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, host_out, dev_out, cap); },
+                         [&] { return check_png_f(w, h, channels, bits, flags); });
 }
 
 int fl_png_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
@@ -1193,13 +1222,9 @@ int fl_png_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int chann
 
 int fl_output_png_f(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = png_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8,
+                        [&] { const int rc = check_png(c, w, h, channels, host_out, dev_out, cap); return rc ? rc : check_png_f(w, h, channels, bits, flags); },
+                        [&](Lane &ln) { return png_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, host_out, dev_out, cap); });
 }
 
 int fl_output_png(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
@@ -1222,11 +1247,9 @@ size_t fl_apng_bound(uint32_t w, uint32_t h, int channels, int bits, unsigned fl
     return png ? png - FL_PNG_HEADER_BYTES - 12u + 4u * (size_t)fl_apng_chunks(w, h, channels, bits) : 0;
 }
 
-static int check_apng(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq, const void *host_out,
-                      uint64_t dev_out, size_t cap, bool need_src, uint64_t src_dev)
+// What a frame block refuses beyond check_png (with no header) and, in fl_apng_encode, the null source, after those
+static int check_apng_f(uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq)
 {
-    if (int rc = check_png(c, w, h, channels, host_out, dev_out, cap, 0)) return rc;
-    if (need_src) REQUIRE(src_dev, "png: null source pixels");
     if (int rc = check_png_f(w, h, channels, bits, flags)) return rc;
     // the last chunk's number is seq + chunks - 1, and 0xffffffff is no number: it asks for IDATs
     REQUIRE(seq == FL_APNG_IDAT || fl_apng_chunks(w, h, channels, bits) - 1u <= 0xfffffffeu - seq, "apng: the frame's sequence numbers would pass 0xfffffffe");
@@ -1246,20 +1269,17 @@ static int apng_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const uns
 int fl_apng_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, unsigned flags, uint32_t seq, void *host_out,
                    uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_apng(c, w, h, channels, bits, flags, seq, host_out, dev_out, cap, true, src_dev)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    return apng_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, seq, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "png: null source pixels", [&] { return check_png(c, w, h, channels, host_out, dev_out, cap, 0); },
+                         [&](Lane &ln) { return apng_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, flags, seq, host_out, dev_out, cap); },
+                         [&] { return check_apng_f(w, h, channels, bits, flags, seq); });
 }
 
 int fl_output_apng(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, unsigned flags, uint32_t seq, void *host_out, uint64_t dev_out,
                    size_t cap)
 {
-    if (int rc = check_apng(c, w, h, channels, bits, flags, seq, host_out, dev_out, cap, false, 0)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = apng_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, seq, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8,
+                        [&] { const int rc = check_png(c, w, h, channels, host_out, dev_out, cap, 0); return rc ? rc : check_apng_f(w, h, channels, bits, flags, seq); },
+                        [&](Lane &ln) { return apng_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, flags, seq, host_out, dev_out, cap); });
 }
 
 // ---- TIFF ----
@@ -1267,7 +1287,7 @@ int fl_output_apng(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, un
 // Adler-32, and a pad byte; in front of them the header, the IFD, BitsPerSample and — with more than one tile — both arrays.
 size_t fl_tiff_bound(uint32_t w, uint32_t h, int channels, int bits)
 {
-    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4) || (bits != 8 && bits != 16)) return 0;
+    if (!sides_ok(w, h) || (channels != 3 && channels != 4) || (bits != 8 && bits != 16)) return 0;
     const TiffLayout l = tiff_layout(w, h, channels, bits);
     const uint64_t n = 16u + l.H + (uint64_t)l.nt * (l.tile_bytes + 5u + 6u + 1u);
     return n > 0xffffffffull ? 0 : (size_t)n;
@@ -1278,8 +1298,8 @@ static int check_tiff(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int
     REQUIRE(c, "null ctx");
     REQUIRE(channels == 3 || channels == 4, "tiff: channels must be 3 or 4");
     REQUIRE(bits == 8 || bits == 16, "tiff: bits must be 8 or 16");
-    const bool sides = w >= 1 && h >= 1 && w <= 65535u && h <= 65535u;      // (check_encode refuses the others before it looks at the header)
-    if (int rc = check_encode(c, "tiff", w, h, sides ? (size_t)tiff_layout(w, h, channels, bits).H : 0, host_out, dev_out, cap)) return rc;
+    if (int rc = check_sides("tiff", w, h)) return rc;
+    if (int rc = check_encode(c, "tiff", w, h, (size_t)tiff_layout(w, h, channels, bits).H, host_out, dev_out, cap)) return rc;
     REQUIRE(fl_tiff_bound(w, h, channels, bits) != 0, "tiff: the file could pass 2^32 - 1 bytes");
     return FL_OK;
 }
@@ -1295,20 +1315,14 @@ static int tiff_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const uns
 
 int fl_tiff_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_tiff(c, w, h, channels, bits, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "tiff: null source pixels");
-    HIPCHK(hipSetDevice(c->device));
-    return tiff_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "tiff: null source pixels", [&] { return check_tiff(c, w, h, channels, bits, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return tiff_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, channels, bits, host_out, dev_out, cap); });
 }
 
 int fl_output_tiff(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_tiff(c, w, h, channels, bits, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = tiff_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, bits == 16 ? FL_OUT_RGBA16 : FL_OUT_RGBA8, [&] { return check_tiff(c, w, h, channels, bits, host_out, dev_out, cap); },
+                        [&](Lane &ln) { return tiff_encode_on(c, ln, w, h, ln.d_outpix, channels, bits, host_out, dev_out, cap); });
 }
 
 // ---- OpenEXR ----
@@ -1316,7 +1330,7 @@ int fl_output_tiff(fl_ctx *c, uint32_t w, uint32_t h, int channels, int bits, vo
 // 8 of its place in the offset table.  A zlib stream is only chosen where it is smaller.
 size_t fl_exr_bound(uint32_t w, uint32_t h, int channels, int pixel)
 {
-    if (!w || !h || w > 65535u || h > 65535u || (channels != 3 && channels != 4) || (pixel != FL_EXR_HALF && pixel != FL_EXR_FLOAT)) return 0;
+    if (!sides_ok(w, h) || (channels != 3 && channels != 4) || (pixel != FL_EXR_HALF && pixel != FL_EXR_FLOAT)) return 0;
     const ExrLayout l = exr_layout(w, h, channels, pixel);
     const uint64_t n = 16u + l.H + 20ull * l.nt + l.raw;
     return n > 0xffffffffull ? 0 : (size_t)n;
@@ -1327,8 +1341,8 @@ static int check_exr(const fl_ctx *c, uint32_t w, uint32_t h, int channels, int 
     REQUIRE(c, "null ctx");
     REQUIRE(channels == 3 || channels == 4, "exr: channels must be 3 or 4");
     REQUIRE(pixel == FL_EXR_HALF || pixel == FL_EXR_FLOAT, "exr: pixel must be FL_EXR_HALF or FL_EXR_FLOAT");
-    const bool sides = w >= 1 && h >= 1 && w <= 65535u && h <= 65535u;      // (check_encode refuses the others before it looks at the header)
-    if (int rc = check_encode(c, "exr", w, h, sides ? (size_t)exr_layout(w, h, channels, pixel).H : 0, host_out, dev_out, cap)) return rc;
+    if (int rc = check_sides("exr", w, h)) return rc;
+    if (int rc = check_encode(c, "exr", w, h, (size_t)exr_layout(w, h, channels, pixel).H, host_out, dev_out, cap)) return rc;
     REQUIRE(fl_exr_bound(w, h, channels, pixel) != 0, "exr: the file could pass 2^32 - 1 bytes");
     return FL_OK;
 }
@@ -1345,25 +1359,21 @@ static int exr_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const floa
 int fl_exr_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, uint32_t src_stride, int channels, int pixel, void *host_out,
                   uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_exr(c, w, h, channels, pixel, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "exr: null source pixels");
-    REQUIRE(src_stride >= w, "exr: the source's stride is below the width");
-    HIPCHK(hipSetDevice(c->device));
-    return exr_encode_on(c, c->lane(), w, h, (const float4 *)(uintptr_t)src_dev, src_stride, channels, pixel, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "exr: null source pixels", [&] { return check_exr(c, w, h, channels, pixel, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return exr_encode_on(c, ln, w, h, (const float4 *)(uintptr_t)src_dev, src_stride, channels, pixel, host_out, dev_out, cap); },
+                         [&]() -> int { REQUIRE(src_stride >= w, "exr: the source's stride is below the width"); return FL_OK; });
 }
 
 // The front buffer itself is the source: no conversion pass, no dither draw, so nothing of the state the lanes share is touched.
 int fl_output_exr(fl_ctx *c, uint32_t w, uint32_t h, int channels, int pixel, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_exr(c, w, h, channels, pixel, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
     fl_dim d;
-    if (int rc = ensure_fb(ln, w, h, &d)) return rc;
-    if (int rc = flush_pending(c, ln)) return rc;             // deferred ends of the filter chain
-    const float4 *src = (const float4 *)ln.d_front.p + (size_t)d.astride * FL_GUTTER + FL_GUTTER;
-    if (int rc = exr_encode_on(c, ln, w, h, src, d.astride, channels, pixel, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, [&] { return check_exr(c, w, h, channels, pixel, host_out, dev_out, cap); },
+                        [&](Lane &ln) { const int rc = ensure_fb(ln, w, h, &d); return rc ? rc : flush_pending(c, ln); },      // (deferred ends of the filter chain)
+                        [&](Lane &ln) {
+                            const float4 *src = (const float4 *)ln.d_front.p + (size_t)d.astride * FL_GUTTER + FL_GUTTER;
+                            return exr_encode_on(c, ln, w, h, src, d.astride, channels, pixel, host_out, dev_out, cap);
+                        });
 }
 
 // ---- GIF ----
@@ -1371,7 +1381,7 @@ int fl_output_exr(fl_ctx *c, uint32_t w, uint32_t h, int channels, int pixel, vo
 // seven CLEARs of 9 as padding, 12 n + 84 bits, under 3 n / 2 + 11 bytes; segments are never shorter than 256 pixels but the last.
 size_t fl_gif_bound(uint32_t w, uint32_t h)
 {
-    if (!w || !h || w > 65535u || h > 65535u || (uint64_t)w * h > (1ull << 24)) return 0;
+    if (!sides_ok(w, h) || (uint64_t)w * h > (1ull << 24)) return 0;
     const uint64_t n = (uint64_t)w * h, T = (3u * n + 1u) / 2u + 11u * ((n + 255u) / 256u);
     return (size_t)(16u + FL_GIF_HEADER_BYTES + T + (T + 254u) / 255u + 1u);
 }
@@ -1395,27 +1405,21 @@ static int gif_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const unsi
 
 int fl_gif_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "gif: null source pixels");
-    HIPCHK(hipSetDevice(c->device));
-    return gif_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, colors, dither_amp, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "gif: null source pixels", [&] { return check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return gif_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, colors, dither_amp, host_out, dev_out, cap); });
 }
 
 int fl_output_gif(fl_ctx *c, uint32_t w, uint32_t h, int colors, int dither_amp, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = gif_encode_on(c, ln, w, h, ln.d_outpix, colors, dither_amp, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, FL_OUT_RGBA8, [&] { return check_gif(c, w, h, colors, dither_amp, host_out, dev_out, cap); },
+                        [&](Lane &ln) { return gif_encode_on(c, ln, w, h, ln.d_outpix, colors, dither_amp, host_out, dev_out, cap); });
 }
 
 // ---- WebP ----
 // No block can be longer: the proof is with the declaration in include/flame_hip.h.
 size_t fl_webp_bound(uint32_t w, uint32_t h, int channels)
 {
-    if (!w || !h || w > 16384u || h > 16384u || (channels != 3 && channels != 4)) return 0;
+    if (!sides_ok(w, h, 16384u) || (channels != 3 && channels != 4)) return 0;
     const uint64_t n = 16u + 8u + (webp_bound_bits(w, h) + 7u) / 8u + 1u;
     return n > 0xffffffffull ? 0 : (size_t)n;
 }
@@ -1424,7 +1428,7 @@ static int check_webp(const fl_ctx *c, uint32_t w, uint32_t h, int channels, con
 {
     if (int rc = check_encode(c, "webp", w, h, FL_WEBP_HEADER_BYTES, host_out, dev_out, cap)) return rc;
     REQUIRE(channels == 3 || channels == 4, "webp: channels must be 3 or 4");
-    REQUIRE(w <= 16384u && h <= 16384u, "webp: width and height must be 1..16384");
+    REQUIRE(sides_ok(w, h, 16384u), "webp: width and height must be 1..16384");
     REQUIRE(fl_webp_bound(w, h, channels) != 0, "webp: the block could pass 2^32 - 1 bytes");
     return FL_OK;
 }
@@ -1439,20 +1443,14 @@ static int webp_encode_on(fl_ctx *c, Lane &ln, uint32_t w, uint32_t h, const uns
 
 int fl_webp_encode(fl_ctx *c, uint32_t w, uint32_t h, uint64_t src_dev, int channels, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_webp(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    REQUIRE(src_dev, "webp: null source pixels");
-    HIPCHK(hipSetDevice(c->device));
-    return webp_encode_on(c, c->lane(), w, h, (const unsigned char *)(uintptr_t)src_dev, channels, host_out, dev_out, cap);
+    return encode_source(c, src_dev, "webp: null source pixels", [&] { return check_webp(c, w, h, channels, host_out, dev_out, cap); },
+                         [&](Lane &ln) { return webp_encode_on(c, ln, w, h, (const unsigned char *)(uintptr_t)src_dev, channels, host_out, dev_out, cap); });
 }
 
 int fl_output_webp(fl_ctx *c, uint32_t w, uint32_t h, int channels, void *host_out, uint64_t dev_out, size_t cap)
 {
-    if (int rc = check_webp(c, w, h, channels, host_out, dev_out, cap)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    Lane &ln = c->lane();
-    if (int rc = convert_front(c, ln, w, h, FL_OUT_RGBA8, nullptr)) return rc;
-    if (int rc = webp_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap)) return rc;
-    return close_frame(c, ln);
+    return encode_front(c, w, h, FL_OUT_RGBA8, [&] { return check_webp(c, w, h, channels, host_out, dev_out, cap); },
+                        [&](Lane &ln) { return webp_encode_on(c, ln, w, h, ln.d_outpix, channels, host_out, dev_out, cap); });
 }
 
 int fl_sort_u32(fl_ctx *c, uint64_t dst_dev, uint64_t src_dev, uint32_t n, uint32_t lo_bit, uint32_t nbits, int ignore_max,
@@ -1778,6 +1776,23 @@ int fl_debug_math(fl_ctx *c, int fn, uint32_t n, const float *a, const float *b,
     launch_math_tap(ln.stream, fn, n, da, db, dout);
     HIPCHK(hipStreamSynchronize(ln.stream));
     HIPCHK(hipMemcpy(out_bits, dout, dout.bytes(), hipMemcpyDeviceToHost));
+    return FL_OK;
+}
+
+int fl_debug_place(fl_ctx *c, const uint32_t *lens, uint32_t n, uint64_t front, uint64_t *offs_out, uint64_t *total_out)
+{
+    REQUIRE(c && lens && offs_out && total_out, "null argument");
+    REQUIRE(n > 0, "no elements");
+    Lane &ln = c->lane();
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf<uint32_t> dl; DevBuf<u64> doffs;                     // (the total lies behind the n offsets)
+    int rc;
+    if ((rc = dl.reserve(n, "placement tap scratch")) || (rc = doffs.reserve((size_t)n + 1u, "placement tap scratch"))) return rc;
+    HIPCHK(hipMemcpy(dl, lens, dl.bytes(), hipMemcpyHostToDevice));
+    launch_debug_place(ln.stream, dl, n, front, doffs, doffs.p + n);
+    HIPCHK(hipStreamSynchronize(ln.stream));
+    HIPCHK(hipMemcpy(offs_out, doffs, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(total_out, doffs.p + n, 8, hipMemcpyDeviceToHost));
     return FL_OK;
 }
 

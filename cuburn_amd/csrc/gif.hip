@@ -275,23 +275,19 @@ k_gif_lzw(const unsigned char *__restrict__ idx, uint32_t npix, uint32_t S, uint
 }
 
 // ---- placement -----------------------------------------------------------------------------------------------------
-// offs[i] = where segment i's bytes start in the data stream; info = {stream bytes, block bytes, status, 0}.  The record, the descriptor,
+// offs[i] = where segment i's bytes start in the data stream; info's own word is the stream's bytes.  The record, the descriptor,
 // the table, the code size and the block terminator go to `out` (cap >= 16 + kHead: the callers checked).
 __global__ void __launch_bounds__(1024)
 k_gif_scan(const uint32_t *__restrict__ lens, uint32_t nseg, uint32_t S, uint32_t w, uint32_t h, const uint32_t *__restrict__ pal,
            uint32_t *__restrict__ offs, uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, per = (nseg + 1023u) / 1024u, lo = min(t * per, nseg), hi = min(lo + per, nseg);
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += lens[i];
-    u64 run = block_excl_scan_1024(s_sum, mine, t, total);
-    const u64 need = kHead + total + (total + 254u) / 255u + 1u;
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
-    if (t == 0) { info[0] = (uint32_t)total; info[1] = (uint32_t)need; info[2] = status; info[3] = 0u; }
-    write_record(out, need, status, S, t);
-    if (status) return;                                       // a block that does not fit leaves nothing behind the record
-    for (uint32_t i = lo; i < hi; ++i) { offs[i] = (uint32_t)run; run += lens[i]; }
+    const uint32_t t = threadIdx.x;
+    const auto len = [&](uint32_t i) { return lens[i]; };
+    const Placement p = place_pieces(s_sum, nseg, t, 0ull, len);
+    const u64 total = p.total, need = kHead + total + (total + 254u) / 255u + 1u;
+    if (finish_placement(info, out, need, cap, S, (uint32_t)total, t)) return;      // a block that does not fit leaves nothing behind the record
+    store_offsets(offs, p, len);
     unsigned char *blk = out + 16u;
     if (t < 10u) {
         const unsigned char d[10] = {0x2c, 0, 0, 0, 0, (unsigned char)w, (unsigned char)(w >> 8), (unsigned char)h, (unsigned char)(h >> 8), 0x87};
@@ -312,8 +308,8 @@ k_gif_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     extern __shared__ uint32_t s_mem[];
     unsigned char *s_bytes = (unsigned char *)s_mem;
     const uint32_t t = threadIdx.x, seg = blockIdx.x;
-    if (info[2]) return;
-    const uint32_t o = offs[seg], L = lens[seg], total = info[0], last = o + L - 1u;
+    if (info[kInfoStatus]) return;
+    const uint32_t o = offs[seg], L = lens[seg], total = info[kInfoExtra], last = o + L - 1u;
     const uint32_t q0 = o + o / 255u + (o % 255u ? 1u : 0u), q1 = last + last / 255u + 1u, n = q1 - q0 + 1u;
     const unsigned char *from = segbuf + (size_t)seg * stride;
     for (uint32_t i = t; i < n; i += 256u) {

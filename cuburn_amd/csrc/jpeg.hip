@@ -218,7 +218,7 @@ struct Bits {                         // a lane's writer into the interval's bit
 
 // One workgroup of one wave per interval of `ri` MCUs (NB * ri <= 64: a lane per block).  WRITE = false: lens[interval] = bytes of the
 // interval, stuffing and the RSTm / EOI marker behind it included.  WRITE = true: the bytes go to out + base + offs[interval],
-// unless info[2] (the status the scan left) says that the stream does not fit.
+// unless info[kInfoStatus] (the status the scan left) says that the stream does not fit.
 // LDS, sized for the worst case of ri MCUs whatever the input (launch_jpeg_kernels): the symbol tables | bit buffer of
 // ceil(ri * BITS / 32) + 2 words | stuffed bytes, 2 * ceil(ri * BITS / 8) + 2 and 8 of padding
 // OPT: the symbol tables are the frame's own, read from `huff` (k_jpeg_tables wrote them), and BITS is BITS_OPT.
@@ -234,7 +234,7 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
     const uint32_t nbw = (ri * Mcu<S>::bits(OPT) + 31u) / 32u + 2u;
     unsigned char *s_out = (unsigned char *)(s_bits + nbw);
     const uint32_t lane = threadIdx.x, it = blockIdx.x;
-    if (WRITE && info[2]) return;
+    if (WRITE && info[kInfoStatus]) return;
     for (uint32_t i = lane; i < kHuffWords; i += 64) s_huff[i] = OPT ? huff[i] : g_huff.e[i];
     const uint32_t mcu0 = it * ri, nb = NB * min(ri, nmcu - mcu0);
     const bool live = lane < nb;
@@ -323,7 +323,7 @@ k_jpeg_entropy(const short *__restrict__ coef, const unsigned short *__restrict_
 }
 
 // ---- where the intervals go ------------------------------------------------------------------------------------------
-// One workgroup: offs[i] = sum of lens[0 .. i), info = {total low, total high, status}; the record and the header go to `out`.
+// One workgroup: offs[i] = sum of lens[0 .. i), info as encode_device.h lays it out; the record and the header go to `out`.
 // OPT: but for BITS and HUFFVAL of the four DHT segments, which k_jpeg_tables has written there.
 // Where they lie in the header: SOI 2, APP0 18, DQT 2 x 69, SOF0 19 = 177, then FFC4, the length and the class / id in front of each.
 enum { kDhtDcLum = 177 + 5, kDhtAcLum = kDhtDcLum + 28 + 5, kDhtDcChr = kDhtAcLum + 178 + 5, kDhtAcChr = kDhtDcChr + 28 + 5 };
@@ -339,15 +339,11 @@ k_jpeg_scan(const uint32_t *__restrict__ lens, uint32_t nint, u64 *__restrict__ 
             unsigned char *__restrict__ out, u64 cap, uint32_t ri, JpegHeaderArg hdr)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, per = (nint + 1023u) / 1024u, lo = min(t * per, nint), hi = min(lo + per, nint);
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += lens[i];
-    u64 run = block_excl_scan_1024(s_sum, mine, t, total);
-    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += lens[i]; }
-    const u64 need = (u64)FL_JPEG_HEADER_BYTES + total;                    // bytes behind the record
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
-    if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; }
-    write_record(out, need, status, ri, t);
+    const uint32_t t = threadIdx.x;
+    const auto len = [&](uint32_t i) { return lens[i]; };
+    const Placement p = place_pieces(s_sum, nint, t, 0ull, len);
+    store_offsets(offs, p, len);
+    finish_placement(info, out, (u64)FL_JPEG_HEADER_BYTES + p.total, cap, ri, 0u, t);      // (the header's bytes and the stream's lie behind the record)
     if (t < FL_JPEG_HEADER_BYTES && !(OPT && in_dht_body(t))) out[16u + t] = hdr.b[t];      // (cap >= 16 + the header: the callers checked)
 }
 
@@ -601,4 +597,20 @@ void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, ui
         if (optimize) launch_jpeg_kernels<FL_JPEG_444, true>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
         else launch_jpeg_kernels<FL_JPEG_444, false>(st, src, w, h, ri, l, Q, hdr, scratch, out, cap);
     }
+}
+
+// ---- the placement helpers alone (fl_debug_place) ------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024)
+k_debug_place(const uint32_t *__restrict__ lens, uint32_t n, u64 front, u64 *__restrict__ offs, u64 *__restrict__ total)
+{
+    __shared__ u64 s_sum[1024];
+    const auto len = [&](uint32_t i) { return lens[i]; };
+    const Placement p = place_pieces(s_sum, n, threadIdx.x, front, len);
+    store_offsets(offs, p, len);
+    if (threadIdx.x == 0) *total = p.total;
+}
+
+void launch_debug_place(hipStream_t st, const uint32_t *lens, uint32_t n, u64 front, u64 *offs, u64 *total)
+{
+    hipLaunchKernelGGL(k_debug_place, dim3(1), dim3(1024), 0, st, lens, n, front, offs, total);
 }

@@ -124,6 +124,8 @@ struct JpegLayout { uint32_t mw, nmcu, nint; size_t coef, offs, lens, acbits, in
 JpegLayout jpeg_layout(uint32_t w, uint32_t h, uint32_t ri, int sampling);
 void launch_jpeg_encode(hipStream_t st, const unsigned char *src, uint32_t w, uint32_t h, int quality, uint32_t ri, int sampling, bool optimize,
                         uint32_t *scratch, unsigned char *out, size_t cap);
+// encode_device.h's place_pieces and store_offsets in a kernel of their own (fl_debug_place): offs[i] = front + lens[0] + .. + lens[i - 1]
+void launch_debug_place(hipStream_t st, const uint32_t *lens, uint32_t n, u64 front, u64 *offs, u64 *total);
 
 // png.hip: truecolour PNG of 8 or 16 bits a sample from u8 or u16 [h][w][4] (channels 3: the alpha sample is left out).  `scratch` holds
 // png_layout().words words; the 16-byte record, signature + IHDR, one IDAT per segment and IEND go to `out`, of which nothing at or

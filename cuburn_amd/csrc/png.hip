@@ -406,7 +406,7 @@ k_png_segment(const unsigned char *__restrict__ filt, uint32_t F, uint32_t seg, 
 
 // ---- where the segments go ---------------------------------------------------------------------------------------------
 // IDAT i holds segment i; the first also the two bytes of the zlib header, the last also the Adler-32.  offs[i] = where IDAT i starts in
-// the file; info = {file bytes low, high, status, Adler-32}.  The record and the signature + IHDR go to `out`.
+// the file; info's own word is the file's Adler-32.  The record and the signature + IHDR go to `out`.
 // form (kPngFile, kApngIdat, kApngFdat; wave-uniform): a frame block has no header and no IEND, its record's fourth word is the number
 // of chunks, and an fdAT is 4 bytes longer than the IDAT of the same segment.
 enum : uint32_t { kPngFile = 0, kApngIdat = 1, kApngFdat = 2 };
@@ -417,25 +417,22 @@ k_png_scan(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ adl, 
            u64 *__restrict__ offs, uint32_t *__restrict__ info, unsigned char *__restrict__ out, u64 cap, PngHeaderArg hdr, uint32_t form)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, per = (nseg + 1023u) / 1024u, lo = min(t * per, nseg), hi = min(lo + per, nseg);
+    const uint32_t t = threadIdx.x;
     const uint32_t frame = 12u + (form == kApngFdat ? 4u : 0u), front = form == kPngFile ? FL_PNG_HEADER_BYTES : 0u;
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += frame + idat_data_bytes(lens[i], i, nseg);
-    u64 run = (u64)front + block_excl_scan_1024(s_sum, mine, t, total);
-    for (uint32_t i = lo; i < hi; ++i) { offs[i] = run; run += frame + idat_data_bytes(lens[i], i, nseg); }
-    const u64 need = (u64)front + total + (form == kPngFile ? 12u : 0u);   // bytes behind the record, IEND included where there is one
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
+    const auto len = [&](uint32_t i) { return frame + idat_data_bytes(lens[i], i, nseg); };
+    const Placement p = place_pieces(s_sum, nseg, t, (u64)front, len);
+    store_offsets(offs, p, len);
+    uint32_t A = 1u, B = 0u;
     if (t == 0) {
         // Adler-32 of a concatenation: a = a1 + a2 - 1, b = b1 + b2 + len2 * (a1 - 1), mod 65521
-        uint32_t A = 1u, B = 0u;
         for (uint32_t i = 0; i < nseg; ++i) {
             const uint32_t a2 = adl[i] & 0xffffu, b2 = adl[i] >> 16, len2 = i + 1u == nseg ? F - i * seg : seg;
             B = (uint32_t)((B + b2 + (u64)(len2 % kAdlerMod) * ((A + kAdlerMod - 1u) % kAdlerMod)) % kAdlerMod);
             A = (A + a2 + kAdlerMod - 1u) % kAdlerMod;
         }
-        info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = B << 16 | A;
     }
-    write_record(out, need, status, seg, t);
+    // bytes behind the record, IEND included where there is one
+    finish_placement(info, out, (u64)front + p.total + (form == kPngFile ? 12u : 0u), cap, seg, B << 16 | A, t);
     if (form == kPngFile) {
         if (t < FL_PNG_HEADER_BYTES) out[16u + t] = hdr.b[t];              // (cap >= 16 + the header: the callers checked)
     } else if (t >= 12u && t < 16u) out[t] = (unsigned char)(nseg >> (8u * (t - 12u)));      // (the thread that stored the record's zero there)
@@ -474,10 +471,10 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
     __shared__ uint32_t s_tab[256], s_crc;
     unsigned char *s_chunk = (unsigned char *)s_mem;
     const uint32_t t = threadIdx.x, it = blockIdx.x;
-    if (info[2]) return;
+    if (info[kInfoStatus]) return;
     const bool first = it == 0, last = it + 1u == nseg;
     const bool fdat = form == kApngFdat, iend = last && form == kPngFile;
-    const uint32_t L = lens[it], dlen = idat_data_bytes(L, it, nseg), sq = fdat ? 4u : 0u, data = 8u + sq, body = data + (first ? 2u : 0u);
+    const uint32_t L = lens[it], dlen = idat_data_bytes(L, it, nseg), sq = fdat ? 4u : 0u, data = 8u + sq;
     {
         uint32_t c = t;
 #pragma unroll
@@ -491,22 +488,13 @@ k_png_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const ui
         const uint32_t tag = fdat ? 0x54416466u : 0x54414449u;               // "fdAT", "IDAT"
         for (uint32_t i = 0; i < 4u; ++i) s_chunk[4u + i] = (unsigned char)(tag >> (8u * i));
         if (fdat) for (uint32_t i = 0; i < 4u; ++i) s_chunk[8u + i] = (unsigned char)(no >> (24u - 8u * i));
-        if (first) { s_chunk[data] = 0x78; s_chunk[data + 1u] = 0x01; }      // zlib: deflate, 32 KiB window, no dictionary, FCHECK
-        if (last) {
-            const uint32_t ad = info[3];
-            for (uint32_t i = 0; i < 4u; ++i) s_chunk[body + L + i] = (unsigned char)(ad >> (24u - 8u * i));
-        }
         if (iend) {
             const unsigned char tail[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
             for (uint32_t i = 0; i < 12u; ++i) s_chunk[12u + dlen + i] = tail[i];
         }
     }
-    const uint32_t *src = (const uint32_t *)(segbuf + (size_t)it * stride);
-    for (uint32_t i = t; i < (L + 3u) / 4u; i += 256u) {
-        const uint32_t wd = src[i];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) s_chunk[body + 4u * i + k] = (unsigned char)(wd >> (8u * k));
-    }
+    // the segment, behind the zlib header in the first chunk and in front of the file's Adler-32 in the last
+    stage_block(s_chunk + data, (const uint32_t *)(segbuf + (size_t)it * stride), L, t, first, last ? info + kInfoExtra : nullptr);
     __syncthreads();
     // the CRC of tag (+ sequence number) + data: M bytes from s_chunk + 4, padded in front to 256 shares of S
     const uint32_t M = 4u + sq + dlen, S = (M + 255u) / 256u, pad = 256u * S - M;

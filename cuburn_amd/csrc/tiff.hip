@@ -59,40 +59,28 @@ k_tiff_tiles(const unsigned char *__restrict__ src, uint32_t w, uint32_t h, uint
 __device__ __forceinline__ uint32_t tile_data_bytes(uint32_t len) { return len + 6u; }
 __device__ __forceinline__ uint32_t tile_placed_bytes(uint32_t len, uint32_t i, uint32_t nt) { return len + 6u + (i + 1u < nt ? len & 1u : 0u); }
 
-__device__ __forceinline__ void put_le32(unsigned char *p, uint32_t v)      // (p may have any alignment)
-{
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) p[k] = (unsigned char)(v >> (8u * k));
-}
-
-// offs[i] = where tile i starts in the file (the file stays below 2^32 bytes: the callers checked the bound); info = {file bytes low,
-// high, status, 0}.  The record, the header and both arrays go to `out` (cap >= 16 + the header and the arrays: the callers checked).
+// offs[i] = where tile i starts in the file (the file stays below 2^32 bytes: the callers checked the bound).  The record, the header
+// and both arrays go to `out` (cap >= 16 + the header and the arrays: the callers checked).
 __global__ void __launch_bounds__(1024)
 k_tiff_scan(const uint32_t *__restrict__ lens, uint32_t nt, uint32_t tile_bytes, uint32_t *__restrict__ offs, uint32_t *__restrict__ info,
             unsigned char *__restrict__ out, u64 cap, TiffHeaderArg hdr)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, per = (nt + 1023u) / 1024u, lo = min(t * per, nt), hi = min(lo + per, nt);
+    const uint32_t t = threadIdx.x;
     const u64 H = (u64)hdr.n + (nt > 1u ? 8ull * nt : 0ull);
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += tile_placed_bytes(lens[i], i, nt);
-    u64 run = H + block_excl_scan_1024(s_sum, mine, t, total);
-    const u64 need = H + total;
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
-    if (t == 0) { info[0] = (uint32_t)need; info[1] = (uint32_t)(need >> 32); info[2] = status; info[3] = 0u; }
-    write_record(out, need, status, tile_bytes, t);
+    const auto len = [&](uint32_t i) { return tile_placed_bytes(lens[i], i, nt); };
+    const Placement p = place_pieces(s_sum, nt, t, H, len);
+    finish_placement(info, out, H + p.total, cap, tile_bytes, 0u, t);
     if (t < hdr.n) {
         uint32_t v = hdr.b[t];
         if (nt == 1u && t - hdr.count_at < 4u) v = tile_data_bytes(lens[0]) >> (8u * (t - hdr.count_at)) & 0xffu;
         out[16u + t] = (unsigned char)v;
     }
     unsigned char *po = out + 16u + hdr.n, *pc = po + 4u * (size_t)nt;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t len = lens[i];
-        offs[i] = (uint32_t)run;
-        if (nt > 1u) { put_le32(po + 4u * (size_t)i, (uint32_t)run); put_le32(pc + 4u * (size_t)i, tile_data_bytes(len)); }
-        run += tile_placed_bytes(len, i, nt);
-    }
+    for_placed(p, len, [&](uint32_t i, u64 at) {
+        offs[i] = (uint32_t)at;
+        if (nt > 1u) { put_le32(po + 4u * (size_t)i, (uint32_t)at); put_le32(pc + 4u * (size_t)i, tile_data_bytes(lens[i])); }
+    });
 }
 
 // ---- the finished tiles ------------------------------------------------------------------------------------------------
@@ -105,20 +93,10 @@ k_tiff_gather(const unsigned char *__restrict__ segbuf, uint32_t stride, const u
     extern __shared__ uint32_t s_mem[];
     unsigned char *s_tile = (unsigned char *)s_mem;
     const uint32_t t = threadIdx.x, it = blockIdx.x;
-    if (info[2]) return;
+    if (info[kInfoStatus]) return;
     const uint32_t L = lens[it];
-    if (t == 0) {
-        s_tile[0] = 0x78; s_tile[1] = 0x01;                   // zlib: deflate, 32 KiB window, no dictionary, FCHECK
-        const uint32_t ad = adl[it];                          // (a | b << 16: the Adler-32 as it is sent, most significant byte first)
-        for (uint32_t i = 0; i < 4u; ++i) s_tile[2u + L + i] = (unsigned char)(ad >> (24u - 8u * i));
-        s_tile[6u + L] = 0;                                   // the pad byte
-    }
-    const uint32_t *src = (const uint32_t *)(segbuf + (size_t)it * stride);
-    for (uint32_t i = t; i < (L + 3u) / 4u; i += 256u) {
-        const uint32_t wd = src[i];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) if (4u * i + k < L) s_tile[2u + 4u * i + k] = (unsigned char)(wd >> (8u * k));
-    }
+    if (t == 0) s_tile[6u + L] = 0;                           // the pad byte
+    stage_block(s_tile, (const uint32_t *)(segbuf + (size_t)it * stride), L, t, true, adl + it);
     __syncthreads();
     store_bytes<256>(out + 16u + offs[it], s_mem, tile_placed_bytes(L, it, nt), t);      // (s_tile, with the 2 words of padding behind it)
 }

@@ -385,22 +385,18 @@ k_webp_stats(const uint32_t *__restrict__ src, uint32_t w, uint32_t h, int alpha
 }
 
 // ---- placement -----------------------------------------------------------------------------------------------------
-// off[i] = the bit at which piece i (group headers, then runs in raster order) begins; info = {payload bytes, status, 0, 0}.
+// off[i] = the bit at which piece i (group headers, then runs in raster order) begins; info's own word is the payload's bytes.
 __global__ void __launch_bounds__(1024)
 k_webp_scan(const uint32_t *__restrict__ cnt, uint32_t n, const uint32_t *__restrict__ subinfo, u64 *__restrict__ off, uint32_t *__restrict__ info,
             unsigned char *__restrict__ out, u64 cap)
 {
     __shared__ u64 s_sum[1024];
-    const uint32_t t = threadIdx.x, per = (n + 1023u) / 1024u, lo = min(t * per, n), hi = min(lo + per, n);
-    u64 mine = 0, total;
-    for (uint32_t i = lo; i < hi; ++i) mine += cnt[i];
-    u64 run = subinfo[0] + block_excl_scan_1024(s_sum, mine, t, total);
-    const u64 payload = (subinfo[0] + total + 7u) / 8u, need = 8u + payload + (payload & 1u);
-    const uint32_t status = need > cap - 16u ? 1u : 0u;
-    if (t == 0) { info[0] = (uint32_t)payload; info[1] = status; info[2] = 0u; info[3] = 0u; }
-    write_record(out, need, status, kPB | kEB << 8, t);
-    if (status) return;                                       // a block that does not fit leaves nothing behind the record
-    for (uint32_t i = lo; i < hi; ++i) { off[i] = run; run += cnt[i]; }
+    const uint32_t t = threadIdx.x;
+    const auto len = [&](uint32_t i) { return cnt[i]; };
+    const Placement p = place_pieces(s_sum, n, t, (u64)subinfo[0], len);
+    const u64 payload = (subinfo[0] + p.total + 7u) / 8u, need = 8u + payload + (payload & 1u);
+    if (finish_placement(info, out, need, cap, kPB | kEB << 8, (uint32_t)payload, t)) return;      // a block that does not fit leaves nothing behind the record
+    store_offsets(off, p, len);
     if (t < 8u) {
         const unsigned char hd[8] = {'V', 'P', '8', 'L', (unsigned char)payload, (unsigned char)(payload >> 8), (unsigned char)(payload >> 16), (unsigned char)(payload >> 24)};
         out[16u + t] = hd[t];
@@ -410,8 +406,8 @@ k_webp_scan(const uint32_t *__restrict__ cnt, uint32_t n, const uint32_t *__rest
 
 __global__ void __launch_bounds__(256) k_webp_clear(const uint32_t *__restrict__ info, uint32_t *__restrict__ asmb)
 {
-    if (info[1]) return;
-    const uint32_t nw = (info[0] + 3u) / 4u + 2u;
+    if (info[kInfoStatus]) return;
+    const uint32_t nw = (info[kInfoExtra] + 3u) / 4u + 2u;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw; i += gridDim.x * 256u) asmb[i] = 0;
 }
 
@@ -420,7 +416,7 @@ __global__ void __launch_bounds__(256)
 k_webp_heads(const uint32_t *__restrict__ hdr, const uint32_t *__restrict__ cnt, const u64 *__restrict__ off, const uint32_t *__restrict__ sub,
              const uint32_t *__restrict__ subinfo, const uint32_t *__restrict__ info, uint32_t G, uint32_t *__restrict__ asmb)
 {
-    if (info[1]) return;
+    if (info[kInfoStatus]) return;
     const uint32_t g = blockIdx.x;
     if (g < G) or_bits(asmb, off[g], hdr + (size_t)g * kHdrWords, cnt[g], threadIdx.x, 256u);
     else or_bits(asmb, 0ull, sub, subinfo[0], threadIdx.x, 256u);
@@ -433,7 +429,7 @@ k_webp_emit(const uint32_t *__restrict__ src, uint32_t w, uint32_t h, int alpha,
             const uint32_t *__restrict__ codes, const u64 *__restrict__ roff, const uint32_t *__restrict__ info, uint32_t *__restrict__ asmb)
 {
     __shared__ uint32_t s_w[4][124];
-    if (info[1]) return;
+    if (info[kInfoStatus]) return;
     const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6, nr = h * gx, r = blockIdx.x * 4u + wv;
     uint32_t *sw = s_w[wv];
     for (uint32_t i = lane; i < 124u; i += 64u) sw[i] = 0;
@@ -475,8 +471,8 @@ k_webp_copy(const uint32_t *__restrict__ asmb, const uint32_t *__restrict__ info
 {
     __shared__ uint32_t s_b[1026];
     const uint32_t t = threadIdx.x, start = blockIdx.x * 4096u;
-    if (info[1] || start >= info[0]) return;
-    const uint32_t n = min(4096u, info[0] - start);
+    if (info[kInfoStatus] || start >= info[kInfoExtra]) return;
+    const uint32_t n = min(4096u, info[kInfoExtra] - start);
     for (uint32_t i = t; i <= n / 4u + 1u; i += 256u) s_b[i] = asmb[start / 4u + i];
     __syncthreads();
     store_bytes<256>(out + 24u + start, s_b, n, t);

@@ -25,7 +25,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from .output import DeviceEncodedOutput, DeviceJPEGOutput, Output
+from .output import DeviceEncodedOutput, DeviceJPEGOutput, Output, _bits, _bool, _int_in, _one_of
 
 
 class _EncoderPipe(object):
@@ -287,7 +287,66 @@ def _avi_header(w, h, fps, sizes, movi_bytes):
     return out
 
 
-class MJPEGOutput(DeviceJPEGOutput):
+def frame_ticks(k, fps, per_second):
+    """How many ticks (``per_second`` of them a second) frame k lasts: round(u (k + 1) / fps) - round(u k / fps) with
+    u = per_second, so a file keeps the rate on average."""
+    return int(round(float(per_second) * (k + 1) / fps)) - int(round(float(per_second) * k / fps))
+
+
+class _FrameFile(object):
+    """What the animations the device writes frame by frame share (mixed into a DeviceEncodedOutput): the temporary file, its frame
+    count and frame size, ``abort``, and ``encode(buf)`` — ``None`` flushes; else the block behind the record is parsed for its
+    size, a size other than the last flushes and starts a new file (as X264Output does), the first frame of a file writes the
+    header, and the frame's wrapper and the block, copied out of the pinned buffer, follow.  A subclass supplies ``_parse(data)
+    -> (h, w)`` or raises, ``_header() -> bytes``, ``_wrap(data) -> (bytes in front, bytes behind)``, which may refuse the
+    frame, and ``_finish() -> the complete file``."""
+
+    @staticmethod
+    def _need_fps(name, fps, most=None, why=None):
+        if not fps > 0:
+            raise ValueError('%s needs fps above 0' % name)
+        if most is not None and fps > most:
+            raise ValueError('%s: fps %g gives frames of %s: use %d or less' % (name, fps, why, most))
+
+    def _reset(self):
+        self._file, self._nframes, self.framesize = None, 0, None
+
+    def abort(self):
+        if self._file is not None:
+            self._file.close()
+        self._reset()
+
+    def _flush(self):
+        if self._nframes == 0:
+            return {}, []
+        f = self._finish()
+        f.seek(0)
+        self._reset()
+        return {self.suffix: f}, []
+
+    def _add(self, data):
+        front, behind = self._wrap(data)
+        if self._file is None:
+            self._file = tempfile.TemporaryFile()
+            self._file.write(self._header())
+        self._file.write(front)
+        self._file.write(memoryview(np.ascontiguousarray(data)))      # the pinned frame buffer is reused by the next frame: the bytes are copied out here
+        self._file.write(behind)
+        self._nframes += 1
+
+    def encode(self, buf):
+        if buf is None:
+            return self._flush()
+        data = self.file_bytes(buf, self.noun)
+        size, out = self._parse(data), ({}, [])
+        if self.framesize != size:
+            out = self._flush()
+            self.framesize = size
+        self._add(data)
+        return out
+
+
+class MJPEGOutput(_FrameFile, DeviceJPEGOutput):
     """Animations as Motion-JPEG in an AVI 1.0 file (``output: {"type": "mjpeg", "quality": 1..100, "sampling": "420" | "444",
     "optimize": bool}``, ``--codec mjpeg``; ``optimize`` as DeviceJPEGOutput's, every frame with tables of its own): every frame leaves the GPU as a finished baseline JPEG (``copy`` is DeviceJPEGOutput's) and becomes a
     ``00dc`` chunk; ``encode(None)`` writes the header and the ``idx1`` index and returns the file.  No external program.
@@ -297,67 +356,50 @@ class MJPEGOutput(DeviceJPEGOutput):
     def __init__(self, fps=24, quality=90, sampling='420', alpha=False, optimize=False):
         if alpha:
             raise ValueError('mjpeg has no alpha plane: use x264 with "alpha"')
-        if not fps > 0:
-            raise ValueError('mjpeg needs fps above 0')
+        self._need_fps('mjpeg', fps)
         DeviceJPEGOutput.__init__(self, quality=quality, sampling=sampling, optimize=optimize)
         self.fps = fps
-        self._file, self._sizes, self._movi, self.framesize = None, [], 0, None
+        self._reset()
 
-    def abort(self):
-        if self._file is not None:
-            self._file.close()
-        self._file, self._sizes, self._movi = None, [], 0
+    def _reset(self):
+        _FrameFile._reset(self)
+        self._sizes, self._movi = [], 0
 
-    def _flush(self):
-        if self._file is None:
-            return {}, []
-        f, sizes, off = self._file, self._sizes, 4
-        index = bytearray()
-        for n in sizes:                           # offsets count from the 'movi' fourcc
-            index += struct.pack('<4sIII', b'00dc', 0x10, off, n)       # 0x10: AVIIF_KEYFRAME
-            off += 8 + n + (n & 1)
-        f.write(b'idx1' + struct.pack('<I', len(index)) + index)
-        f.seek(0)
-        f.write(_avi_header(self.framesize[1], self.framesize[0], self.fps, sizes, self._movi))
-        f.seek(0)
-        self._file, self._sizes, self._movi = None, [], 0
-        return {'.avi': f}, []
-
-    def encode(self, buf):
-        out = ({}, [])
-        if buf is None:
-            return self._flush()
-        data = self.file_bytes(buf, self.noun)
+    def _parse(self, data):
         if len(data) < _JPEG_SOF0 + 9 or bytes(data[_JPEG_SOF0:_JPEG_SOF0 + 2]) != b'\xff\xc0':
             raise IOError('the frame is not a JPEG stream of the device encoder')
-        size = struct.unpack('>HH', bytes(data[_JPEG_SOF0 + 5:_JPEG_SOF0 + 9]))      # (height, width)
-        if self.framesize != size:
-            out = self._flush()
-            self.framesize = size
+        return struct.unpack('>HH', bytes(data[_JPEG_SOF0 + 5:_JPEG_SOF0 + 9]))      # (height, width)
+
+    def _header(self):
+        return b'\0' * _AVI_MOVI_DATA                  # its place: written at the flush, when the sizes are known
+
+    def _wrap(self, data):
         n = len(data)
         if _AVI_MOVI_DATA + self._movi + 8 + n + (n & 1) + 8 + 16 * (len(self._sizes) + 1) > AVI_MAX_BYTES:
             raise IOError('the AVI file would pass %d bytes at frame %d: render shorter files with "shard" (--shard SECS)'
                           % (AVI_MAX_BYTES, len(self._sizes) + 1))
-        if self._file is None:
-            self._file = tempfile.TemporaryFile()
-            self._file.write(b'\0' * _AVI_MOVI_DATA)
-        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
-        self._file.write(b'00dc' + struct.pack('<I', n))
-        self._file.write(memoryview(np.ascontiguousarray(data)))
-        if n & 1:
-            self._file.write(b'\0')
         self._sizes.append(n)
         self._movi += 8 + n + (n & 1)
-        return out
+        return b'00dc' + struct.pack('<I', n), b'\0' * (n & 1)
+
+    def _finish(self):
+        f, off = self._file, 4
+        index = bytearray()
+        for n in self._sizes:                     # offsets count from the 'movi' fourcc
+            index += struct.pack('<4sIII', b'00dc', 0x10, off, n)       # 0x10: AVIIF_KEYFRAME
+            off += 8 + n + (n & 1)
+        f.write(b'idx1' + struct.pack('<I', len(index)) + index)
+        f.seek(0)
+        f.write(_avi_header(self.framesize[1], self.framesize[0], self.fps, self._sizes, self._movi))
+        return f
 
 
 def gif_delays(nframes, fps):
-    """Centiseconds of frames 0 .. nframes - 1: frame k lasts round(100 (k + 1) / fps) - round(100 k / fps), so the file keeps
-    the rate on average."""
-    return [int(round(100.0 * (k + 1) / fps)) - int(round(100.0 * k / fps)) for k in range(nframes)]
+    """Centiseconds of frames 0 .. nframes - 1 (frame_ticks at 100 a second)."""
+    return [frame_ticks(k, fps, 100) for k in range(nframes)]
 
 
-class GIFOutput(DeviceEncodedOutput):
+class GIFOutput(_FrameFile, DeviceEncodedOutput):
     """Animations as a looping GIF89a file (``output: {"type": "gif", "colors": 2..256, "dither": "ordered" | "none",
     "loop": 0..65535}``, ``--codec gif``): every frame leaves the GPU as a finished frame block with a palette of its own — median
     cut, ordered dither, LZW (include/flame_hip.h, fl_output_gif) — and the host writes the header, the NETSCAPE2.0 loop
@@ -367,18 +409,11 @@ class GIFOutput(DeviceEncodedOutput):
     suffix, entry, noun = '.gif', 'fl_output_gif', 'GIF frame block'
 
     def __init__(self, fps=24, colors=256, dither='ordered', loop=0):
-        if not fps > 0:
-            raise ValueError('gif needs fps above 0')
-        if fps > 50:
-            raise ValueError('gif: fps %g gives frames of less than 2 centiseconds, which browsers play at 10: use 50 or less' % fps)
-        if isinstance(colors, bool) or not isinstance(colors, int) or not 2 <= colors <= 256:
-            raise ValueError('output.colors must be an integer in 2..256')
-        if not isinstance(dither, str) or dither not in _lib.GIF_DITHER:
-            raise ValueError('output.dither must be "ordered" or "none", not "%s"' % (dither,))
-        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
-            raise ValueError('output.loop must be an integer in 0..65535')
-        self.fps, self.colors, self.dither, self.loop = fps, colors, dither, loop
-        self._file, self._nframes, self.framesize = None, 0, None
+        self._need_fps('gif', fps, 50, 'less than 2 centiseconds, which browsers play at 10')
+        self.fps, self.colors = fps, _int_in('colors', colors, 2, 256)
+        self.dither = _one_of('dither', dither, _lib.GIF_DITHER, '"ordered" or "none"')
+        self.loop = _int_in('loop', loop, 0, 65535)
+        self._reset()
 
     def arguments(self):
         return (self.colors, _lib.GIF_DITHER[self.dither])
@@ -387,47 +422,29 @@ class GIFOutput(DeviceEncodedOutput):
         """The library's bound: no frame needs more (twelve bits a pixel and the segments' framing)."""
         return int(_lib.load().fl_gif_bound(dim.w, dim.h))
 
-    def abort(self):
-        if self._file is not None:
-            self._file.close()
-        self._file, self._nframes = None, 0
-
-    def _flush(self):
-        if self._file is None:
-            return {}, []
-        f = self._file
-        f.write(b'\x3b')
-        f.seek(0)
-        self._file, self._nframes = None, 0
-        return {'.gif': f}, []
-
-    def encode(self, buf):
-        out = ({}, [])
-        if buf is None:
-            return self._flush()
-        data = self.file_bytes(buf, self.noun)
+    def _parse(self, data):
         if len(data) < _lib.GIF_HEADER_BYTES + 2 or data[0] != 0x2c or data[9] != 0x87:
             raise IOError('the frame is not a block of the device GIF encoder')
         w, h = struct.unpack('<HH', bytes(data[5:9]))
-        if self.framesize != (h, w):
-            out = self._flush()
-            self.framesize = (h, w)
-        if self._file is None:
-            self._file = tempfile.TemporaryFile()
-            self._file.write(b'GIF89a' + struct.pack('<HH', w, h) + b'\x70\x00\x00')      # no global table, 8 bits a primary
-            self._file.write(b'\x21\xff\x0bNETSCAPE2.0\x03\x01' + struct.pack('<H', self.loop) + b'\x00')
-        k = self._nframes
-        delay = int(round(100.0 * (k + 1) / self.fps)) - int(round(100.0 * k / self.fps))
-        self._file.write(b'\x21\xf9\x04\x04' + struct.pack('<H', delay) + b'\x00\x00')      # disposal 1: leave the frame in place
-        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
-        self._file.write(memoryview(np.ascontiguousarray(data)))
-        self._nframes += 1
-        return out
+        return h, w
+
+    def _header(self):
+        h, w = self.framesize
+        return (b'GIF89a' + struct.pack('<HH', w, h) + b'\x70\x00\x00'      # no global table, 8 bits a primary
+                + b'\x21\xff\x0bNETSCAPE2.0\x03\x01' + struct.pack('<H', self.loop) + b'\x00')
+
+    def _wrap(self, data):
+        delay = frame_ticks(self._nframes, self.fps, 100)
+        return b'\x21\xf9\x04\x04' + struct.pack('<H', delay) + b'\x00\x00', b''      # disposal 1: leave the frame in place
+
+    def _finish(self):
+        self._file.write(b'\x3b')
+        return self._file
 
 
 def webp_duration(k, fps):
-    """Milliseconds of frame k: round(1000 (k + 1) / fps) - round(1000 k / fps), so the file keeps the rate on average."""
-    return int(round(1000.0 * (k + 1) / fps)) - int(round(1000.0 * k / fps))
+    """Milliseconds of frame k (frame_ticks at 1000 a second)."""
+    return frame_ticks(k, fps, 1000)
 
 
 def webp_durations(nframes, fps):
@@ -438,7 +455,7 @@ def _u24(v):
     return struct.pack('<I', v)[:3]
 
 
-class WebPOutput(DeviceEncodedOutput):
+class WebPOutput(_FrameFile, DeviceEncodedOutput):
     """Stills and animations as lossless WebP (``output: {"type": "webp", "alpha": bool, "loop": 0..65535}``, ``--codec webp``):
     every frame leaves the GPU as a finished `VP8L` chunk — subtract green, a predictor mode per 16 x 16 tile, prefix codes per
     64 x 64 tile (include/flame_hip.h, fl_output_webp) — and the host writes the RIFF file around the chunks.  A file that ends
@@ -449,19 +466,18 @@ class WebPOutput(DeviceEncodedOutput):
     PB | EB << 8, the tiles' size bits."""
     suffix, entry, noun = '.webp', 'fl_output_webp', 'WebP frame block'
     LIMIT = (1 << 32) - 10                 # a RIFF size is 32 bits
+    _HEAD = 12 + 18 + 14                   # `RIFF`, `VP8X` and `ANIM` in front of an animation's frames
+    _TOO_LONG = 'the WebP file would pass 4 GiB: use shard to split the animation into several files'
 
     def __init__(self, fps=24, alpha=False, loop=0):
-        if not fps > 0:
-            raise ValueError('webp needs fps above 0')
-        if fps > 90:
-            raise ValueError('webp: fps %g gives frames of 10 ms or less, which players show for 100 ms: use 90 or less' % fps)
-        if not isinstance(alpha, bool):
-            raise ValueError('output.alpha must be true or false')
-        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
-            raise ValueError('output.loop must be an integer in 0..65535')
-        self.fps, self.alpha, self.loop = fps, alpha, loop
+        self._need_fps('webp', fps, 90, '10 ms or less, which players show for 100 ms')
+        self.fps, self.alpha, self.loop = fps, _bool('alpha', alpha), _int_in('loop', loop, 0, 65535)
         self.channels = 4 if alpha else 3
-        self._file, self._first, self._nframes, self._size, self.framesize = None, None, 0, 0, None
+        self._reset()
+
+    def _reset(self):
+        _FrameFile._reset(self)
+        self._first, self._size = None, 0      # the frame held back (it counts as one while it is); the bytes of the animation's `ANMF`s
 
     def argument(self):
         return self.channels
@@ -470,66 +486,47 @@ class WebPOutput(DeviceEncodedOutput):
         """The library's bound: no frame needs more (60 bits a pixel and the codes' headers)."""
         return int(_lib.load().fl_webp_bound(dim.w, dim.h, self.channels))
 
-    def abort(self):
-        if self._file is not None:
-            self._file.close()
-        self._file, self._first, self._nframes, self._size = None, None, 0, 0
-
-    def _flush(self):
-        if self._nframes == 0:
-            return {}, []
-        if self._nframes == 1:
-            f = tempfile.TemporaryFile()
-            f.write(b'RIFF' + struct.pack('<I', 4 + len(self._first)) + b'WEBP')
-            f.write(self._first)
-        else:
-            f = self._file
-            f.seek(4)
-            f.write(struct.pack('<I', self._size - 8))
-        f.seek(0)
-        self._file, self._first, self._nframes, self._size = None, None, 0, 0
-        return {'.webp': f}, []
-
-    def _anmf(self, block):
-        h, w = self.framesize
-        dur = webp_duration(self._nframes, self.fps)
-        if self._size + 24 + len(block) > self.LIMIT:
-            self.abort()
-            raise IOError('the WebP file would pass 4 GiB: use shard to split the animation into several files')
-        self._file.write(b'ANMF' + struct.pack('<I', 16 + len(block)) + _u24(0) + _u24(0) + _u24(w - 1) + _u24(h - 1) + _u24(dur) + b'\x02')
-        self._file.write(block)
-        self._size += 24 + len(block)
-        self._nframes += 1
-
-    def encode(self, buf):
-        out = ({}, [])
-        if buf is None:
-            return self._flush()
-        data = self.file_bytes(buf, self.noun)
+    def _parse(self, data):
         if len(data) < 8 + 5 or bytes(data[:4]) != b'VP8L' or data[8] != 0x2f or len(data) & 1:
             raise IOError('the frame is not a block of the device WebP encoder')
         bits, = struct.unpack('<I', bytes(data[9:13]))
-        w, h = (bits & 0x3fff) + 1, (bits >> 14 & 0x3fff) + 1
-        if self.framesize != (h, w):
-            out = self._flush()
-            self.framesize = (h, w)
-        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
-        block = bytes(memoryview(np.ascontiguousarray(data)))
-        if self._nframes == 0:
+        return (bits >> 14 & 0x3fff) + 1, (bits & 0x3fff) + 1
+
+    def _header(self):
+        h, w = self.framesize
+        return (b'RIFF\0\0\0\0WEBP' + b'VP8X' + struct.pack('<I', 10) + bytes([0x12 if self.alpha else 0x02, 0, 0, 0]) + _u24(w - 1) + _u24(h - 1)
+                + b'ANIM' + struct.pack('<IIH', 6, 0, self.loop))
+
+    def _wrap(self, block):
+        h, w = self.framesize
+        dur = webp_duration(self._nframes, self.fps)
+        if self._HEAD + self._size + 24 + len(block) > self.LIMIT:
+            self.abort()
+            raise IOError(self._TOO_LONG)
+        self._size += 24 + len(block)
+        return b'ANMF' + struct.pack('<I', 16 + len(block)) + _u24(0) + _u24(0) + _u24(w - 1) + _u24(h - 1) + _u24(dur) + b'\x02', b''
+
+    def _add(self, data):
+        if self._nframes == 0:                              # the first frame of a file: held back, copied out of the pinned buffer
+            block = bytes(memoryview(np.ascontiguousarray(data)))
             if 12 + len(block) > self.LIMIT:
-                raise IOError('the WebP file would pass 4 GiB: use shard to split the animation into several files')
+                raise IOError(self._TOO_LONG)
             self._first, self._nframes = block, 1
-            return out
-        if self._nframes == 1:                              # a second frame: the file is an animation
-            self._file = tempfile.TemporaryFile()
-            self._file.write(b'RIFF\0\0\0\0WEBP')
-            self._file.write(b'VP8X' + struct.pack('<I', 10) + bytes([0x12 if self.alpha else 0x02, 0, 0, 0]) + _u24(w - 1) + _u24(h - 1))
-            self._file.write(b'ANIM' + struct.pack('<IIH', 6, 0, self.loop))
-            self._size, self._nframes = 12 + 18 + 14, 0
-            first, self._first = self._first, None
-            self._anmf(first)
-        self._anmf(block)
-        return out
+            return
+        if self._first is not None:                         # a second frame: the file is an animation
+            first, self._first, self._nframes = self._first, None, 0
+            _FrameFile._add(self, first)
+        _FrameFile._add(self, data)
+
+    def _finish(self):
+        if self._first is not None:                         # one frame: the simple format
+            f = tempfile.TemporaryFile()
+            f.write(b'RIFF' + struct.pack('<I', 4 + len(self._first)) + b'WEBP')
+            f.write(self._first)
+            return f
+        self._file.seek(4)
+        self._file.write(struct.pack('<I', self._HEAD + self._size - 8))
+        return self._file
 
 
 def apng_delay(fps):
@@ -545,7 +542,7 @@ def _png_chunk(tag, data):
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
 
 
-class APNGOutput(DeviceEncodedOutput):
+class APNGOutput(_FrameFile, DeviceEncodedOutput):
     """Animations as APNG (``output: {"type": "apng", "bits": 8 | 16, "alpha": bool, "filter": "paeth" | "adaptive", "loop":
     0..65535}``, ``--codec apng``): lossless, 8 or 16 bits a sample, and a PNG reader that knows no animation shows frame 0.
     Every frame leaves the GPU as its finished chunks — the device PNG's zlib stream as `IDAT`s for frame 0 and as `fdAT`s, sequence
@@ -562,21 +559,12 @@ class APNGOutput(DeviceEncodedOutput):
     _ACTL = 8 + 25                          # where `acTL` lies: behind the signature and IHDR
 
     def __init__(self, fps=24, alpha=False, bits=8, filter='paeth', loop=0):
-        if not fps > 0:
-            raise ValueError('apng needs fps above 0')
-        if fps > 90:                        # (webp's cap, taken over as a stated condition: DESIGN §4.17)
-            raise ValueError('apng: fps %g gives frames of 10 ms or less, which players show for 100 ms: use 90 or less' % fps)
+        self._need_fps('apng', fps, 90, '10 ms or less, which players show for 100 ms')      # (webp's cap, taken over as a stated condition: DESIGN §4.17)
         self.delay = apng_delay(fps)
-        if not isinstance(alpha, bool):
-            raise ValueError('output.alpha must be true or false')
-        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
-            raise ValueError('output.bits must be 8 or 16')
-        if not isinstance(filter, str) or filter not in _lib.PNG_FILTERS:
-            raise ValueError('output.filter must be "paeth" or "adaptive", not "%s"' % (filter,))
-        if isinstance(loop, bool) or not isinstance(loop, int) or not 0 <= loop <= 65535:
-            raise ValueError('output.loop must be an integer in 0..65535')
-        self.fps, self.alpha, self.channels, self.bits, self.filter, self.loop = fps, alpha, 4 if alpha else 3, bits, filter, loop
-        self._file, self._nframes, self.framesize = None, 0, None
+        self.fps, self.alpha, self.bits = fps, _bool('alpha', alpha), _bits(bits)
+        self.filter = _one_of('filter', filter, _lib.PNG_FILTERS, '"paeth" or "adaptive"')
+        self.loop, self.channels = _int_in('loop', loop, 0, 65535), 4 if alpha else 3
+        self._reset()
         self._queued = collections.deque()      # (w, h, chunks a frame, first number) of the frames numbered and not yet encoded
         self._qsize, self._qframes = None, 0    # the size and count of the frames numbered for the file being queued
 
@@ -624,25 +612,11 @@ class APNGOutput(DeviceEncodedOutput):
         return h_out
 
     def abort(self):
-        if self._file is not None:
-            self._file.close()
-        self._file, self._nframes, self.framesize = None, 0, None
+        _FrameFile.abort(self)
         self._queued.clear()
         self._qsize, self._qframes = None, 0
 
-    def _flush(self):
-        if self._file is None:
-            return {}, []
-        f = self._file
-        f.write(_png_chunk(b'IEND', b''))
-        f.seek(self._ACTL)
-        f.write(_png_chunk(b'acTL', struct.pack('>II', self._nframes, self.loop)))
-        f.seek(0)
-        self._file, self._nframes, self.framesize = None, 0, None
-        return {'.apng': f}, []
-
     def encode(self, buf):
-        out = ({}, [])
         if buf is None:
             if self._queued:                    # frames numbered for this file that never arrived
                 self.abort()
@@ -653,29 +627,35 @@ class APNGOutput(DeviceEncodedOutput):
             raise IOError('an APNG frame block that was never numbered: number(w, h) comes before encode')
         w, h, n, _ = self._queued.popleft()
         try:
-            nchunks = int(np.frombuffer(buf[12:16], '<u4')[0])
-            data = self.file_bytes(buf, self.noun)
+            self._frame = (w, h, n, int(np.frombuffer(buf[12:16], '<u4')[0]))      # what _parse and _wrap go by: the last is the record's chunks
+            return _FrameFile.encode(self, buf)
         except Exception:
-            self.abort()                        # a frame is missing: the file cannot go on
+            self.abort()                        # a frame is missing: no file with a gap, what was written goes
             raise
-        if self.framesize != (h, w):            # the first frame of a size: a new file
-            out = self._flush()
-            self.framesize = (h, w)
+
+    def _parse(self, data):
+        w, h = self._frame[:2]                  # (the block does not say: the frame was numbered with its size)
+        return h, w
+
+    def _header(self):
+        h, w = self.framesize
+        return (b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, self.bits, 6 if self.alpha else 2, 0, 0, 0))
+                + _png_chunk(b'acTL', struct.pack('>II', 0, self.loop)))      # the frame count: patched at the flush
+
+    def _wrap(self, data):
+        w, h, n, nchunks = self._frame
         want = self.first_number(self._nframes, n)
         tag = b'IDAT' if want == _lib.APNG_IDAT else b'fdAT'
         head = bytes(data[4:8]) if want == _lib.APNG_IDAT else bytes(data[4:12])
         if nchunks != n or len(data) < 12 or head != (tag if want == _lib.APNG_IDAT else tag + struct.pack('>I', want)):
-            what = ('frame %d of the APNG file needs a block of %d chunks that starts with %s%s; the block has %d and starts with %r'
-                    % (self._nframes, n, tag.decode(), '' if want == _lib.APNG_IDAT else ' %d' % want, nchunks, head))
-            self.abort()                        # no file with a gap: what was written goes
-            raise IOError(what)
-        if self._file is None:
-            self._file = tempfile.TemporaryFile()
-            self._file.write(b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, self.bits, 6 if self.alpha else 2, 0, 0, 0)))
-            self._file.write(_png_chunk(b'acTL', struct.pack('>II', 0, self.loop)))      # the frame count: patched at the flush
+            raise IOError('frame %d of the APNG file needs a block of %d chunks that starts with %s%s; the block has %d and starts with %r'
+                          % (self._nframes, n, tag.decode(), '' if want == _lib.APNG_IDAT else ' %d' % want, nchunks, head))
         fctl = 0 if self._nframes == 0 else want - 1
-        self._file.write(_png_chunk(b'fcTL', struct.pack('>IIIIIHHBB', fctl, w, h, 0, 0, self.delay[0], self.delay[1], 0, 0)))
-        # the pinned frame buffer is reused by the next frame: the bytes are copied out here
-        self._file.write(memoryview(np.ascontiguousarray(data)))
-        self._nframes += 1
-        return out
+        return _png_chunk(b'fcTL', struct.pack('>IIIIIHHBB', fctl, w, h, 0, 0, self.delay[0], self.delay[1], 0, 0)), b''
+
+    def _finish(self):
+        f = self._file
+        f.write(_png_chunk(b'IEND', b''))
+        f.seek(self._ACTL)
+        f.write(_png_chunk(b'acTL', struct.pack('>II', self._nframes, self.loop)))
+        return f

@@ -13,6 +13,30 @@ import numpy as np
 from . import _lib
 
 
+def _bool(key, v):
+    if not isinstance(v, bool):
+        raise ValueError('output.%s must be true or false' % key)
+    return v
+
+
+def _int_in(key, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError('output.%s must be an integer in %d..%d' % (key, lo, hi))
+    return v
+
+
+def _one_of(key, v, table, wording):
+    if not isinstance(v, str) or v not in table:
+        raise ValueError('output.%s must be %s, not "%s"' % (key, wording, v))
+    return v
+
+
+def _bits(v, name='output.bits'):
+    if isinstance(v, bool) or not isinstance(v, int) or v not in (8, 16):
+        raise ValueError('%s must be 8 or 16' % name)
+    return v
+
+
 class Output(object):
     fmt = 0
     dtype = 'u1'
@@ -175,13 +199,9 @@ class DeviceJPEGOutput(DeviceEncodedOutput):
     def __init__(self, quality=100, alpha=False, sampling='444', optimize=False):
         if alpha:
             raise ValueError('the device JPEG encoder has no alpha plane: use "device": false with "alpha"')
-        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-            raise ValueError('output.quality must be an integer in 1..100')
-        if str(sampling) not in _lib.JPEG_SAMPLING:
-            raise ValueError('output.sampling must be "444" or "420", not "%s"' % (sampling,))
-        if not isinstance(optimize, bool):
-            raise ValueError('output.optimize must be true or false')
-        self.quality, self.alpha, self.sampling, self.optimize = quality, False, str(sampling), optimize
+        self.quality, self.alpha = _int_in('quality', quality, 1, 100), False
+        self.sampling = _one_of('sampling', str(sampling), _lib.JPEG_SAMPLING, '"444" or "420"')
+        self.optimize = _bool('optimize', optimize)
         if optimize:
             self.entry = 'fl_output_jpeg_f'
         elif self.sampling != '444':            # (4:4:4 stays on the entry point it has always used)
@@ -211,13 +231,9 @@ class DevicePNGOutput(DeviceEncodedOutput):
     suffix, entry, noun = '.png', 'fl_output_png', 'PNG file'
 
     def __init__(self, alpha=False, bits=8, filter='paeth'):
-        if not isinstance(alpha, bool):
-            raise ValueError('output.alpha must be true or false')
-        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
-            raise ValueError('output.bits must be 8 or 16')
-        if not isinstance(filter, str) or filter not in _lib.PNG_FILTERS:
-            raise ValueError('output.filter must be "paeth" or "adaptive", not "%s"' % (filter,))
-        self.alpha, self.channels, self.bits, self.filter = alpha, 4 if alpha else 3, bits, filter
+        self.alpha, self.bits = _bool('alpha', alpha), _bits(bits)
+        self.filter = _one_of('filter', filter, _lib.PNG_FILTERS, '"paeth" or "adaptive"')
+        self.channels = 4 if alpha else 3
         self.extended = bits != 8 or filter != 'paeth'          # (the defaults stay on the entry points they have always used)
         if self.extended:
             self.entry = 'fl_output_png_f'
@@ -270,11 +286,8 @@ class DeviceTIFFOutput(DeviceEncodedOutput):
     suffix, entry, noun = '.tiff', 'fl_output_tiff', 'TIFF file'
 
     def __init__(self, alpha=False, bits=16):
-        if not isinstance(alpha, bool):
-            raise ValueError('output.alpha must be true or false')
-        if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 16):
-            raise ValueError('bits must be 8 or 16')
-        self.alpha, self.channels, self.bits = alpha, 4 if alpha else 3, bits
+        self.alpha, self.bits = _bool('alpha', alpha), _bits(bits, 'bits')
+        self.channels = 4 if alpha else 3
 
     def arguments(self):
         return (self.channels, self.bits)
@@ -291,11 +304,8 @@ class DeviceEXROutput(DeviceEncodedOutput):
     suffix, entry, noun = '.exr', 'fl_output_exr', 'OpenEXR file'
 
     def __init__(self, alpha=False, pixel='half'):
-        if not isinstance(alpha, bool):
-            raise ValueError('output.alpha must be true or false')
-        if not isinstance(pixel, str) or pixel not in _lib.EXR_PIXELS:
-            raise ValueError('output.pixel must be "half" or "float", not "%s"' % (pixel,))
-        self.alpha, self.channels, self.pixel = alpha, 4 if alpha else 3, pixel
+        self.alpha, self.pixel = _bool('alpha', alpha), _one_of('pixel', pixel, _lib.EXR_PIXELS, '"half" or "float"')
+        self.channels = 4 if alpha else 3
 
     def arguments(self):
         return (self.channels, _lib.EXR_PIXELS[self.pixel])
@@ -326,33 +336,42 @@ def get_suffix(codec, alpha=False):
     return ('_color' + ext) if alpha else ext
 
 
+# The outputs the device alone writes: their class (where it lives in encoders.py, by name: that module imports this one), the
+# keys their ``output`` block may hold in the order the refusal names them, and what the refusal calls them.
+_DEVICE_OUTPUTS = {
+    'exr': (DeviceEXROutput, ('pixel', 'alpha'), 'the device OpenEXR encoder'),
+    'gif': ('GIFOutput', ('colors', 'dither', 'loop'), 'the device GIF encoder'),
+    'webp': ('WebPOutput', ('alpha', 'loop'), 'the device WebP encoder'),
+    'apng': ('APNGOutput', ('alpha', 'bits', 'filter', 'loop'), 'the device APNG encoder'),
+    'png': (DevicePNGOutput, ('alpha', 'bits', 'filter'), 'the device PNG encoder'),
+    'tiff': (DeviceTIFFOutput, ('alpha',), 'output.compression: the device TIFF encoder'),
+}
+
+
+def _device_output(kind, opts, **more):
+    """The device's output of this kind from the keys left in ``opts``; no key of another encoder means anything to it."""
+    cls, keys, who = _DEVICE_OUTPUTS[kind]
+    extra = sorted(set(opts) - set(keys))
+    if extra:
+        quoted = ['"%s"' % k for k in keys]
+        takes = quoted[0] if len(keys) == 1 else ', '.join(quoted[:-1]) + ' and ' + quoted[-1]
+        raise ValueError('%s takes %s only, not %s' % (who, takes, ', '.join(extra)))
+    if isinstance(cls, str):
+        from . import encoders
+        cls = getattr(encoders, cls)
+    return cls(**dict(opts, **more))
+
+
 def get_output_for_profile(gprof):
     """Output module for the profile's ``output`` block (cuburn/output.py:421-436)."""
     opts = dict(gprof.output.raw())
     handler = opts.pop('type', 'jpeg')
-    if handler == 'exr':                                 # the device's file and nothing else: no key of another encoder means anything here
-        if set(opts) - {'alpha', 'pixel'}:
-            raise ValueError('the device OpenEXR encoder takes "pixel" and "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha', 'pixel'})))
-        return DeviceEXROutput(**opts)
+    if handler == 'exr':
+        return _device_output('exr', opts)
     if 'pixel' in opts:
         raise ValueError('output.pixel: only exr takes it, not "%s"' % handler)
-    if handler == 'gif':                                 # a format of its own: no key of another encoder means anything here
-        if set(opts) - {'colors', 'dither', 'loop'}:
-            raise ValueError('the device GIF encoder takes "colors", "dither" and "loop" only, not %s'
-                             % ', '.join(sorted(set(opts) - {'colors', 'dither', 'loop'})))
-        from . import encoders
-        return encoders.GIFOutput(fps=gprof.fps, **opts)
-    if handler == 'webp':                                # lossless, on the device only: no key of another encoder means anything here
-        if set(opts) - {'alpha', 'loop'}:
-            raise ValueError('the device WebP encoder takes "alpha" and "loop" only, not %s' % ', '.join(sorted(set(opts) - {'alpha', 'loop'})))
-        from . import encoders
-        return encoders.WebPOutput(fps=gprof.fps, **opts)
-    if handler == 'apng':                                # lossless, on the device only: no key of another encoder means anything here
-        if set(opts) - {'alpha', 'bits', 'filter', 'loop'}:
-            raise ValueError('the device APNG encoder takes "alpha", "bits", "filter" and "loop" only, not %s'
-                             % ', '.join(sorted(set(opts) - {'alpha', 'bits', 'filter', 'loop'})))
-        from . import encoders
-        return encoders.APNGOutput(fps=gprof.fps, **opts)
+    if handler in ('gif', 'webp', 'apng'):               # formats of their own, on the device only
+        return _device_output(handler, opts, fps=gprof.fps)
     for key in ('colors', 'dither', 'loop'):
         if key in opts:
             raise ValueError('output.%s: only gif%s, not "%s"' % (key, ', webp and apng take it' if key == 'loop' else ' takes it', handler))
@@ -364,8 +383,7 @@ def get_output_for_profile(gprof):
     if compression is not None:
         if handler != 'tiff':
             raise ValueError('output.compression: only tiff takes it, not "%s"' % handler)
-        if not isinstance(compression, str) or compression not in ('none', 'deflate'):
-            raise ValueError('output.compression must be "none" or "deflate", not "%s"' % (compression,))
+        _one_of('compression', compression, ('none', 'deflate'), '"none" or "deflate"')
     if opts.pop('device', False):
         if handler != 'jpeg':
             raise ValueError('output.device: only jpeg is encoded on the device, not "%s"' % handler)
@@ -376,10 +394,7 @@ def get_output_for_profile(gprof):
             raise ValueError('output.encoder: "device" is the only encoder to choose, not "%s"' % (encoder,))
         if handler != 'png':
             raise ValueError('output.encoder: selects the device PNG encoder ("device": true is the JPEG switch), not "%s"' % handler)
-        if set(opts) - {'alpha', 'bits', 'filter'}:
-            raise ValueError('the device PNG encoder takes "alpha", "bits" and "filter" only, not %s'
-                             % ', '.join(sorted(set(opts) - {'alpha', 'bits', 'filter'})))
-        return DevicePNGOutput(**opts)
+        return _device_output('png', opts)
     if 'optimize' in opts and handler != 'mjpeg':
         raise ValueError('output.optimize: only the device JPEG encoder optimises its Huffman tables: '
                          'set "device": true on a jpeg output, or use mjpeg')
@@ -387,9 +402,7 @@ def get_output_for_profile(gprof):
         return PILOutput(codec=handler, **opts)
     if handler == 'tiff':
         if compression == 'deflate':                     # the device's file; "none", or no key: the host writer, as before
-            if set(opts) - {'alpha'}:
-                raise ValueError('output.compression: the device TIFF encoder takes "alpha" only, not %s' % ', '.join(sorted(set(opts) - {'alpha'})))
-            return DeviceTIFFOutput(**opts)
+            return _device_output('tiff', opts)
         return TiffOutput(**opts)
     if handler == 'raw':
         return RawOutput()

@@ -703,6 +703,9 @@ enum {
     FL_MATH_COUNT
 };
 int fl_debug_math(fl_ctx *ctx, int fn, uint32_t n, const float *a, const float *b, uint32_t *out_bits);
+/* The encoders' placement helper in a kernel of its own (one workgroup): offs_out[i] = front + lens[0] + .. + lens[i - 1] for the
+ * n >= 1 pieces, *total_out = the sum of all lens (without front), in 64 bits.  Host pointers; synchronous. */
+int fl_debug_place(fl_ctx *ctx, const uint32_t *lens, uint32_t n, uint64_t front, uint64_t *offs_out, uint64_t *total_out);
 /* Compile (only) the iterate kernel specialised for a genome structure, as fl_iterate does on a genome's
  * first launch — the counterpart of cuburn/render.py:232-236 Renderer.compile.  Needs libhiprtc but no
  * GPU; FL_E_UNSUPPORTED if hipRTC is not installed.  nw = 4 | 8 | 16, acc = 0 (atomic), 1 / 3 (binned narrow / wide);

@@ -1,6 +1,7 @@
 """
-What the GPU tests of the device encoders share (test_gpu_jpeg.py, test_gpu_png.py, test_gpu_encoders_shared.py): destinations
-pre-filled with a sentinel, the call of fl_jpeg_encode / fl_png_encode, and the 16-byte record in front of the file.
+What the GPU tests of the device encoders share (test_gpu_jpeg.py, test_gpu_jpeg_opt.py, test_gpu_mjpeg.py, test_gpu_png.py,
+test_gpu_png_ext.py, test_gpu_tiff.py, test_gpu_exr.py, test_gpu_gif.py, test_gpu_webp.py, test_gpu_encoders_shared.py):
+destinations pre-filled with a sentinel, the call of an encoder's fl_X_encode, and the 16-byte record in front of the file.
 """
 import numpy as np
 
