@@ -829,8 +829,9 @@ static void launch_de_dir_one(hipStream_t st, fl_dim d, float4 *Nout, const floa
 // in_mode (pattern 0 only; ignored by the others): 1 = N is the raw accumulator, 2 = the raw YUV accumulator (yuv -> rgb first) — the first
 // direction always normalises as it stages; anything else is refused (a "0 = already normalised" form existed until round 5: a caller
 // that still relied on it would get a second normalisation).  tail (pattern 7 only, may be null): un-normalise + the tone filters riding along.
+// order_override (fl_debug_de_dir): 0 / 1 / 2 forces the tile order for this launch, before FLAME_DE_ORDER and the table; -1 = none.
 void launch_de_dir(hipStream_t st, fl_dim d, int pattern, float4 *Nout, const float4 *N, const float *coefs7,
-                   float sstd, float cstd, float dstd, float dpow, float gspeed, int in_mode, const DeTail *tail)
+                   float sstd, float cstd, float dstd, float dpow, float gspeed, int in_mode, const DeTail *tail, int order_override)
 {
     DeCoefs kc;
     for (int i = 0; i < 7; ++i) kc.k[i] = coefs7[i];
@@ -861,7 +862,7 @@ void launch_de_dir(hipStream_t st, fl_dim d, int pattern, float4 *Nout, const fl
     const int forced = !forced_s || !*forced_s ? -1 : (strlen(forced_s) == 8 ? forced_s[pattern] - '0' : forced_s[0] - '0');
     const bool beyond_mall = (size_t)d.astride * d.ah * 16u > ((size_t)256 << 20);
     const int table = (pattern == 1) ? 0 : (pattern == 5 || pattern == 7) ? (beyond_mall ? 2 : 0) : 2;
-    const int order = forced >= 0 && forced <= 2 ? forced : table;
+    const int order = order_override >= 0 && order_override <= 2 ? order_override : forced >= 0 && forced <= 2 ? forced : table;
     none.order = order;
     DeTail tl = tail ? *tail : none;
     tl.order = order;

@@ -1796,6 +1796,31 @@ int fl_debug_place(fl_ctx *c, const uint32_t *lens, uint32_t n, uint64_t front, 
     return FL_OK;
 }
 
+int fl_debug_de_dir(fl_ctx *c, uint32_t w, uint32_t h, int pattern, const float *scalars, int in_mode, int order)
+{
+    REQUIRE(c && scalars, "null argument");
+    REQUIRE(pattern >= 0 && pattern <= 7, "de direction must be 0..7");
+    REQUIRE(order >= -1 && order <= 2, "tile order must be -1 (the table's) or 0..2");
+    REQUIRE(pattern != 0 || in_mode == 1 || in_mode == 2, "direction 0 reads the raw accumulator: in_mode 1, or 2 (YUV)");
+    REQUIRE(w && h, "empty frame");
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim d;
+    int rc = ensure_fb(ln, w, h, &d);
+    if (rc) return rc;
+    if ((rc = flush_pending(c, ln))) return rc;
+    float k7[7];
+    gauss7(1.0f, k7);                                       // fl_filter's (FL_FILT_BILATERAL)
+    // a pixel the kernel does not write stays NaN (all bits set)
+    HIPCHK(hipMemsetAsync(ln.d_back, 0xff, 16 * (size_t)d.ah * d.astride, ln.stream));
+    const DeTail none = {};                                 // direction 7: un-normalise, no tone filter riding along
+    launch_de_dir(ln.stream, d, pattern, ln.d_back, ln.d_front, k7, scalars[0], scalars[1], scalars[2], scalars[3], scalars[4],
+                  in_mode, pattern == 7 ? &none : nullptr, order);
+    swap(ln.d_front, ln.d_back);
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
 int fl_rtc_compile_check(const int32_t *prog, uint32_t nprog, const int32_t *ops, uint32_t nops, int nw, int count, int acc,
                          char *log, size_t log_bytes)
 {

@@ -706,6 +706,16 @@ int fl_debug_math(fl_ctx *ctx, int fn, uint32_t n, const float *a, const float *
 /* The encoders' placement helper in a kernel of its own (one workgroup): offs_out[i] = front + lens[0] + .. + lens[i - 1] for the
  * n >= 1 pieces, *total_out = the sum of all lens (without front), in 64 bits.  Host pointers; synchronous. */
 int fl_debug_place(fl_ctx *ctx, const uint32_t *lens, uint32_t n, uint64_t front, uint64_t *offs_out, uint64_t *total_out);
+/* Bilateral DE tap: ONE direction (pattern 0..7, csrc/de.hip) of the eight FL_FILT_BILATERAL chains, on the lane's buffers, in the
+ * instantiation the chain itself uses — the front buffer is the input, the result ends in the front buffer (a deferred `yuv` or
+ * chain runs first).  Pattern 0 reads the raw accumulator (in_mode 1) or the raw YUV accumulator (in_mode 2) and writes the
+ * normalised image (x / w, y / w, z / w, w); patterns 1..6 read and write the normalised image; pattern 7 reads it and writes raw
+ * pixels (no tone filter rides along).  in_mode is ignored for patterns 1..7.  scalars = sstd, cstd, dstd, dpow, gspeed as
+ * fl_filter takes them; the blur coefficients are fl_filter's.  order: -1 = the tile order the launch would take by itself
+ * (FLAME_DE_ORDER, else the per-direction table), 0 / 1 / 2 = that order.  The destination is filled with NaN (all bits set)
+ * before the launch: a pixel of the padded frame that the kernel does not write shows.  FL_E_INVAL, with nothing queued: a
+ * pattern outside 0..7, an order outside -1..2, pattern 0 with an in_mode other than 1 or 2, an empty frame, null pointers. */
+int fl_debug_de_dir(fl_ctx *ctx, uint32_t w, uint32_t h, int pattern, const float scalars[5], int in_mode, int order);
 /* Compile (only) the iterate kernel specialised for a genome structure, as fl_iterate does on a genome's
  * first launch — the counterpart of cuburn/render.py:232-236 Renderer.compile.  Needs libhiprtc but no
  * GPU; FL_E_UNSUPPORTED if hipRTC is not installed.  nw = 4 | 8 | 16, acc = 0 (atomic), 1 / 3 (binned narrow / wide);
