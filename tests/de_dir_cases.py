@@ -13,7 +13,7 @@ import numpy as np
 
 from common import O
 import de_dir_model as M
-from test_gpu_parity import synth_accum, sparse_accum
+from accum_inputs import synth_accum, sparse_accum
 
 # ---------------------------------------------------------------------------------------------- geometry (csrc/de.hip)
 K = (0, 0, 2, -2, 4, -1, -4, 1)                    # x step per two rows of a sheared tile

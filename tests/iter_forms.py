@@ -11,7 +11,7 @@ thresholds; this module is its executable statement:
     interpreter kernel) bit for bit.
 
 Oracle rows use `linear` and `bent` only (no transcendentals: the device model is exact), unequal weights, distinct colours and
-colour speeds, and post affines / final xforms that are not the identity.  They start from test_gpu_edges.nxf_flame's ring.
+colour speeds, and post affines / final xforms that are not the identity.  They start from flames.nxf_flame's ring.
 """
 import copy
 import itertools
@@ -19,8 +19,8 @@ import itertools
 import numpy as np
 
 from cuburn_amd import configs
-from test_gpu_edges import nxf_flame
-from test_gpu_parity import run_device_model, setup_frame
+from flames import nxf_flame
+from gpu_harness import run_device_model, setup_frame
 
 BUDGETS = (12, 7, 5, 0)         # FL_HOIST_BUDGET: the default, and what rtc_iter_kernel falls back to past the register limit
 MERGE_MAX_XF = 4                # FL_ITER_MERGE_MAX_XF

@@ -394,3 +394,38 @@ def test_documents_name_only_tools_that_exist():
     # (a micro-benchmark built in place, `atomic_bench` next to `atomic_bench.hip`, is its source's product)
     files = set(f for f in have if f != 'README.md' and not ('.' not in f and (f + '.hip' in have or f + '.c' in have)))
     assert not files - rows, sorted(files - rows)
+
+
+HELPER_MODULES = ('flames', 'accum_inputs', 'gpu_harness', 'encoder_harness')
+TOOLS_ON_HELPERS = ('soak_filters', 'soak_filters2', 'soak_slots', 'soak_interp', 'soak_packed_log', 'soak_random_genomes', 'diag_accum',
+                    'diag_binned', 'diag_chain_error', 'diag_de_cancel', 'diag_de_cancel2', 'diag_point_filters', 'diag_random_seed',
+                    'iter_codegen_digest')
+
+
+def test_nothing_imports_a_test_module():
+    """Helpers live in harness modules (tests/flames.py, accum_inputs.py, gpu_harness.py, encoder_harness.py, ...): no file under
+    tests/ or tools/ imports a test module — the raw text is searched, so a child script kept in a string counts — and whatever
+    a tool takes from a helper module is there."""
+    import ast
+    import importlib
+    rule = re.compile(r'^\s*(from|import)\s+test_\w+', re.M)
+    paths = [os.path.join(REPO, d, f) for d in ('tests', 'tools') for f in sorted(os.listdir(os.path.join(REPO, d))) if f.endswith('.py')]
+    found = ['%s: %s' % (os.path.relpath(p, REPO), m.group(0).strip()) for p in paths for m in rule.finditer(open(p, errors='replace').read())]
+    assert not found, '\n'.join(found)
+    assert len(paths) > 150, len(paths)                                  # the scan found its subjects
+    missing = []
+    for tool in TOOLS_ON_HELPERS:
+        tree = ast.parse(open(os.path.join(REPO, 'tools', tool + '.py')).read())
+        alias = {}
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                alias.update((a.asname or a.name, a.name) for a in node.names if a.name in HELPER_MODULES)
+            elif isinstance(node, ast.ImportFrom) and node.module in HELPER_MODULES:
+                missing += ['%s: %s.%s' % (tool, node.module, a.name) for a in node.names
+                            if not hasattr(importlib.import_module(node.module), a.name)]
+        assert alias or any(isinstance(n, ast.ImportFrom) and n.module in HELPER_MODULES for n in ast.walk(tree)), tool
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in alias:
+                if not hasattr(importlib.import_module(alias[node.value.id]), node.attr):
+                    missing.append('%s: %s.%s' % (tool, alias[node.value.id], node.attr))
+    assert not missing, '\n'.join(missing)

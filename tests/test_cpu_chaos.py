@@ -18,13 +18,10 @@ from cuburn_amd import _lib, configs, profile, render
 from cuburn_amd.genome import blend, store
 from cuburn_amd.packer import GenomePacker, OP_CDF, OP_CHAOS_CDF, PROG_MAGIC
 import chaos_model as X
-from test_cpu_opacity import pack_digest, _compile, _resources
+from flames import FRACTIONAL, FORBIDDEN, CYCLE, many_xforms, rich_xml
+from gpu_harness import pack_digest, compile_check as _compile, kernel_resources as _resources
 
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
-FRACTIONAL = [[1.0, 0.5, 2.0], [0.25, 1.0, 1.0], [1.0, 3.0, 0.5]]
-FORBIDDEN = [[0.5, 1.0, 0.0], [1.0, 1.0, 2.0], [1.0, 0.0, 1.0]]          # 0 -> 2 and 2 -> 1 never happen; lambda = 0.31
-ZERO_DIAGONAL = [[0.0, 1.0, 1.0], [1.0, 0.0, 0.5], [2.0, 1.0, 0.0]]      # no xform follows itself (lambda = 0.81: exact tests only)
-CYCLE = [[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]]              # 0 -> 1 -> 2 -> 0
 
 
 def const_inputs(table, weights=X.WEIGHTS):
@@ -104,13 +101,6 @@ def test_one_entry_off_one_makes_a_chaos_genome():
 
 
 # ------------------------------------------------------------------ rejections and warnings
-def many_xforms(n, chaos):
-    gnm, prof = X.nine_boxes()
-    xf = gnm['xforms']['0']
-    gnm['xforms'] = dict(('%02d' % i, copy.deepcopy(xf)) for i in range(n))
-    if chaos:
-        gnm['xforms']['00']['chaos'] = {'01': 0.5}
-    return gnm, prof
 
 
 def test_renderer_rejects_33_xforms_with_chaos_only():
@@ -148,10 +138,6 @@ def test_renderer_warns_about_unknown_targets_and_final_chaos():
 
 
 # ------------------------------------------------------------------ front end
-def rich_xml():
-    src = json.load(open(os.path.join(GOLD, 'genome_front.json')))['xml']['rich']
-    assert src.count(' chaos="1 0.5 2"') == 1
-    return src
 
 
 def test_flam3_file_with_chaos_becomes_an_animation_that_carries_the_table(tmp_path):

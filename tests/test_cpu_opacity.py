@@ -3,14 +3,13 @@ Xform opacity on the host side (no GPU): what the packer emits for the `opacity`
 FL_OP_OPACITY in float32, and the per-genome iterate kernels of genomes with an opacity (hipRTC compiles without a
 device).  The contract is include/flame_hip.h (5) words 14 / 15 and (6) FL_OP_OPACITY; DESIGN.md §4.1.
 
-Also home of the "three boxes" test flame that tests/test_gpu_opacity.py renders.
+The "three boxes" test flame that tests/test_gpu_opacity.py renders too is in tests/flames.py.
 """
 import copy
 import ctypes as C
 import json
 import os
 import re
-import subprocess
 import warnings
 
 import numpy as np
@@ -18,46 +17,10 @@ import pytest
 
 from cuburn_amd import _lib, configs, profile, render
 from cuburn_amd.packer import GenomePacker, OP_CONST, OP_OPACITY, OP_SPLINE_MAG
+from flames import three_boxes, with_opacity, plot_probability
+from gpu_harness import pack_digest, compile_check as _compile, kernel_resources as _resources
 
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
-BOX_OFFSETS = ((-0.45, -0.3), (0.45, -0.3), (0.0, 0.42))
-BOX_WEIGHTS = (0.5, 0.3, 0.2)
-# Pixel rectangles (rows, columns; inclusive) of the padded accumulator (272 rows of 352, 344 columns in use) that hold the three disjoint images of the
-# attractor's hull, found with the CPU oracle at 2^24 samples: the box of xform `2`, and the two lower boxes (which of them
-# is xform `0` follows from the camera's sign conventions; the GPU test reads it off the keyless render's masses).
-BOX_TOP = (80, 118, 148, 196)
-BOX_LOW_LEFT = (138, 176, 112, 160)
-BOX_LOW_RIGHT = (138, 176, 184, 232)
-
-
-def three_boxes(opacity=None, samples=2 ** 26):
-    """Three linear xforms whose images are disjoint: a plotted sample lies in box k exactly when xform k produced it, so
-    without opacity box k holds the fraction w_k of what is plotted, and with opacities q_k w_k / sum_j q_j w_j.
-    ``opacity``: None (no key anywhere) or one value per xform (None: no key on that xform)."""
-    xforms = {}
-    for k, ((ox, oy), w) in enumerate(zip(BOX_OFFSETS, BOX_WEIGHTS)):
-        xforms[str(k)] = {'weight': w, 'color': 0.5 * k, 'color_speed': 0.5,
-                          'pre_affine': configs._affine(0, 0.4, ox, oy), 'variations': {'linear': {'weight': 1.0}}}
-        if opacity is not None and opacity[k] is not None:
-            xforms[str(k)]['opacity'] = opacity[k]
-    gnm = {'type': 'animation', 'name': 'three-boxes',
-           'camera': {'center': {'x': 0.0, 'y': 0.0}, 'rotation': 0.0, 'scale': 0.25},
-           'time': {'duration': 1, 'frame_width': 0.0},
-           'palette': [configs._pal(0.0, configs.grey_ramp())], 'xforms': xforms}
-    prof = {'width': 320, 'height': 240, 'spp': samples / (320.0 * 240.0), 'fps': 1, 'duration': 1, 'frame_width': 0,
-            'output': {'type': 'raw'}, 'filter_order': ['bilateral', 'logscale', 'colorclip']}
-    return gnm, prof
-
-
-def plot_probability(p):
-    """The contract's q(p) in float64."""
-    p = min(max(float(p), 0.0), 1.0)
-    if p <= 0.0:
-        return 0.0
-    if p >= float(np.float32(1) - np.float32(1e-6)):          # (the snap's threshold is the float32 number, 0.99999899)
-        return 1.0
-    q = 10.0 ** np.log2(p)
-    return 0.0 if q < 2.0 ** -32 else q
 
 
 def plot_probability_f32(p):
@@ -72,13 +35,6 @@ def plot_probability_f32(p):
     return f(0) if p <= f(0) else f(1) if p >= f(1) - f(1.0e-6) else q
 
 
-def with_opacity(gnm, keys, value=0.5):
-    gnm = copy.deepcopy(gnm)
-    for k in keys:
-        gnm['xforms'][k]['opacity'] = value
-    return gnm
-
-
 def _consts(pk):
     return dict((int(o[1]), int(o[2])) for o in pk.ops_array if o[0] == OP_CONST)
 
@@ -89,16 +45,6 @@ def _consts(pk):
 KEYLESS_PACKS = {'cfg1': 'cd519df5d228bc4f9d20826907b02a69', 'cfg2': 'a5b54a14e3b0f1eb3388fbf145f9fcee',
                  'cfg3': '64527c157a84760fa4cd02392cd84681', 'cfg5': '1dc894a6ef16badcbff93601eae748e0',
                  'allvars': 'a1b1251d2635c55c5fe8d21df77ec55c'}
-
-
-def pack_digest(pk):
-    import hashlib
-    h = hashlib.sha256()
-    h.update(np.ascontiguousarray(pk.prog, np.int32).tobytes())
-    h.update(np.ascontiguousarray(pk.ops_array, np.int32).tobytes())
-    h.update(json.dumps([['.'.join(p), bool(m)] for p, m in pk.rows]).encode())
-    h.update(json.dumps(['.'.join(p) for p in pk.packed]).encode())
-    return h.hexdigest()[:32]
 
 
 @pytest.mark.parametrize('cfg', ['cfg1', 'cfg2', 'cfg3', 'cfg5', 'allvars'])
@@ -215,28 +161,6 @@ def test_plot_probability_curve_float32():
 
 
 # ------------------------------------------------------------------ 2. / 3. the per-genome kernels
-def _compile(gnm, nw, count, acc):
-    pk = GenomePacker(gnm)
-    prog = np.ascontiguousarray(pk.prog, np.int32)
-    ops = np.ascontiguousarray(pk.ops_array, np.int32)
-    log = C.create_string_buffer(8192)
-    rc = _lib.load().fl_rtc_compile_check(prog.ctypes.data, len(prog), ops.ctypes.data, len(ops), nw, count, acc, log, len(log))
-    if rc == _lib.FL_E_UNSUPPORTED:
-        pytest.skip('libhiprtc is not installed')
-    return rc, log.value.decode()
-
-
-def _resources(tmp_path):
-    readelf = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-    if not os.path.exists(readelf):
-        pytest.skip('no llvm-readelf')
-    co = str(tmp_path / 'k_iter_spec.co')
-    notes = subprocess.run([readelf, '--notes', co], capture_output=True, text=True, timeout=60).stdout
-    num = lambda key: int(re.search(r'\.' + key + r':\s+(\d+)', notes).group(1))
-    sect = subprocess.run([readelf, '-S', co], capture_output=True, text=True, timeout=60).stdout
-    text = int(re.search(r'\.text\s+PROGBITS\s+\S+\s+\S+\s+([0-9a-f]+)', sect).group(1), 16)
-    return dict(vgpr=num('vgpr_count'), sgpr=num('sgpr_count'), spill=num('vgpr_spill_count'), sgpr_spill=num('sgpr_spill_count'),
-                scratch=num('private_segment_fixed_size'), lds=num('group_segment_fixed_size'), text=text)
 
 
 def _opacity_genomes():

@@ -21,56 +21,17 @@ from cuburn_amd import configs, profile, render, _lib
 from cuburn_amd.packer import GenomePacker, OP_CDF, OP_CHAOS_CDF
 import chaos_model as X
 import interp_model as M
-from test_cpu_chaos import FRACTIONAL, FORBIDDEN, ZERO_DIAGONAL, CYCLE, many_xforms, rich_xml
-from test_gpu_opacity import env, same_bits, setup_frame
-from test_gpu_fullsize import check_against_cpu_game
+from flames import FRACTIONAL, FORBIDDEN, ZERO_DIAGONAL, CYCLE, many_xforms, rich_xml, spread_flame
+from gpu_harness import env, same_bits, setup_frame, launch, snapshot, check_against_cpu_game
 
 pytestmark = pytest.mark.gpu
 FUSE = 256
 U = 2.0 ** -24
-SIZE = (256, 256)
 
 
 @pytest.fixture(scope='module')
 def mgr(built):
     return render.RenderManager(device=0, nslots=1024, host_seed=43)
-
-
-def launch(m, gnm, prof, mode, nrounds, fuse, seeds_in=None, points_in=None):
-    """One counted iterate launch from cleared buffers — and NaN points, or ``points_in`` — then the flush: everything the
-    launch left behind (walkers with their fourth word)."""
-    lib = _lib.load()
-    if seeds_in is not None:
-        m.fb.write('seeds', seeds_in)
-    seeds0 = m.fb.read('seeds', (m.fb.nwalkers, 3), np.uint32)
-    rdr, dim, g, ts, td = setup_frame(m, gnm, prof)
-    nbins = dim.ah * dim.astride
-    nwalk = m.fb.nslots * m.fb.nthreads
-    _lib.check(lib.fl_debug_clear(m.fb.ctx, dim.w, dim.h, 1 if points_in is None else 0))
-    if points_in is not None:
-        m.fb.write('points', points_in)
-    _lib.check(lib.fl_debug_iter_launch(m.fb.ctx, g, dim.w, dim.h, 0, nrounds + fuse, fuse, mode))
-    ctr = np.zeros(4, np.uint64)
-    _lib.check(lib.fl_debug_counters(m.fb.ctx, ctr.ctypes.data))
-    atom = m.fb.read('atom', (nbins,), np.uint64)
-    rng = m.fb.read('seeds', (m.fb.nwalkers, 3), np.uint32)[:nwalk]
-    pts = m.fb.read('points', (nwalk, 4), np.float32).view(np.uint32).copy()
-    params = m.fb.read('params', (1024, rdr.packer.pstride), np.float32, g)
-    _lib.check(lib.fl_debug_flush(m.fb.ctx, dim.w, dim.h))
-    front = m.fb.read('front', (nbins, 4), np.float32)
-    return dict(ctr=ctr, atom=atom, rng=rng, pts=pts, front=front, seeds0=seeds0, dim=(dim.ah, dim.astride),
-                samples=nrounds * nwalk, params=params, prog=rdr.packer.prog)
-
-
-def snapshot(gnm, prof, mode, nw=4, nslots=1024, nrounds=29, fuse=5, seeds_in=None, **switches):
-    """A launch in a context of its own geometry and switches."""
-    with env(FLAME_NW=None if nw == 4 else str(nw), **switches):
-        m = render.RenderManager(device=0, nslots=nslots, host_seed=44)
-        assert (m.fb.nw, m.fb.nslots) == (nw, nslots)
-        try:
-            return launch(m, gnm, prof, mode, nrounds, fuse, seeds_in)
-        finally:
-            m.fb.free()
 
 
 def density(r):
@@ -84,7 +45,7 @@ def rects_of(r):
 
 def frame(m, gnm, prof, nsamples, mode=_lib.ACCUM_BINNED):
     """A frame through fl_iterate; the flushed accumulator."""
-    rdr, dim, g, ts, td = setup_frame(m, gnm, prof)
+    rdr, gprof, dim, g, ts, td = setup_frame(m, gnm, prof)
     run = C.c_uint64()
     _lib.check(_lib.load().fl_iterate(m.fb.ctx, g, dim.w, dim.h, float(nsamples), FUSE, mode, C.byref(run)))
     assert run.value == nsamples
@@ -174,7 +135,7 @@ def test_interp_writes_the_chaos_matrix(mgr, case):
     if case == 'animated':
         gnm['time'] = {'duration': 1, 'frame_width': 1.0}
         prof = dict(prof, frame_width=1.0)
-    rdr, dim, g, ts, td = setup_frame(mgr, gnm, prof, 0.5)
+    rdr, gprof, dim, g, ts, td = setup_frame(mgr, gnm, prof, 0.5)
     assert (td > 0.9) == (case == 'animated')
     pk = rdr.packer
     n, co = int(pk.prog[1]), int(pk.prog[8])
@@ -224,7 +185,7 @@ def test_interp_writes_the_chaos_matrix(mgr, case):
     plain = copy.deepcopy(gnm)
     for xf in plain['xforms'].values():
         xf.pop('chaos', None)
-    rdr0, _, g0, _, _ = setup_frame(mgr, plain, prof, 0.5)
+    rdr0, _, _, g0, _, _ = setup_frame(mgr, plain, prof, 0.5)
     assert rdr0.packer.pstride == co and len(rdr0.packer.prog) == 8
     dev0 = mgr.fb.read('params', (1024, co), np.float32, g0)
     assert np.array_equal(dev0.view(np.uint32), dev[:, :co].view(np.uint32))
@@ -276,17 +237,6 @@ def test_cyclic_table_splits_the_samples_in_exact_thirds(mgr):
     assert [X.in_rect(d, rc).sum() for rc in first] == [N // 3] * 3
     for (p, n), rect in second.items():
         assert X.in_rect(d, rect).sum() == (N // 3 if n == (p + 1) % 3 else 0), (p, n)
-
-
-def spread_flame(table):
-    """cfg2 (linear, spherical, swirl) with a chaos table at 256 x 256, zoomed in: many lit cells below the drain threshold for
-    the atomic comparisons (the nine boxes' attractor is a dust of ~200 hot pixels), and samples out of frame."""
-    gnm, prof = configs.cfg2(samples=2 ** 22)
-    prof = dict(prof, width=SIZE[0], height=SIZE[1], spp=2 ** 22 / float(SIZE[0] * SIZE[1]))
-    gnm['camera']['scale'] = 0.5
-    for p, k in enumerate(sorted(gnm['xforms'])):
-        gnm['xforms'][k]['chaos'] = dict((str(n), v) for n, v in enumerate(table[p]))
-    return gnm, prof
 
 
 def _forms_agree(gnm, prof, what, min_lit=200):
@@ -407,7 +357,7 @@ def test_equal_rows_are_the_reweighted_keyless_genome(mgr):
     for k in chaos['xforms']:
         chaos['xforms'][k]['chaos'] = dict(col)
         plain['xforms'][k]['weight'] = gnm['xforms'][k]['weight'] * col[k]
-    rdr, dim, g, ts, td = setup_frame(mgr, chaos, prof)
+    rdr, gprof, dim, g, ts, td = setup_frame(mgr, chaos, prof)
     assert len(rdr.packer.prog) == 9
     run = C.c_uint64()
     _lib.check(_lib.load().fl_iterate(mgr.fb.ctx, g, dim.w, dim.h, float(2 ** 24), FUSE, _lib.ACCUM_BINNED, C.byref(run)))

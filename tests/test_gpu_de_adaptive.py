@@ -10,8 +10,9 @@ import pytest
 
 from common import frame_times
 from de_model import de_filter
-from test_gpu_parity import synth_accum
 from cuburn_amd import _lib, configs, profile, render
+from accum_inputs import fractional_band_accum as accum
+from gpu_harness import run_filter
 
 pytestmark = pytest.mark.gpu
 
@@ -26,35 +27,12 @@ def mgr(built):
     m.fb.free()
 
 
-def run_de(mgr, dim, buf, vals):
-    lib = _lib.load()
-    _lib.check(lib.fl_debug_clear(mgr.fb.ctx, dim.w, dim.h, 0))
-    mgr.fb.write('front', buf)
-    arr = np.asarray(vals, np.float32)
-    _lib.check(lib.fl_filter(mgr.fb.ctx, _lib.FILT['de'], dim.w, dim.h, arr.ctypes.data, len(arr)))
-    return mgr.fb.read('front', buf.shape, np.float32)
-
-
-def accum(dim, seed=1):
-    """The parity tests' accumulator (blobs + Poisson + an empty band), with a band of fractional densities, many
-    of them in (0, 1)."""
-    buf = synth_accum(dim, seed).reshape(dim.ah, dim.astride, 4)
-    r0 = dim.ah // 5                                        # rows above are empty
-    buf[r0:r0 + 24] *= np.float32(0.37)
-    rs = np.random.RandomState(seed)
-    buf[r0 - 6:r0 - 2, 20:120, 3] = rs.uniform(0.05, 0.95, (4, 100)).astype(np.float32)
-    buf[r0 - 6:r0 - 2, 20:120, :3] = buf[r0 - 6:r0 - 2, 20:120, 3:] * rs.uniform(0.2, 0.8, (4, 100, 3)).astype(np.float32)
-    w = buf[r0 - 8:r0 + 24, :, 3]
-    assert (w == 0).any() and ((w > 0) & (w < 1)).any() and (w % 1 != 0).any()
-    return buf
-
-
 @pytest.mark.parametrize('R,minimum,curve', [(11, 0, 0.6), (4.5, 0.5, 0.4), (23, 0.1, 1.0), (96, 0, 0.6)])
 def test_de_matches_model(mgr, R, minimum, curve):
     dim = mgr.fb.calc_dim(FW, FH)
     buf = accum(dim)
     vals = [np.float32(R), np.float32(minimum * R), np.float32(curve)]
-    dev = run_de(mgr, dim, buf.reshape(-1, 4), vals).reshape(buf.shape).astype(np.float64)
+    dev = run_filter(mgr, 'de', dim, buf.reshape(-1, 4), vals).reshape(buf.shape).astype(np.float64)
     ref = de_filter(buf, *vals)
     assert np.isfinite(dev).all()
     for ch in range(4):
@@ -68,7 +46,7 @@ def test_de_conserves_energy(mgr, R, minimum, curve):
     buf = accum(dim, seed=2)
     edge = int(np.ceil(R))
     buf[:edge] = 0; buf[-edge:] = 0; buf[:, :edge] = 0; buf[:, -edge:] = 0
-    dev = run_de(mgr, dim, buf.reshape(-1, 4), [R, minimum * R, curve]).reshape(buf.shape)
+    dev = run_filter(mgr, 'de', dim, buf.reshape(-1, 4), [R, minimum * R, curve]).reshape(buf.shape)
     assert not np.array_equal(dev, buf)
     s0, s1 = buf.astype(np.float64).sum((0, 1)), dev.astype(np.float64).sum((0, 1))
     assert np.allclose(s1, s0, rtol=1e-5, atol=0), (s0, s1)
@@ -78,18 +56,18 @@ def test_de_copies_when_nothing_spreads(mgr):
     dim = mgr.fb.calc_dim(FW, FH)
     buf = accum(dim, seed=3)
     flat = buf.reshape(-1, 4)
-    assert np.array_equal(run_de(mgr, dim, flat, [0.0, 0.0, 0.6]), flat)           # R <= 0
+    assert np.array_equal(run_filter(mgr, 'de', dim, flat, [0.0, 0.0, 0.6]), flat)           # R <= 0
     dense = buf.copy()
     dense[..., 3] += 300.0                                   # 11 * 300^-0.6 < 1: every h < 1
     flat = dense.reshape(-1, 4)
-    assert np.array_equal(run_de(mgr, dim, flat, [11.0, 0.0, 0.6]), flat)
+    assert np.array_equal(run_filter(mgr, 'de', dim, flat, [11.0, 0.0, 0.6]), flat)
 
 
 def test_de_deterministic(mgr):
     dim = mgr.fb.calc_dim(FW, FH)
     flat = accum(dim, seed=4).reshape(-1, 4)
-    a = run_de(mgr, dim, flat, [23.0, 0.0, 0.6])
-    b = run_de(mgr, dim, flat, [23.0, 0.0, 0.6])
+    a = run_filter(mgr, 'de', dim, flat, [23.0, 0.0, 0.6])
+    b = run_filter(mgr, 'de', dim, flat, [23.0, 0.0, 0.6])
     assert np.array_equal(a, b) and not np.array_equal(a, flat)
 
 
@@ -97,9 +75,9 @@ def test_de_rejects_bad_parameters(mgr):
     dim = mgr.fb.calc_dim(FW, FH)
     flat = accum(dim).reshape(-1, 4)
     with pytest.raises(ValueError, match='curve'):
-        run_de(mgr, dim, flat, [11.0, 0.0, 0.0])
+        run_filter(mgr, 'de', dim, flat, [11.0, 0.0, 0.0])
     with pytest.raises(ValueError, match='96'):
-        run_de(mgr, dim, flat, [97.0, 0.0, 0.6])
+        run_filter(mgr, 'de', dim, flat, [97.0, 0.0, 0.6])
 
 
 def render_small(order, seed):

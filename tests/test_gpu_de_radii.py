@@ -26,8 +26,7 @@ import pytest
 
 from common import O, frame_times
 from de_model import de_filter, de_gather_at, disc_weights, near_half_densities, radii16
-from test_gpu_de_adaptive import accum
-from test_gpu_parity import synth_accum
+from accum_inputs import fractional_band_accum as accum, synth_accum
 from cuburn_amd import _lib, configs, filters, profile, render
 
 pytestmark = pytest.mark.gpu

@@ -13,9 +13,11 @@ import pytest
 from common import O, prepare, frame_times
 from cuburn_amd import configs, profile, render, _lib
 from cuburn_amd.packer import GenomePacker
-from test_gpu_parity import run_device_model, NSLOTS            # noqa: E402
+from flames import nxf_flame
+from gpu_harness import run_device_model
 
 pytestmark = pytest.mark.gpu
+NSLOTS = 1024
 
 
 @pytest.fixture(scope='module')
@@ -23,19 +25,6 @@ def mgr():
     from __graft_entry__ import build
     build()
     return render.RenderManager(device=0, nslots=NSLOTS, host_seed=11)
-
-
-def nxf_flame(n, w=256, h=144):
-    """n linear xforms on a ring, unequal weights (the density table has n-1 entries)."""
-    gnm, prof = configs.cfg1()
-    xfs = {}
-    for i in range(n):
-        a = 2 * np.pi * i / max(n, 1)
-        xfs[str(i)] = {'weight': 0.2 + (i % 5) * 0.3, 'color': i / max(n - 1, 1), 'color_speed': 0.5,
-                       'pre_affine': configs._affine(7.0 * i, 0.45, 0.55 * float(np.cos(a)), 0.55 * float(np.sin(a))),
-                       'variations': {'linear': {'weight': 1.0}}}
-    gnm['xforms'] = xfs
-    return gnm, dict(prof, width=w, height=h)
 
 
 @pytest.mark.parametrize('n', [1, 2, 9, 33, 64])

@@ -13,7 +13,7 @@ import encoder_harness as H
 import jpeg_cases as JC
 import png_cases as PC
 import png_model as P
-from test_gpu_jpeg import assert_criteria as assert_jpeg_criteria
+from encoder_harness import assert_jpeg_criteria
 
 pytestmark = pytest.mark.gpu
 
@@ -42,8 +42,8 @@ def jpeg_png_jpeg(mgr, inputs, pinned, extra=None):
     planes, quality, tj, rgba, ch, tp = inputs
     jcap, pcap = lib.fl_jpeg_bound(64, 40), lib.fl_png_bound(256, 96, ch)
     make = (lambda cap: None) if pinned else (lambda cap: np.empty(cap + H.SLACK, np.uint8))
-    queue_jpeg = lambda: (H.queue(mgr, 'fl_jpeg_encode', tj, 64, 40, quality, jcap, make(jcap)), jcap)
-    queue_png = lambda cap=pcap: (H.queue(mgr, 'fl_png_encode', tp, 256, 96, ch, cap, make(cap)), cap)
+    queue_jpeg = lambda: (H.queue(mgr, 'fl_jpeg_encode', tj, 64, 40, (quality,), jcap, make(jcap)), jcap)
+    queue_png = lambda cap=pcap: (H.queue(mgr, 'fl_png_encode', tp, 256, 96, (ch,), cap, make(cap)), cap)
     done = [queue_jpeg(), queue_png(), queue_jpeg()]
     if extra:
         done.append(extra(queue_png))

@@ -37,14 +37,7 @@ def encode(mgr, src, ch, px, cap=None, buf=None, stride=None):
     if cap is None:
         cap = lib.fl_exr_bound(w, h, ch, px)
         assert cap
-    t = upload(mgr, np.ascontiguousarray(src).view(np.uint8))
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_exr_encode(mgr.fb.ctx, w, h, t.data_ptr(), sw, ch, px, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    H.assert_untouched(buf, cap)
-    return buf
+    return H.encode(mgr, 'fl_exr_encode', np.ascontiguousarray(src).view(np.uint8), w, h, (sw, ch, px), cap, buf)[0]
 
 
 def file_of(buf, ch):

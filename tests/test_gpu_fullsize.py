@@ -13,100 +13,15 @@ agrees with the oracle's chain — on the whole buffer at 1080p, on an interior 
 (the filters are local: a window plus a margin wider than 8 passes x 16 taps reproduces the
 interior exactly, and keeps the single-threaded CPU chain affordable).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from common import O, prepare, frame_times
-from cuburn_amd import configs, profile, render, _lib
+from common import O
+from cuburn_amd import configs, profile, render
+from gpu_harness import (iterate_frame, blocks, check_against_cpu_game, check_chain_error, filter_chain_on_device,
+                         oracle_chain)
 
 pytestmark = pytest.mark.gpu
-
-
-def iterate_frame(m, gnm, prof, tc, nsamples, geometry_by_samples=False):
-    lib = _lib.load()
-    gprof = profile.wrap(prof, gnm)
-    rdr = render.Renderer(gnm, gprof)
-    dim = m.fb.set_dim(gprof.width, gprof.height, nsamples=nsamples if geometry_by_samples else None)
-    g = rdr._handle(m.fb)
-    ts, td = frame_times(gprof, tc)
-    fid = C.c_uint32()
-    _lib.check(lib.fl_frame_begin(m.fb.ctx, C.byref(fid)))
-    m._copy(rdr, gnm)
-    _lib.check(lib.fl_interp(m.fb.ctx, g, dim.w, dim.h, ts, td))
-    run = C.c_uint64()
-    mode = m.resolve_accum_mode(dim)
-    assert mode == _lib.ACCUM_BINNED
-    _lib.check(lib.fl_iterate(m.fb.ctx, g, dim.w, dim.h, float(nsamples), m.fuse, mode, C.byref(run)))
-    front = m.fb.read('front', (dim.ah * dim.astride, 4), np.float32)
-    return rdr, gprof, dim, td, run.value, front
-
-
-def blocks(dens, bs):
-    H, W = dens.shape[0] // bs * bs, dens.shape[1] // bs * bs
-    return dens[:H, :W].reshape(H // bs, bs, W // bs, bs).sum((1, 3))
-
-
-def check_against_cpu_game(gnm, prof, tc, nslots, dim, front, nrun, ncpu, bs, l1_max, frac_tol, col_tol, nthreads=16):
-    dens = front[:, 3].reshape(dim.ah, dim.astride).astype(np.float64)
-    assert np.array_equal(dens, np.rint(dens)) and dens.min() >= 0, 'density must hold integer counts'
-    assert dens.sum() <= nrun
-    F = prepare(gnm, prof, tc, nslots=nslots)
-    ref, secs, acc = O.flam3_render(F['dim'], F['packer'].prog, F['params'], F['palette'], F['seeds'], ncpu, nthreads)    # one private float4 histogram per thread
-    dr = ref[:, 3].reshape(dim.ah, dim.astride).astype(np.float64)
-    fg, fr = dens.sum() / nrun, dr.sum() / ncpu
-    assert abs(fg - fr) < frac_tol, ('in-frame fraction', fg, fr)
-    bg, br = blocks(dens, bs), blocks(dr, bs)
-    l1 = np.abs(bg / bg.sum() - br / br.sum()).sum()
-    # shot noise of the smaller (CPU) sample alone contributes ~ sum_b sqrt(2 p_b / (pi n)) to the L1
-    p = br / br.sum()
-    noise = np.sqrt(2.0 * p / (np.pi * max(dr.sum(), 1.0))).sum()
-    assert l1 < l1_max + 1.5 * noise, ('block L1', l1, 'shot-noise floor', noise)
-    cg = front[:, :3].sum(0, dtype=np.float64) / dens.sum()
-    cr = ref[:, :3].sum(0, dtype=np.float64) / dr.sum()
-    assert np.abs(cg - cr).max() < col_tol, ('mean colour', cg, cr)
-    return l1, noise, fg, fr
-
-
-# Bars of the full-size filter chain (tone-mapped values in [0, 1]).  Measured (gpurun_out/fullsize_chain_errors.txt,
-# tools/diag_chain_error.py): cfg2 / cfg3 whole 1080p frames max 2.2e-5 / 2.3e-5, 99.9 % below 1.2e-6, mean 4e-8; the
-# 4K / 8K windows max 1.7e-6 / 6.4e-6.  The maximum sits at single-hit pixels at the rim of the flame, where
-# colorclip's linear segment below `gamma_threshold` multiplies differences by lin^(gamma - 1) = 31.6; above a DE
-# density of 10 the relative error of the DE output itself is 3e-6.  The bars are ~4x the worst measured values
-# (round 2 asked for max < 2e-2): hardware exp / log / rcp on one side, libm on the other.
-CHAIN_MAX, CHAIN_P999, CHAIN_MEAN = 1e-4, 5e-6, 5e-7
-
-
-def check_chain_error(err, what):
-    stats = (float(err.max()), float(np.percentile(err, 99.9)), float(err.mean()))
-    try:
-        import os
-        if os.path.isdir('gpurun_out'):
-            with open('gpurun_out/fullsize_chain_errors.txt', 'a') as fp:
-                fp.write('%s: max %.3e p99.9 %.3e mean %.3e\n' % ((what,) + stats))
-    except OSError:
-        pass
-    assert stats[0] < CHAIN_MAX and stats[1] < CHAIN_P999 and stats[2] < CHAIN_MEAN, (what,) + stats
-    return stats
-
-
-def filter_chain_on_device(m, rdr, gprof, dim, tc):
-    vals = {}
-    for filt in rdr.filts:
-        vals[filt.name] = [float(v) for v in filt.scalars(gprof, getattr(gprof.filters, filt.name), dim, tc)]
-        filt.apply(m.fb, gprof, getattr(gprof.filters, filt.name), dim, tc)
-    assert [f.name for f in rdr.filts] == ['yuv', 'bilateral', 'logscale', 'colorclip']
-    dev = m.fb.read('front', (dim.ah * dim.astride, 4), np.float32)
-    assert np.isfinite(dev).all()
-    return vals, dev
-
-
-def oracle_chain(d, buf, vals):
-    cur = O.yuv_to_rgb(d, np.ascontiguousarray(buf))
-    cur = O.bilateral_chain(d, cur, *vals['bilateral'])
-    cur = O.logscale(d, cur, *vals['logscale'])
-    return O.colorclip(d, cur, *vals['colorclip'])
 
 
 def check_window(dim, accum, dev, vals, x0, y0, AW, AH, margin):

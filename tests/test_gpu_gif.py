@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from cuburn_amd import _lib, configs, encoders, output, profile, render
+import encoder_harness as H
 from encoder_harness import SENTINEL, SLACK, assert_untouched, record, upload
 import gif_cases as GC
 import gif_model as M
@@ -33,18 +34,10 @@ def mgr(built):
 
 def encode(mgr, frame, colors, amp, cap=None, buf=None):
     """fl_gif_encode into pinned memory (or `buf`) pre-filled with the sentinel; checks the sentinel at and beyond cap."""
-    lib = _lib.load()
     h, w = frame.shape[:2]
     if cap is None:
-        cap = lib.fl_gif_bound(w, h)
-    t = upload(mgr, frame)
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_gif_encode(mgr.fb.ctx, w, h, t.data_ptr(), colors, amp, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert_untouched(buf, cap)
-    return buf, cap
+        cap = _lib.load().fl_gif_bound(w, h)
+    return H.encode(mgr, 'fl_gif_encode', frame, w, h, (colors, amp), cap, buf)
 
 
 def block_of(buf, seg=M.SEG):

@@ -24,13 +24,11 @@ import pytest
 
 from cuburn_amd import _lib, configs, output, profile, render
 import encoder_harness as H
-from encoder_harness import SENTINEL, SLACK, record, upload
+from encoder_harness import SENTINEL, SLACK, record, upload, assert_jpeg_criteria as assert_criteria
 import jpeg_cases as JC
 import jpeg_model as J
 
 pytestmark = pytest.mark.gpu
-
-EPS = 2.0 ** -8
 
 
 @pytest.fixture(scope='module')
@@ -46,7 +44,7 @@ def encode(mgr, planes, quality, cap=None, buf=None):
     _, h, w = planes.shape
     if cap is None:
         cap = _lib.load().fl_jpeg_bound(w, h)
-    return H.encode(mgr, 'fl_jpeg_encode', planes, w, h, quality, cap, buf)       # (checks the sentinel at and beyond cap)
+    return H.encode(mgr, 'fl_jpeg_encode', planes, w, h, (quality,), cap, buf)       # (checks the sentinel at and beyond cap)
 
 
 def stream_of(buf):
@@ -74,21 +72,6 @@ def encoded_case(mgr, name, ri):
         buf, _ = encode(mgr, planes, quality)
         _done[name] = (planes, quality, check, stream_of(buf), buf)
     return _done[name]
-
-
-def assert_criteria(data, planes, quality, ri):
-    """A, B and C for a stream; returns the parse."""
-    ps = J.parse(data)                                                              # A
-    qt = J.quant_tables(quality)
-    assert (ps.w, ps.h) == (planes.shape[2], planes.shape[1]) and ps.restart_interval == ri
-    assert np.array_equal(ps.qtables, qt)
-    v = J.dct_values(planes)                                                        # B
-    qz = np.stack([qt[0], qt[1], qt[1]])[:, J.ZIGZAG][:, None, :].astype(np.float64)
-    err = np.abs(ps.coefficients * qz - v) - qz / 2
-    print('largest |c q - v| - q / 2: %.3g (EPS %.3g)' % (err.max(), EPS))
-    assert (err <= EPS).all(), '%d coefficients beyond q / 2 + EPS, worst by %g' % (int((err > EPS).sum()), err.max())
-    assert J.assemble(ps.w, ps.h, qt, ri, ps.coefficients) == data                  # C
-    return ps
 
 
 @pytest.mark.parametrize('name', JC.NAMES)

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from cuburn_amd import _lib, configs, encoders, output, profile, render
+import encoder_harness as H
 from encoder_harness import SENTINEL, SLACK, assert_untouched, record, upload
 import jpeg420_model as M
 import jpeg_model as J
@@ -47,31 +48,16 @@ def mgr(built):
 
 def encode(mgr, planes, quality, sampling, flags=OPT, cap=None, buf=None):
     """fl_jpeg_encode_f into pinned memory (or `buf`) pre-filled with the sentinel; checks the sentinel at and beyond cap."""
-    lib = _lib.load()
     _, h, w = planes.shape
     if cap is None:
-        cap = lib.fl_jpeg_bound_f(w, h, sampling, flags)
-    t = upload(mgr, planes)
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_jpeg_encode_f(mgr.fb.ctx, w, h, t.data_ptr(), quality, sampling, flags, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert_untouched(buf, cap)
-    return buf, cap
+        cap = _lib.load().fl_jpeg_bound_f(w, h, sampling, flags)
+    return H.encode(mgr, 'fl_jpeg_encode_f', planes, w, h, (quality, sampling, flags), cap, buf)
 
 
 def encode_s(mgr, planes, quality, sampling):
-    lib = _lib.load()
     _, h, w = planes.shape
-    cap = lib.fl_jpeg_bound_s(w, h, sampling)
-    t = upload(mgr, planes)
-    buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_jpeg_encode_s(mgr.fb.ctx, w, h, t.data_ptr(), quality, sampling, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert_untouched(buf, cap)
-    return buf
+    cap = _lib.load().fl_jpeg_bound_s(w, h, sampling)
+    return H.encode(mgr, 'fl_jpeg_encode_s', planes, w, h, (quality, sampling), cap)[0]
 
 
 def stream_of(buf):

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from cuburn_amd import _lib, configs, encoders, output, profile, render
+import encoder_harness as H
 from encoder_harness import SENTINEL, SLACK, assert_untouched, record, upload
 import jpeg420_cases as JC
 import jpeg420_model as M
@@ -41,18 +42,10 @@ def mgr(built):
 
 def encode(mgr, planes, quality, sampling=S420, cap=None, buf=None):
     """fl_jpeg_encode_s into pinned memory (or `buf`) pre-filled with the sentinel; checks the sentinel at and beyond cap."""
-    lib = _lib.load()
     _, h, w = planes.shape
     if cap is None:
-        cap = lib.fl_jpeg_bound_s(w, h, sampling)
-    t = upload(mgr, planes)
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_jpeg_encode_s(mgr.fb.ctx, w, h, t.data_ptr(), quality, sampling, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    assert_untouched(buf, cap)
-    return buf, cap
+        cap = _lib.load().fl_jpeg_bound_s(w, h, sampling)
+    return H.encode(mgr, 'fl_jpeg_encode_s', planes, w, h, (quality, sampling), cap, buf)
 
 
 def stream_of(buf):

@@ -1,7 +1,7 @@
 """
 Xform opacity on the device (include/flame_hip.h (5) words 14 / 15, (6) FL_OP_OPACITY), through the C ABI.
 
-The CPU oracle knows nothing of opacity.  The tests rest on the "three boxes" flame of tests/test_cpu_opacity.py instead: the
+The CPU oracle knows nothing of opacity.  The tests rest on the "three boxes" flame of tests/flames.py instead: the
 images of its three xforms are disjoint, so a plotted sample lies in box k exactly when xform k produced it, and what an
 opacity must do to each box is known in closed form; exact identities (opacity 1 == no key, opacity 0 == the keyless render
 minus one box, every kernel form == every other) anchor the new code to everything the oracle already pins.
@@ -20,7 +20,9 @@ from common import O, prepare, frame_times
 from cuburn_amd import configs, profile, render, _lib
 from cuburn_amd.genome.use import SplineEval
 from cuburn_amd.packer import GenomePacker, OP_CONST, OP_OPACITY
-from test_cpu_opacity import (three_boxes, with_opacity, plot_probability, BOX_TOP, BOX_LOW_LEFT, BOX_LOW_RIGHT, BOX_WEIGHTS)
+from flames import (three_boxes, with_opacity, plot_probability, BOX_TOP, BOX_LOW_LEFT, BOX_LOW_RIGHT, BOX_WEIGHTS)
+import gpu_harness as H
+from gpu_harness import same_bits, setup_frame
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,111 +35,17 @@ def mgr(built):
     return render.RenderManager(device=0, nslots=1024, host_seed=42)
 
 
-def setup_frame(m, gnm, prof, tc=0.5):
-    gprof = profile.wrap(prof, gnm)
-    rdr = render.Renderer(gnm, gprof)
-    g = rdr._handle(m.fb)
-    m._copy(rdr, gnm)
-    dim = m.fb.calc_dim(gprof.width, gprof.height)
-    ts, td = frame_times(gprof, tc)
-    _lib.check(_lib.load().fl_interp(m.fb.ctx, g, dim.w, dim.h, ts, td))
-    return rdr, dim, g, ts, td
+def _as_pinned_here(r, *drop):
+    """A harness launch reduced to what these tests hold: three point words (the fourth belongs to the chaos tests)."""
+    return dict(((k, v) for k, v in r.items() if k not in ('params', 'prog') + drop), pts=r['pts'][:, :3].copy())
 
 
-def launch(m, gnm, prof, mode, nrounds, fuse, seeds_in=None, tc=0.5):
-    """One counted iterate launch from cleared buffers and NaN points (what fl_iterate does for a frame of up to 1024 rounds),
-    then the flush: everything the launch left behind."""
-    lib = _lib.load()
-    if seeds_in is not None:
-        m.fb.write('seeds', seeds_in)
-    seeds0 = m.fb.read('seeds', (m.fb.nwalkers, 3), np.uint32)
-    rdr, dim, g, ts, td = setup_frame(m, gnm, prof, tc)
-    nbins = dim.ah * dim.astride
-    _lib.check(lib.fl_debug_clear(m.fb.ctx, dim.w, dim.h, 1))
-    _lib.check(lib.fl_debug_iter_launch(m.fb.ctx, g, dim.w, dim.h, 0, nrounds + fuse, fuse, mode))
-    ctr = np.zeros(4, np.uint64)
-    _lib.check(lib.fl_debug_counters(m.fb.ctx, ctr.ctypes.data))
-    atom = m.fb.read('atom', (nbins,), np.uint64)
-    nwalk = m.fb.nslots * m.fb.nthreads
-    rng = m.fb.read('seeds', (m.fb.nwalkers, 3), np.uint32)[:nwalk]
-    pts = m.fb.read('points', (nwalk, 4), np.float32).view(np.uint32)[:, :3].copy()
-    _lib.check(lib.fl_debug_flush(m.fb.ctx, dim.w, dim.h))
-    front = m.fb.read('front', (nbins, 4), np.float32)
-    return dict(ctr=ctr, atom=atom, rng=rng, pts=pts, front=front, seeds0=seeds0, dim=(dim.ah, dim.astride),
-                samples=nrounds * nwalk, rdr=rdr, g=g)
+def launch(*a, **kw):
+    return _as_pinned_here(H.launch(*a, **kw))
 
 
-class env(object):
-    """FLAME_* switches are read when a context is created (FLAME_RTC_FLAGS: when a kernel is compiled)."""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = dict((k, os.environ.get(k)) for k in self.kw)
-        for k, v in self.kw.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def snapshot(gnm, prof, mode, nw=4, nslots=1024, nrounds=29, fuse=5, seeds_in=None, **switches):
-    """A launch in a context of its own geometry and switches."""
-    with env(FLAME_NW=None if nw == 4 else str(nw), **switches):
-        m = render.RenderManager(device=0, nslots=nslots, host_seed=44)
-        assert (m.fb.nw, m.fb.nslots) == (nw, nslots)
-        try:
-            r = launch(m, gnm, prof, mode, nrounds, fuse, seeds_in)
-        finally:
-            m.fb.free()
-    r.pop('rdr'), r.pop('g')
-    return r
-
-
-def same_bits(a, b, what, colour_exact=True, atomic=False, ref=None, min_lit=1000):
-    """Counters, RNG states, walker points and the flushed density channel bit for bit.  The packed cells (FL_BUF_ATOM after the
-    launch) and the colour sums are compared bit for bit too where no cell can have been drained on the way (fewer than 128
-    hits in every pixel); a flame with hotter pixels — the fixed points of the three boxes hold 1e5 hits — drains full cells into
-    the float accumulator in an order that is not reproducible between two runs of ONE kernel (see
-    test_paired_halves_are_the_walkers_of_1024_four_wave_slots): there the colour sums are held to DESIGN §2's 2e-6.
-    With direct atomics (``atomic``) a pixel that takes more than 512 hits in ONE round — the boxes' fixed points take thousands —
-    can pass the cell's 10-bit count before the drain that a returning add asks for has run (iter.hip, "Every add returns the
-    previous cell value"), with or without opacity.  ``ref`` is then the flushed density of the BINNED launch of the same genome
-    from the same seeds (the binned accumulate keeps every sample, and the walk is the same walk): a cell that holds fewer than
-    512 hits there never reaches the drain threshold, so on all those cells both atomic histograms must equal it exactly, and
-    their colour sums each other to 2e-6 — at least ``min_lit`` lit cells of them (the three boxes' attractor lights only ~800
-    cells in all, most of them hot: its callers ask for 20, and the atomic histogram with hidden samples is held cell for cell
-    on zoomed cfg2 in test_fractional_opacity_atomic_histogram_where_cells_are_comparable).  Returns what was compared."""
-    assert np.array_equal(a['ctr'][:3], b['ctr'][:3]), (what, a['ctr'], b['ctr'])
-    assert np.array_equal(a['rng'], b['rng']), what
-    assert np.array_equal(a['pts'], b['pts']), what
-    nodrain = float(a['front'][:, 3].max()) < 128.0 and float(b['front'][:, 3].max()) < 128.0
-    if atomic and not nodrain:
-        assert ref is not None, what
-        safe = ref < 512.0
-        lit = int((ref[safe] > 0).sum())
-        assert lit >= min_lit, (what, lit)
-        for r in (a, b):
-            assert np.array_equal(r['front'][safe, 3], ref[safe]), what
-        np.testing.assert_allclose(a['front'][safe, :3], b['front'][safe, :3], rtol=2e-6, atol=1e-4, err_msg=str(what))
-        return 'cells below the drain threshold: %d' % lit
-    assert np.array_equal(a['front'][:, 3], b['front'][:, 3]), what
-    if nodrain:
-        assert int(a['ctr'][3]) == 0 and int(b['ctr'][3]) == 0
-        assert np.array_equal(a['atom'], b['atom']), what
-    if nodrain and colour_exact:
-        assert np.array_equal(a['front'].view(np.uint32), b['front'].view(np.uint32)), what
-    else:       # (records grouped differently: the order of float additions may move, DESIGN §2 "binned == atomic")
-        np.testing.assert_allclose(a['front'][:, :3], b['front'][:, :3], rtol=2e-6, atol=1e-4, err_msg=str(what))
-    return 'every cell, packed cells too' if nodrain else 'every cell'
+def snapshot(*a, **kw):
+    return _as_pinned_here(H.snapshot(*a, **kw), 'rdr', 'g')
 
 
 def box(front, dim, rect, chan=3):
@@ -228,7 +136,7 @@ def test_interp_writes_plot_probability_per_temporal_sample(mgr):
     gnm, prof = three_boxes((None, [1.0, 0.0, 0.0, 0.0, 0.5, 0.2], 0.7))
     gnm['time'] = {'duration': 1, 'frame_width': 1.0}
     prof = dict(prof, frame_width=1.0)
-    rdr, dim, g, ts, td = setup_frame(mgr, gnm, prof, 0.5)
+    rdr, gprof, dim, g, ts, td = setup_frame(mgr, gnm, prof, 0.5)
     assert td > 0.9
     pk = rdr.packer
     dev = mgr.fb.read('params', (1024, pk.pstride), np.float32, g)
@@ -307,7 +215,7 @@ def test_opacity_zero_removes_exactly_that_xform(mgr):
     fronts = {}
     for tag, gnm in (('keyless', keyless), ('gone', gone)):
         mgr.fb.write('seeds', seeds0)
-        rdr, dim, g, ts, td = setup_frame(mgr, gnm, prof)
+        rdr, gprof, dim, g, ts, td = setup_frame(mgr, gnm, prof)
         run = C.c_uint64()
         _lib.check(lib.fl_iterate(mgr.fb.ctx, g, dim.w, dim.h, float(N), FUSE, _lib.ACCUM_BINNED, C.byref(run)))
         assert run.value == N
@@ -400,18 +308,20 @@ def test_fractional_opacity_distribution(mgr, keyless_reference, opac):
 
 
 # ------------------------------------------------------------------ 10. every kernel form renders the same samples
-FRACTIONAL = (0.5, 1.0, 0.25)
+FRACTIONAL_OPACITY = (0.5, 1.0, 0.25)
 
 CHILD = r'''
 import sys
 sys.path[:0] = [%(repo)r, %(repo)r + '/tests']
 import numpy as np
-import test_gpu_opacity as T
-gnm, prof = T.three_boxes(T.FRACTIONAL)
+import flames
+import gpu_harness
+gnm, prof = flames.three_boxes(%(opacity)r)
 seeds = np.load(%(seeds)r)
 out = {}
 for mode in (0, 1):
-    r = T.snapshot(gnm, prof, mode, seeds_in=seeds)
+    r = gpu_harness.snapshot(gnm, prof, mode, seeds_in=seeds)
+    r['pts'] = r['pts'][:, :3].copy()
     for k in ('ctr', 'atom', 'rng', 'pts', 'front'):
         out['%%s%%d' %% (k, mode)] = r[k]
 np.savez(%(out)r, **out)
@@ -419,7 +329,7 @@ np.savez(%(out)r, **out)
 
 
 def test_fractional_opacity_same_on_every_path(built, tmp_path, capfd):
-    gnm, prof = three_boxes(FRACTIONAL)
+    gnm, prof = three_boxes(FRACTIONAL_OPACITY)
     base = {}
     for mode in (0, 1):
         base[mode] = snapshot(gnm, prof, mode, seeds_in=None if mode == 0 else base[0]['seeds0'])
@@ -440,7 +350,7 @@ def test_fractional_opacity_same_on_every_path(built, tmp_path, capfd):
     # generation switch of the per-genome kernel, so a process of its own (the module cache does not key on the flags)
     np.save(str(tmp_path / 'seeds.npy'), seeds)
     out = str(tmp_path / 'nomerge.npz')
-    r = subprocess.run([sys.executable, '-c', CHILD % dict(repo=REPO, seeds=str(tmp_path / 'seeds.npy'), out=out)], capture_output=True,
+    r = subprocess.run([sys.executable, '-c', CHILD % dict(repo=REPO, opacity=FRACTIONAL_OPACITY, seeds=str(tmp_path / 'seeds.npy'), out=out)], capture_output=True,
                        text=True, timeout=300, env=dict(os.environ, FLAME_RTC_FLAGS='-DFL_ITER_MERGE_MAX_XF=0'))
     assert r.returncode == 0, r.stderr[-3000:]
     assert 'interpreter kernel' not in r.stderr

@@ -16,6 +16,10 @@ import pytest
 from common import O, prepare, frame_times
 from cuburn_amd import configs, profile, render, _lib
 from cuburn_amd.packer import GenomePacker
+from accum_inputs import synth_accum, sparse_accum
+from flames import small, linear_flame, animated_linear_flame, hot_flame, point_flame, animated_cfg5
+from gpu_harness import (walkers, setup_frame, run_device_model, run_device_model_gpu_only, run_filter, assert_close, density,
+                         check_chain_error)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,30 +37,6 @@ def mgr_prod(built):
     m = render.RenderManager(device=0, host_seed=42)
     assert (m.fb.nw, m.fb.nslots) == render.Framebuffers.NARROW == (4, 1536)
     return m
-
-
-def walkers(mgr):
-    """(slots, threads per slot, walker count, oracle geometry) of a manager's current context."""
-    ns, nt = mgr.fb.nslots, mgr.fb.nthreads
-    return ns, nt, ns * nt, {256: O.GEOM_4x64, 512: O.GEOM_8x64, 1024: O.GEOM_16x64}[nt]
-
-
-def small(cfg, w, h, **kw):
-    gnm, prof = cfg(**kw)
-    prof = dict(prof, width=w, height=h)
-    return gnm, prof
-
-
-def setup_frame(mgr, gnm, prof, tc=0.5):
-    """Upload + interp on the GPU; returns (rdr, gprof, dim, handle) and device params/palette."""
-    gprof = profile.wrap(prof, gnm)
-    rdr = render.Renderer(gnm, gprof)
-    g = rdr._handle(mgr.fb)
-    mgr._copy(rdr, gnm)
-    dim = mgr.fb.calc_dim(gprof.width, gprof.height)
-    ts, td = frame_times(gprof, tc)
-    _lib.check(_lib.load().fl_interp(mgr.fb.ctx, g, dim.w, dim.h, ts, td))
-    return rdr, gprof, dim, g, ts, td
 
 
 def test_shuffle_bit_exact(mgr):
@@ -103,64 +83,6 @@ def test_palette_bit_exact(mgr):
     assert np.array_equal(seeds2[nwalk:], rng_after)
 
 
-def run_device_model(mgr, gnm, prof, nrounds, fuse, launches=1, mode=0, seeds_in=None, tc=0.5):
-    """GPU and oracle from the same device params / palette / seeds / points; returns both states.
-    mode 0 = packed global atomics (hot flags + roulette live), 1 = binned (no sample thinning)."""
-    lib = _lib.load()
-    ns, nt, nwalk, geom = walkers(mgr)
-    if seeds_in is not None:                # before interp: the palette kernel draws from these too
-        mgr.fb.write('seeds', seeds_in)
-    seeds0 = mgr.fb.read('seeds', (nwalk + 64 * 256, 3), np.uint32)
-    rdr, gprof, dim, g, ts, td = setup_frame(mgr, gnm, prof, tc)
-    d = O.calc_dim(dim.w, dim.h)
-    nbins = dim.ah * dim.astride
-    _lib.check(lib.fl_debug_clear(mgr.fb.ctx, dim.w, dim.h, 1))
-    params = mgr.fb.read('params', (ns, rdr.packer.pstride), np.float32, g)
-    palette = mgr.fb.read('palette', (64, 256), np.uint64)
-    seeds = mgr.fb.read('seeds', (nwalk + 64 * 256, 3), np.uint32)
-    rng = seeds[:nwalk].copy()
-    points = np.full((nwalk, 4), np.nan, np.float32)
-    hot = np.zeros(nbins // 16, np.uint32)
-    atom = np.zeros(nbins, np.uint64)
-    out4 = np.zeros((nbins, 4), np.float32)
-    res = []
-    r0 = 0
-    for k in range(launches):
-        f = fuse if k == 0 else 0
-        _lib.check(lib.fl_debug_iter_launch(mgr.fb.ctx, g, dim.w, dim.h, r0, nrounds + f, f, mode))
-        ctr_ref = O.iter_launch(geom, d, rdr.packer.prog, params, palette, rng, points, ns,
-                                hot, atom, out4, r0, nrounds + f, f)
-        ctr_dev = np.zeros(4, np.uint64)
-        _lib.check(lib.fl_debug_counters(mgr.fb.ctx, ctr_dev.ctypes.data))
-        dev_atom = mgr.fb.read('atom', (nbins,), np.uint64)
-        res.append(dict(ctr_ref=ctr_ref.copy(), ctr_dev=ctr_dev, atom_ref=atom.copy(), atom_dev=dev_atom))
-        if mode == 1:                       # binned mode never thins: flags are neither read nor kept
-            _lib.check(lib.fl_debug_clear_hot(mgr.fb.ctx, dim.w, dim.h))
-            hot[:] = 0
-        _lib.check(lib.fl_debug_flush(mgr.fb.ctx, dim.w, dim.h))
-        O.flush(d, atom, out4, hot)
-        if mode == 1:
-            _lib.check(lib.fl_debug_clear_hot(mgr.fb.ctx, dim.w, dim.h))
-            hot[:] = 0
-        res[-1].update(front_dev=mgr.fb.read('front', (nbins, 4), np.float32), front_ref=out4.copy(),
-                       hot_dev=mgr.fb.read('hot', (nbins // 16,), np.uint32), hot_ref=hot.copy())
-        r0 += nrounds + f
-    dev_rng = mgr.fb.read('seeds', (nwalk + 64 * 256, 3), np.uint32)[:nwalk]
-    dev_pts = mgr.fb.read('points', (nwalk, 4), np.float32)
-    return res, (rng, points), (dev_rng, dev_pts), dim, seeds0
-
-
-def linear_flame():
-    """3 linear xforms + post affine + final xform: no transcendentals anywhere => bit-exact."""
-    gnm, prof = configs.cfg2()
-    for k in gnm['xforms']:
-        gnm['xforms'][k]['variations'] = {'linear': {'weight': 0.8}, 'bent': {'weight': 0.2}}
-    gnm['xforms']['1']['post_affine'] = configs._affine(10.0, 0.9, 0.05, -0.1)
-    gnm['final_xform'] = {'color': 0.3, 'color_speed': 0.25, 'pre_affine': configs._affine(-8.0, 0.97, 0.02, 0.01),
-                          'variations': {'linear': {'weight': 1.0}}}
-    return gnm, dict(prof, width=1280, height=720)
-
-
 def test_iter_bit_exact_linear(mgr):
     gnm, prof = linear_flame()
     res, ref_state, dev_state, dim, _ = run_device_model(mgr, gnm, prof, nrounds=8, fuse=5, launches=2)
@@ -174,19 +96,6 @@ def test_iter_bit_exact_linear(mgr):
         assert np.array_equal(r['hot_dev'], r['hot_ref']), k
     assert np.array_equal(dev_state[0], ref_state[0])          # RNG states after both launches
     assert np.array_equal(dev_state[1][:, :3], ref_state[1][:, :3])
-
-
-def animated_linear_flame():
-    """The transcendental-free flame in motion: camera pan, one rotating xform, two palettes, a
-    frame window that spans the whole animation: every slot sees a different parameter block
-    and the 64 palette rows differ."""
-    gnm, prof = linear_flame()
-    gnm['camera']['center'] = {'x': [-0.15, 0.3, 0.15, 0.3], 'y': 0.0}
-    gnm['camera']['scale'] = 1.0          # zoomed in: every cell stays below the packed-add limit of the binned drain
-    gnm['xforms']['0']['pre_affine']['angle'] = [70.0, 30.0, 100.0, 30.0]
-    gnm['palette'] = [configs._pal(0.0, configs.fire_palette()), configs._pal(1.0, configs.ice_palette())]
-    gnm['time'] = {'duration': 1, 'frame_width': 1.0}
-    return gnm, dict(prof, frame_width=1.0, fps=1, duration=1)
 
 
 @pytest.mark.parametrize('mode', [0, 1])
@@ -326,30 +235,6 @@ def test_pipelined_launches_equal_serial_launches(built, monkeypatch):
     np.testing.assert_allclose(fa[:, :3], fb[:, :3], rtol=1e-5, atol=1e-3)
 
 
-def hot_flame():
-    """The transcendental-free flame plus a strongly contracting xform: a ~100-pixel region that
-    takes 3 % of all samples."""
-    gnm, prof = linear_flame()
-    gnm['xforms']['3'] = {'weight': 0.031, 'color': 0.8, 'color_speed': 0.5,
-                          'pre_affine': configs._affine(15.0, 0.05, 0.3, -0.2),
-                          'variations': {'linear': {'weight': 1.0}}}
-    return gnm, dict(prof, width=512, height=512)
-
-
-def point_flame(share):
-    """The transcendental-free flame plus an xform that maps everything onto ONE point: that pixel
-    takes about `share` of all samples (share 1: the point xform alone)."""
-    gnm, prof = linear_flame()
-    point = {'weight': 1.0, 'color': 0.8, 'color_speed': 0.5, 'pre_affine': configs._affine(0.0, 0.0, 0.21, -0.13),
-             'variations': {'linear': {'weight': 1.0}}}
-    if share >= 1.0:
-        gnm['xforms'] = {'0': point}
-    else:
-        total = sum(x['weight'] for x in gnm['xforms'].values())
-        gnm['xforms']['3'] = dict(point, weight=total * share / (1.0 - share))
-    return gnm, dict(prof, width=512, height=512)
-
-
 @pytest.mark.parametrize('share', [1.0, 0.9, 0.6, 0.3])
 def test_binned_point_attractor_keeps_every_sample(mgr_prod, share):
     """A pixel that receives most of the samples: thousands of adds reach its LDS cell between the
@@ -481,10 +366,6 @@ def test_binned_hot_region_exact_density(mgr, layout, monkeypatch):
         mgr.fb.free()
 
 
-def density(front, dim):
-    return front[:, 3].reshape(dim.ah, dim.astride).astype(np.float64)
-
-
 @pytest.mark.parametrize('mode', [0, 1])
 def test_iter_distribution_cfg2(mgr, mode):
     """
@@ -532,41 +413,6 @@ def test_iter_distribution_cfg2(mgr, mode):
 
 
 # ---------------------------------------------------------------------------------- filters
-def synth_accum(dim, seed=1):
-    """A plausible accumulation buffer: smooth blobs + sparse noise + empty regions, YUV-ish."""
-    rs = np.random.RandomState(seed)
-    H, W = dim.ah, dim.astride
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
-    dens = np.zeros((H, W), np.float32)
-    for _ in range(6):
-        cx, cy, s = rs.uniform(0, W), rs.uniform(0, H), rs.uniform(8, 60)
-        dens += rs.uniform(20, 2000) * np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * s * s))
-    dens = rs.poisson(dens).astype(np.float32)
-    dens[: H // 5] = 0
-    buf = np.zeros((H, W, 4), np.float32)
-    buf[..., 3] = dens
-    buf[..., 0] = dens * rs.uniform(0.1, 0.9, (H, W))
-    buf[..., 1] = dens * rs.uniform(0.3, 0.7, (H, W))
-    buf[..., 2] = dens * rs.uniform(0.3, 0.7, (H, W))
-    return buf.reshape(-1, 4)
-
-
-def run_filter(mgr, name, dim, buf, vals):
-    lib = _lib.load()
-    _lib.check(lib.fl_debug_clear(mgr.fb.ctx, dim.w, dim.h, 0))
-    mgr.fb.write('front', buf)
-    arr = np.asarray(vals, np.float32)
-    _lib.check(lib.fl_filter(mgr.fb.ctx, _lib.FILT[name], dim.w, dim.h, arr.ctypes.data, len(arr)))
-    return mgr.fb.read('front', buf.shape, np.float32)
-
-
-def assert_close(dev, ref, rtol, atol, what):
-    assert np.isfinite(dev[np.isfinite(ref)]).all(), '%s: %d non-finite device values where the oracle is finite' % (
-        what, (~np.isfinite(dev[np.isfinite(ref)])).sum())
-    err = np.abs(dev - ref) - (atol + rtol * np.abs(ref))
-    bad = err > 0
-    assert not bad.any(), '%s: %d / %d out of tolerance, worst dev=%r ref=%r' % (
-        what, bad.sum(), bad.size, dev.flat[np.argmax(err)], ref.flat[np.argmax(err)])
 
 
 FW, FH = 200, 120
@@ -710,23 +556,6 @@ def test_filter_bilateral_wide_parameters(mgr, kind, vals):
     ref = O.bilateral_chain(d, buf, *vals)
     assert np.isfinite(ref).all()
     assert_close(dev, ref, 2e-3, 2e-4, 'bilateral chain %s %r' % (kind, vals))
-
-
-def sparse_accum(dim, seed=3):
-    """A few-samples-per-pixel buffer: isolated single hits, empty gaps, black and saturated colours
-    (the regime where the DE weights underflow to denormals)."""
-    rs = np.random.RandomState(seed)
-    H, W = dim.ah, dim.astride
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
-    lam = 0.02 + 3.0 * np.exp(-((xx - W * 0.6) ** 2 + (yy - H * 0.5) ** 2) / (2 * 25.0 ** 2))
-    lam[:, : W // 4] = 0.002
-    dens = rs.poisson(lam).astype(np.float32)
-    dens[H // 2, W // 8] = 900.0                      # one bright pixel in the empty quarter
-    col = rs.choice(np.array([0.0, 0.5, 1.0], np.float32), size=(H, W, 3))
-    buf = np.zeros((H, W, 4), np.float32)
-    buf[..., 3] = dens
-    buf[..., :3] = dens[..., None] * col
-    return buf.reshape(-1, 4)
 
 
 def test_filter_bilateral_sparse(built):
@@ -1005,17 +834,6 @@ def test_long_launch_log_beyond_4gb_binned_equals_atomic(monkeypatch, built):
     m.fb.free()
 
 
-def animated_cfg5():
-    """cfg5's twelve heavy xforms (more than the per-genome kernel keeps resident: records fetched per round, operand table in LDS)
-    with a moving xform, a moving offset and a turning camera, so that every temporal sample has its own parameter block."""
-    gnm, prof = configs.cfg5(samples=2 ** 26)
-    gnm['time'] = {'duration': 1, 'frame_width': 1.0}
-    gnm['camera'] = dict(gnm['camera'], rotation=[0.0, 15.0, 15.0, 15.0])
-    gnm['xforms']['03']['pre_affine']['angle'] = [30.0, 50.0, 80.0, 50.0]
-    gnm['xforms']['07']['pre_affine']['offset']['x'] = [-0.3, 0.5, 0.2, 0.5]
-    return gnm, dict(prof, frame_width=1.0, fps=24, duration=2)
-
-
 @pytest.mark.parametrize('rtc', ['1', '0'])
 @pytest.mark.parametrize('geom', [(8, 512), (16, 256)])
 @pytest.mark.parametrize('which,size', [('cfg3', (640, 360)), ('cfg3', (3840, 2160)), ('cfg5', (1280, 720))])
@@ -1055,22 +873,6 @@ def test_paired_halves_are_the_walkers_of_1024_four_wave_slots(which, size, geom
         np.testing.assert_allclose(fa[:, :3], fb[:, :3], rtol=1e-5, atol=1e-4)
     # binned == atomic in the paired geometry itself
     assert np.array_equal(out['paired', 0][1][:, 3], out['paired', 1][1][:, 3])
-
-
-def run_device_model_gpu_only(mgr, gnm, prof, nrounds, fuse, mode, seeds_in=None):
-    lib = _lib.load()
-    if seeds_in is not None:
-        mgr.fb.write('seeds', seeds_in)
-    seeds0 = mgr.fb.read('seeds', (mgr.fb.nwalkers, 3), np.uint32)
-    rdr, gprof, dim, g, ts, td = setup_frame(mgr, gnm, prof)
-    nbins = dim.ah * dim.astride
-    _lib.check(lib.fl_debug_clear(mgr.fb.ctx, dim.w, dim.h, 1))
-    _lib.check(lib.fl_debug_iter_launch(mgr.fb.ctx, g, dim.w, dim.h, 0, nrounds + fuse, fuse, mode))
-    ctr = np.zeros(4, np.uint64)
-    _lib.check(lib.fl_debug_counters(mgr.fb.ctx, ctr.ctypes.data))
-    atom = mgr.fb.read('atom', (nbins,), np.uint64)
-    rng = mgr.fb.read('seeds', (mgr.fb.nwalkers, 3), np.uint32)[:walkers(mgr)[2]]
-    return dict(ctr=ctr, atom=atom), None, rng, dim, seeds0
 
 
 def test_8k_wide_binned_equals_atomic(mgr):
@@ -1482,7 +1284,6 @@ def test_cfg2_full_size_iterate_and_filter_chain(built):
     cur = O.colorclip(d, cur, *vals['colorclip'])
     assert np.isfinite(dev).all()
     # tone-mapped values live in [0, 1]: 8 DE passes + log + gamma in fast math on both sides
-    from test_gpu_fullsize import check_chain_error
     check_chain_error(np.abs(dev - cur), 'cfg2 whole frame')
     # queue_frame renders the same frame in the same context (no geometry switch), and its 8-bit frame is the chain's
     # output: alpha > 0 exactly where the tone-mapped density is visible
@@ -1525,8 +1326,6 @@ def test_deferred_filter_fusion_is_bit_identical(mgr):
         a, b = run(chain, False), run(chain, True)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), chain
         assert np.isfinite(a).all()
-
-
 
 
 def test_filters_match_reference_kernel_vectors(mgr):

@@ -43,7 +43,7 @@ def encode(mgr, rgba, ch, cap=None, buf=None):
     h, w, _ = rgba.shape
     if cap is None:
         cap = _lib.load().fl_png_bound(w, h, ch)
-    return H.encode(mgr, 'fl_png_encode', rgba, w, h, ch, cap, buf)                # (checks the sentinel at and beyond cap)
+    return H.encode(mgr, 'fl_png_encode', rgba, w, h, (ch,), cap, buf)              # (checks the sentinel at and beyond cap)
 
 
 def file_of(buf):

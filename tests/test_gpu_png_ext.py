@@ -39,14 +39,7 @@ def encode_f(mgr, src, ch, bits, flags, cap=None, buf=None):
     if cap is None:
         cap = lib.fl_png_bound_f(w, h, ch, bits, flags)
         assert cap
-    t = upload(mgr, np.ascontiguousarray(src).view(np.uint8))
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_png_encode_f(mgr.fb.ctx, w, h, t.data_ptr(), ch, bits, flags, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    H.assert_untouched(buf, cap)
-    return buf
+    return H.encode(mgr, 'fl_png_encode_f', np.ascontiguousarray(src).view(np.uint8), w, h, (ch, bits, flags), cap, buf)[0]
 
 
 def file_of(buf):
@@ -144,7 +137,7 @@ def test_default_form_is_fl_png_encode(mgr, device_seg):
     img = XC.ten_band(37, 4)
     for ch in (3, 4):
         src = XC.source(img[:, :, :ch], ch, 8)
-        old, _ = H.encode(mgr, 'fl_png_encode', src, 37, 10, ch, _lib.load().fl_png_bound(37, 10, ch))
+        old, _ = H.encode(mgr, 'fl_png_encode', src, 37, 10, (ch,), _lib.load().fl_png_bound(37, 10, ch))
         new = encode_f(mgr, src, ch, 8, 0)
         assert file_of(new) == file_of(old) == P.encode(src[:, :, :ch], device_seg) and record(new) == record(old)
 

@@ -38,14 +38,7 @@ def encode(mgr, src, ch, bits, cap=None, buf=None):
     if cap is None:
         cap = lib.fl_tiff_bound(w, h, ch, bits)
         assert cap
-    t = upload(mgr, np.ascontiguousarray(src).view(np.uint8))
-    if buf is None:
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    buf[:] = SENTINEL
-    _lib.check(lib.fl_tiff_encode(mgr.fb.ctx, w, h, t.data_ptr(), ch, bits, buf.ctypes.data, 0, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    H.assert_untouched(buf, cap)
-    return buf
+    return H.encode(mgr, 'fl_tiff_encode', np.ascontiguousarray(src).view(np.uint8), w, h, (ch, bits), cap, buf)[0]
 
 
 def file_of(buf, ch, bits):

@@ -24,7 +24,8 @@ from common import O, frame_times
 from cuburn_amd import configs, profile, render, _lib
 import tone_model as TM
 import tone_cases as T
-from test_gpu_parity import run_filter, synth_accum, sparse_accum
+from accum_inputs import synth_accum, sparse_accum
+from gpu_harness import run_filter, check_chain_error, filter_chain_on_device, oracle_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -281,7 +282,6 @@ def test_rich_flam3_chain_against_the_oracle(mgr, tmp_path):
     """The `rich` flam3 file (vibrancy 0.9, highlight_power 1.5, gamma 3, gamma_threshold 0.02) at 320 x 240 through the
     Renderer's own filter objects: the device chain against the oracle's on the same accumulator, under the full-size bars."""
     from cuburn_amd.genome import store
-    from test_gpu_fullsize import check_chain_error, filter_chain_on_device, oracle_chain
     lib = _lib.load()
     gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'genome_front.json')))
     path = tmp_path / 'rich.flam3'

@@ -9,12 +9,12 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O
 from cuburn_amd import configs, render
-import test_gpu_fullsize as T
+import gpu_harness as H
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else 'cfg2'
 gnm, prof = configs.CONFIGS[cfg]()
 m = render.RenderManager(device=0, host_seed=42)
-rdr, gprof, dim, td, nrun, front = T.iterate_frame(m, gnm, prof, 0.5, 2 ** 28)
+rdr, gprof, dim, td, nrun, front = H.iterate_frame(m, gnm, prof, 0.5, 2 ** 28)
 d = O.calc_dim(gprof.width, gprof.height)
 vals = {}
 stages = {}

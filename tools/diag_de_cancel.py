@@ -7,14 +7,14 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O
 from cuburn_amd import render, _lib
-import test_gpu_parity as P
+import accum_inputs as A
 lib = _lib.load()
 m = render.RenderManager(device=0, nslots=1024, host_seed=7)
 for k in [int(v) for v in sys.argv[1:]]:
     rs = np.random.RandomState(7000 + k)
     w, h = int(rs.choice([96, 161, 320, 480, 641])), int(rs.choice([64, 97, 180, 270, 359]))
     dim = m.fb.set_dim(w, h); d = O.calc_dim(w, h)
-    acc = (P.synth_accum if k % 2 == 0 else P.sparse_accum)(dim, seed=k + 1)
+    acc = (A.synth_accum if k % 2 == 0 else A.sparse_accum)(dim, seed=k + 1)
     buf = O.yuv_to_rgb(d, acc)
     bil = [float(rs.uniform(0.5, 12.0)), float(10 ** rs.uniform(-2.5, -0.3)), float(rs.uniform(0.3, 4.0)), float(rs.uniform(0.3, 1.2)), float(rs.uniform(0.5, 8.0))]
     _lib.check(lib.fl_debug_clear(m.fb.ctx, dim.w, dim.h, 0))

@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O
 from cuburn_amd import render, _lib
-import test_gpu_parity as P
+import accum_inputs as A
 lib = _lib.load()
 os.environ['FLAME_DE_UNFUSED_ENDS'] = '1'
 k = int(sys.argv[1])
@@ -24,7 +24,7 @@ for nd in range(1, 9):
     m = render.RenderManager(device=0, nslots=1024, host_seed=7)
     dim = m.fb.set_dim(w, h)
     if bil is None:
-        acc = (P.synth_accum if k % 2 == 0 else P.sparse_accum)(dim, seed=k + 1)
+        acc = (A.synth_accum if k % 2 == 0 else A.sparse_accum)(dim, seed=k + 1)
         buf = O.yuv_to_rgb(d, acc)
         bil = [float(rs.uniform(0.5, 12.0)), float(10 ** rs.uniform(-2.5, -0.3)), float(rs.uniform(0.3, 4.0)), float(rs.uniform(0.3, 1.2)), float(rs.uniform(0.5, 8.0))]
         ref = buf.copy()

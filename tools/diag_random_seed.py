@@ -9,11 +9,11 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O, prepare, frame_times
 from cuburn_amd import profile, render, _lib
-import test_gpu_random_genomes as T
+import flames as F
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 lib = _lib.load()
-gnm, prof = T.random_genome(seed)
+gnm, prof = F.random_genome(seed)
 print('xforms:', {k: sorted(v['variations']) for k, v in gnm['xforms'].items()}, 'final' in gnm)
 gprof = profile.wrap(prof, gnm)
 tc = 0.37

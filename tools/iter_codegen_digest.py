@@ -24,10 +24,7 @@ def genomes():
     sys.path[:0] = [REPO, os.path.join(REPO, 'tests')]
     from cuburn_amd import configs
     import chaos_model
-    from test_cpu_chaos import FRACTIONAL, many_xforms
-    from test_cpu_opacity import three_boxes, with_opacity
-    from test_gpu_chaos import spread_flame
-    from test_gpu_parity import linear_flame
+    from flames import FRACTIONAL, many_xforms, three_boxes, with_opacity, spread_flame, linear_flame
     out = dict((k, configs.CONFIGS[k]()[0]) for k in ('cfg2', 'cfg3', 'cfg4', 'cfg5'))
     out['allvars'] = configs.allvars()[0]
     out['linear_post_final'] = linear_flame()[0]

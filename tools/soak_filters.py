@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O
 from cuburn_amd import render, _lib
-import test_gpu_parity as P
+import accum_inputs as A
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 lib = _lib.load()
@@ -19,7 +19,7 @@ for k in (only or range(cases)):
     rs = np.random.RandomState(7000 + k)
     w, h = int(rs.choice([96, 161, 320, 480, 641])), int(rs.choice([64, 97, 180, 270, 359]))
     dim = m.fb.set_dim(w, h); d = O.calc_dim(w, h)
-    acc = (P.synth_accum if k % 2 == 0 else P.sparse_accum)(dim, seed=k + 1)
+    acc = (A.synth_accum if k % 2 == 0 else A.sparse_accum)(dim, seed=k + 1)
     buf = O.yuv_to_rgb(d, acc)
     bil = [float(rs.uniform(0.5, 12.0)), float(10 ** rs.uniform(-2.5, -0.3)), float(rs.uniform(0.3, 4.0)), float(rs.uniform(0.3, 1.2)), float(rs.uniform(0.5, 8.0))]
     log = [float(rs.uniform(1.0, 8.0)), float(10 ** rs.uniform(-4, -1.5))]

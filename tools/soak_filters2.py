@@ -9,7 +9,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import O
 from cuburn_amd import render, _lib
-import test_gpu_parity as P
+import accum_inputs as A
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 lib = _lib.load()
@@ -38,7 +38,7 @@ for k in (only or range(cases)):
     rs = np.random.RandomState(9000 + k)
     w, h = int(rs.choice([161, 320, 480])), int(rs.choice([97, 180, 270]))
     dim = m.fb.set_dim(w, h); d = O.calc_dim(w, h)
-    acc = (P.synth_accum if k % 2 == 0 else P.sparse_accum)(dim, seed=k + 1)
+    acc = (A.synth_accum if k % 2 == 0 else A.sparse_accum)(dim, seed=k + 1)
     buf = O.yuv_to_rgb(d, acc)
     bil = [float(10 ** rs.uniform(-1.3, 1.7)), float(10 ** rs.uniform(-1.7, -0.3)), float(10 ** rs.uniform(-1.3, 1.0)), float(rs.uniform(0.0, 2.0)), float(rs.uniform(-8.0, 8.0))]
     report('bilateral', k, run(dim, buf, 'bilateral', bil), O.bilateral_chain(d, buf, *bil), bil)

@@ -8,14 +8,14 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from common import prepare, frame_times
 from cuburn_amd import profile, render, _lib
-import test_gpu_random_genomes as T
+import flames as F
 
 lib = _lib.load()
 m = render.RenderManager(device=0, nslots=1024, host_seed=3)
 worst = 0.0
 nbad = 0
 for seed in range(1, 60, 2):                     # odd seeds are the animated ones
-    gnm, prof = T.random_genome(seed)
+    gnm, prof = F.random_genome(seed)
     rs = np.random.RandomState(seed)
     for tc in [0.0, 1.0, 0.5, float(rs.uniform(-0.2, 1.2)), float(rs.uniform(0, 1))]:
         for fw in (0.0, 1.0, 8.0):

@@ -12,7 +12,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from cuburn_amd import _lib, profile, render
-import test_gpu_random_genomes as T
+import flames as F
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 SIZES = [(33, 17), (640, 360), (1000, 999), (1280, 720), (1920, 1080), (2560, 1440), (3840, 2160), (4096, 1716), (7680, 4320)]
@@ -21,7 +21,7 @@ lib = _lib.load()
 rs = np.random.RandomState(2026)
 for case in range(ncases):
     seed = 1000 + case
-    gnm, prof = T.random_genome(seed)
+    gnm, prof = F.random_genome(seed)
     w, h = SIZES[rs.randint(len(SIZES))]
     nw, nslots = GEOMS[rs.randint(len(GEOMS))]
     nsamp = float(2 ** rs.uniform(21.0, 28.6))             # (above 2^28: two launches)
