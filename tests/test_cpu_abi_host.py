@@ -396,7 +396,7 @@ def test_documents_name_only_tools_that_exist():
     assert not files - rows, sorted(files - rows)
 
 
-HELPER_MODULES = ('flames', 'accum_inputs', 'gpu_harness', 'encoder_harness')
+HELPER_MODULES = ('flames', 'accum_inputs', 'gpu_harness', 'encoder_harness', 'encoder_contract')
 TOOLS_ON_HELPERS = ('soak_filters', 'soak_filters2', 'soak_slots', 'soak_interp', 'soak_packed_log', 'soak_random_genomes', 'diag_accum',
                     'diag_binned', 'diag_chain_error', 'diag_de_cancel', 'diag_de_cancel2', 'diag_point_filters', 'diag_random_seed',
                     'iter_codegen_digest')

@@ -9,6 +9,7 @@ child runs once for the module.  The whole path — fl_output_apng against fl_ou
 queue_frame against the raw output of the same seeds — runs here, with the library's own segment length.
 """
 import ctypes as C
+import functools
 import io
 import os
 import pickle
@@ -22,6 +23,8 @@ import pytest
 
 from cuburn_amd import _lib, configs, encoders, output, profile, render
 import apng_cases as A
+import encoder_contract as EC
+import encoder_harness as H
 import png_ext_model as X
 
 pytestmark = pytest.mark.gpu
@@ -41,8 +44,7 @@ def child(built, tmp_path_factory):
         return pickle.load(f)
 
 
-def record(buf):
-    return tuple(int(v) for v in np.frombuffer(bytes(buf[:16]), '<u4'))
+record = functools.partial(H.record, chunks=True)          # (nbytes, status, segment, chunks)
 
 
 def block_of(buf, n, seg=A.SMALL_SEG):
@@ -163,12 +165,7 @@ def test_frame_bytes_in_the_file(child, shape, pattern, flags):
 
 
 # ------------------------------------------------------------------ the whole path, in this process
-@pytest.fixture(scope='module')
-def mgr(built):
-    m = render.RenderManager(device=0, nslots=1024, host_seed=42)
-    yield m
-    _lib.check(_lib.load().fl_ctx_sync(m.fb.ctx))
-    m.fb.free()
+mgr = EC.mgr_fixture()
 
 
 @pytest.mark.parametrize('bits', (8, 16))

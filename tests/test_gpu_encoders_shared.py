@@ -8,7 +8,8 @@ cases of the encoders' own tests for which the regrow and the reuse both happen.
 import numpy as np
 import pytest
 
-from cuburn_amd import _lib, render
+from cuburn_amd import _lib
+import encoder_contract as EC
 import encoder_harness as H
 import jpeg_cases as JC
 import png_cases as PC
@@ -18,12 +19,7 @@ from encoder_harness import assert_jpeg_criteria
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope='module')
-def mgr(built):
-    m = render.RenderManager(device=0, nslots=1024, host_seed=42)
-    yield m
-    _lib.check(_lib.load().fl_ctx_sync(m.fb.ctx))
-    m.fb.free()
+mgr = EC.mgr_fixture()
 
 
 @pytest.fixture(scope='module')

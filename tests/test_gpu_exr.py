@@ -2,48 +2,40 @@
 The device OpenEXR encoder (cuburn_amd/csrc/exr.hip; fl_exr_encode, fl_output_exr, DeviceEXROutput) against the model of
 tests/exr_model.py, which tests/test_cpu_exr.py holds to numpy's float16 and to its own reader.  Every file is compared byte for
 byte with the file the model writes for the same samples; the frames are those of tests/exr_cases.py, the smallest at which the
-conversion, the cropped tiles, the two data forms and the placement can go wrong.  Then the source's stride, the capacity rule, the
-destinations, bad arguments, fl_output_exr on the front buffer in place, and the path through the shim.
+conversion, the cropped tiles, the two data forms and the placement can go wrong.  Then the source's stride, fl_output_exr on the
+front buffer in place, and the path through the shim.  What fl_exr_encode and fl_output_exr share with every encoder's entry points
+(the capacity rule, the destinations, refused calls, the timing slot) is the `exr` row of tests/encoder_contract.py.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from cuburn_amd import _lib, configs, output, profile, render
+from cuburn_amd import _lib, output, render
+import encoder_contract as EC
 import encoder_harness as H
-from encoder_harness import SENTINEL, SLACK, record, upload
+from encoder_harness import SENTINEL, SLACK
 import exr_cases as XC
 import exr_model as X
 
 pytestmark = pytest.mark.gpu
+ROW = EC.ROW['exr']
+mgr = EC.mgr_fixture()
 
 
-@pytest.fixture(scope='module')
-def mgr(built):
-    m = render.RenderManager(device=0, nslots=1024, host_seed=42)
-    yield m
-    _lib.check(_lib.load().fl_ctx_sync(m.fb.ctx))
-    m.fb.free()
-
-
-def encode(mgr, src, ch, px, cap=None, buf=None, stride=None):
-    """fl_exr_encode from f32 [h][stride][4] into pinned memory (or `buf`) pre-filled with the sentinel; waits, checks the sentinel
-    at and beyond cap; returns the buffer.  `src` is [h][w][4] unless `stride` says its rows are longer than the frame's."""
-    lib = _lib.load()
+def encode(mgr, src, ch, px, stride=None):
+    """fl_exr_encode from f32 [h][stride][4] into pinned memory pre-filled with the sentinel; waits, checks the sentinel at and beyond
+    cap; returns the buffer.  `src` is [h][w][4] unless `stride` says its rows are longer than the frame's."""
     h, sw, _ = src.shape
     w = sw if stride is None else stride[0]
     assert src.shape[2] == 4 and src.dtype == np.float32
-    if cap is None:
-        cap = lib.fl_exr_bound(w, h, ch, px)
-        assert cap
-    return H.encode(mgr, 'fl_exr_encode', np.ascontiguousarray(src).view(np.uint8), w, h, (sw, ch, px), cap, buf)[0]
+    cap = _lib.load().fl_exr_bound(w, h, ch, px)
+    assert cap
+    return H.encode(mgr, 'fl_exr_encode', np.ascontiguousarray(src).view(np.uint8), w, h, (sw, ch, px), cap)[0]
 
 
 def file_of(buf, ch):
-    nbytes, status, param = record(buf)
-    assert status == 0 and param == X.tile_bytes(ch)
-    return bytes(buf[16:16 + nbytes])
+    return EC.file_of(ROW, buf, (0, ch, 0))                  # (status 0, and the record's parameter is the channel count's tile)
 
 
 def explain(data, want, src, ch, px):
@@ -148,84 +140,6 @@ def test_source_stride(mgr, form):
     want = X.encode(np.ascontiguousarray(src[:, :w]), ch, px)
     explain(data, want, np.ascontiguousarray(src[:, :w]), ch, px)
     assert data == want
-
-
-# ------------------------------------------------------------------ capacity, destinations, bad arguments
-def test_capacity(mgr):
-    src = XC.mixed(X.HALF, XC.MIXED_SEED[(X.HALF, 4)])
-    h, w, _ = src.shape
-    data = file_of(encode(mgr, src, 4, X.HALF), 4)
-    need, tb = len(data), X.tile_bytes(4)
-    buf = encode(mgr, src, 4, X.HALF, cap=16 + need)          # (encode checks the sentinel at and beyond cap)
-    assert record(buf) == (need, 0, tb) and file_of(buf, 4) == data
-    for cap in (16 + need - 1, 16 + X.header_bytes(w, h, 4, X.HALF) + 8 * 6):
-        buf = encode(mgr, src, 4, X.HALF, cap=cap)
-        assert record(buf) == (need, 1, tb)
-        assert (buf[16:] == SENTINEL).all()                   # nothing behind the record
-
-
-def test_pageable_memory(mgr):
-    src = XC.mixed(X.FLOAT, XC.MIXED_SEED[(X.FLOAT, 3)])
-    cap = _lib.load().fl_exr_bound(src.shape[1], src.shape[0], 3, X.FLOAT)
-    buf = encode(mgr, src, 3, X.FLOAT, buf=np.empty(cap + SLACK, np.uint8))
-    assert file_of(buf, 3) == X.encode(src, 3, X.FLOAT)
-
-
-def test_device_destination_at_an_odd_address(mgr):
-    import torch
-    lib = _lib.load()
-    src = XC.mixed(X.HALF, XC.MIXED_SEED[(X.HALF, 3)])
-    h, w, _ = src.shape
-    want = X.encode(src, 3, X.HALF)
-    cap = 16 + len(want) + 7
-    t = upload(mgr, src.view(np.uint8))
-    out = torch.full((cap + SLACK,), SENTINEL, dtype=torch.uint8, device=t.device)
-    host = mgr.fb._pinned((cap,), 'u1')
-    host[:] = SENTINEL
-    torch.cuda.synchronize(mgr.fb.device)
-    _lib.check(lib.fl_exr_encode(mgr.fb.ctx, w, h, t.data_ptr(), w, 3, X.HALF, host.ctypes.data, out.data_ptr() + 1, cap))      # both destinations
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    dev = out.cpu().numpy()
-    assert dev[0] == SENTINEL and (dev[1 + cap:] == SENTINEL).all() and file_of(dev[1:], 3) == want
-    assert file_of(host, 3) == want
-
-
-def test_bad_arguments(mgr):
-    lib = _lib.load()
-    w, h = 37, 10
-    src = XC.ramps(w, h, 4)
-    want = X.encode(src, 4, X.HALF)
-    t = upload(mgr, src.view(np.uint8))
-    cap = lib.fl_exr_bound(w, h, 4, X.HALF)
-    buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    ctx, sp, dst = mgr.fb.ctx, t.data_ptr(), buf.ctypes.data
-    assert lib.fl_exr_bound(20000, 65535, 4, X.HALF) == 0 == lib.fl_exr_bound(20000, 65535, 3, X.FLOAT)
-    # (w, h, src, stride, channels, pixel, host, dev, cap)
-    bad = [(0, h, sp, w, 4, 1, dst, 0, cap), (w, 0, sp, w, 4, 1, dst, 0, cap), (65536, h, sp, 65536, 4, 1, dst, 0, cap), (w, 65536, sp, w, 4, 1, dst, 0, cap),
-           (w, h, sp, w, 2, 1, dst, 0, cap), (w, h, sp, w, 5, 1, dst, 0, cap), (w, h, sp, w, 0, 1, dst, 0, cap),
-           (w, h, sp, w, 4, 0, dst, 0, cap), (w, h, sp, w, 4, 3, dst, 0, cap), (w, h, sp, w, 4, 16, dst, 0, cap),
-           (20000, 65535, sp, 20000, 4, 1, dst, 0, cap),                   # a frame whose fl_exr_bound is 0: beyond 2^32 - 1
-           (w, h, 0, w, 4, 1, dst, 0, cap), (w, h, sp, w - 1, 4, 1, dst, 0, cap), (w, h, sp, 0, 4, 1, dst, 0, cap), (w, h, sp, w, 4, 1, None, 0, cap),
-           (w, h, sp, w, 4, 1, dst, 0, 16 + X.header_bytes(w, h, 4, X.HALF) + 8 - 1)]
-    for args in bad:
-        buf[:] = SENTINEL
-        assert lib.fl_exr_encode(ctx, *args) == _lib.FL_E_INVAL, args
-        assert lib.fl_last_error()
-        if args[2] and args[3] >= args[0]:
-            assert lib.fl_output_exr(ctx, *(args[:2] + args[4:])) == _lib.FL_E_INVAL, args
-        _lib.check(lib.fl_ctx_sync(ctx))
-        assert (buf == SENTINEL).all()
-        _lib.check(lib.fl_exr_encode(ctx, w, h, sp, w, 4, 1, dst, 0, cap))      # ... and the next frame is still right
-        _lib.check(lib.fl_ctx_sync(ctx))
-        assert file_of(buf, 4) == want and (buf[cap:] == SENTINEL).all()
-
-
-def test_encode_is_timed(mgr):
-    """The encode's kernels are in slot 5 of fl_timings_detail, like the other encoders'."""
-    _lib.check(_lib.load().fl_timings_reset(mgr.fb.ctx))
-    assert mgr.timings()['encode_ms'] == 0.0
-    encode(mgr, XC.ramps(70, 70, 2), 3, X.HALF)
-    assert mgr.timings()['encode_ms'] > 0.0
 
 
 # ------------------------------------------------------------------ the front buffer in place
@@ -334,10 +248,8 @@ class _ExrWithFront(output.DeviceEXROutput):
 @pytest.mark.parametrize('block', ({'type': 'exr'}, {'type': 'exr', 'pixel': 'float', 'alpha': True}), ids=('half', 'float-alpha'))
 def test_through_the_shim(built, block):
     """output: {"type": "exr"} through profile, Renderer and queue_frame: the file decodes to the accumulator's crop."""
-    gnm, prof = configs.cfg2(samples=2 ** 22)
     W, Hh = 320, 180
-    prof = dict(prof, width=W, height=Hh, spp=2 ** 22 / float(W * Hh), output=block)
-    gprof = profile.wrap(prof, gnm)
+    gnm, gprof = EC.small_profile(block, W, Hh)
     m = render.RenderManager(device=0, host_seed=7)
     try:
         rdr = render.Renderer(gnm, gprof)
@@ -363,20 +275,10 @@ def test_through_the_shim(built, block):
 
 def test_command_line_writes_an_exr(built, tmp_path):
     """python -m cuburn_amd FLAME --still --codec exr --exr-pixel float, end to end."""
-    import json
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    gold = json.load(open(os.path.join(here, 'golden', 'genome_front.json')))
-    (tmp_path / 'B.json').write_text(json.dumps(gold['db']['B']))
-    out = subprocess.run([sys.executable, '-m', 'cuburn_amd', 'B', '-d', str(tmp_path), '--still', '-P', 'preview', '--codec', 'exr',
-                          '--exr-pixel', 'float', '-o', str(tmp_path), '--width', '320', '--height', '180', '--spp', '200'],
-                         cwd=os.path.dirname(here), capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    files = sorted(f for f in os.listdir(str(tmp_path)) if f.endswith('.exr'))
-    assert len(files) == 1, (os.listdir(str(tmp_path)), out.stderr[-500:])
-    data = open(os.path.join(str(tmp_path), files[0]), 'rb').read()
+    files = [f for f in EC.run_cli(tmp_path, '--still', '-P', 'preview', '--codec', 'exr', '--exr-pixel', 'float', '--width', '320', '--height', '180',
+                                   '--spp', '200') if f.endswith('.exr')]
+    assert len(files) == 1, files
+    data = open(files[0], 'rb').read()
     ps = X.parse(data)
     assert (ps.w, ps.h, ps.channels, ps.pixel, ps.nt) == (320, 180, 3, X.FLOAT, 5 * 6)
     pic = ps.samples.view(np.float32)

@@ -3,57 +3,40 @@ The device PNG encoder's extended forms (cuburn_amd/csrc/png.hip; fl_png_encode_
 filter) against the model of tests/png_ext_model.py, which tests/test_cpu_png_ext.py holds to zlib and Pillow: 16-bit samples and a
 filter type per row.  Every file is compared byte for byte with the file the model writes for the same pixels, with the segment
 length the device's record reports; the frames are those of tests/png_ext_cases.py, the smallest at which the filter stage can go
-wrong.  Then the default form against fl_png_encode, fl_output_png_f against fl_output(FL_OUT_RGBA16), the capacity rule, the
-destinations, bad arguments, and the path through the shim.
+wrong.  Then the default form against fl_png_encode, and the path through the shim.  What fl_png_encode_f and fl_output_png_f
+share with every encoder's entry points (the capacity rule, the destinations, refused calls, fl_output_png_f against
+fl_output(FL_OUT_RGBA16)) is in the `png_f_paeth` and `png_f_adaptive` rows of tests/encoder_contract.py.
 """
-import ctypes as C
+import functools
 import io
 
 import numpy as np
 import pytest
 
-from cuburn_amd import _lib, configs, output, profile, render
-import encoder_harness as H
-from encoder_harness import SENTINEL, SLACK, record, upload
+from cuburn_amd import _lib, output, render
+import encoder_contract as EC
+from encoder_harness import record
 import png_ext_cases as XC
 import png_ext_model as X
 import png_model as P
 
 pytestmark = pytest.mark.gpu
+ROW = EC.ROW['png_f_adaptive']
+mgr = EC.mgr_fixture()
+file_of = functools.partial(EC.file_of, ROW)
 
 
-@pytest.fixture(scope='module')
-def mgr(built):
-    m = render.RenderManager(device=0, nslots=1024, host_seed=42)
-    yield m
-    _lib.check(_lib.load().fl_ctx_sync(m.fb.ctx))
-    m.fb.free()
-
-
-def encode_f(mgr, src, ch, bits, flags, cap=None, buf=None):
-    """fl_png_encode_f from u8 / u16 [h][w][4] into pinned memory (or `buf`) pre-filled with the sentinel; waits, checks the
-    sentinel at and beyond cap; returns the buffer."""
-    lib = _lib.load()
-    h, w, _ = src.shape
+def encode_f(mgr, src, ch, bits, flags):
+    """fl_png_encode_f from u8 / u16 [h][w][4] into pinned memory pre-filled with the sentinel; waits, checks the sentinel at and
+    beyond cap; returns the buffer."""
     assert src.shape[2] == 4 and src.dtype == (np.uint8 if bits == 8 else np.uint16)
-    if cap is None:
-        cap = lib.fl_png_bound_f(w, h, ch, bits, flags)
-        assert cap
-    return H.encode(mgr, 'fl_png_encode_f', np.ascontiguousarray(src).view(np.uint8), w, h, (ch, bits, flags), cap, buf)[0]
-
-
-def file_of(buf):
-    nbytes, status, seg = record(buf)
-    assert status == 0
-    return bytes(buf[16:16 + nbytes])
+    return EC.encode(mgr, ROW, src, (ch, bits, flags))[0]
 
 
 @pytest.fixture(scope='module')
 def device_seg(mgr):
     """The library's segment length, from the record of a one-pixel frame."""
-    seg = record(encode_f(mgr, np.zeros((1, 1, 4), np.uint16), 3, 16, 0))[2]
-    assert 256 <= seg <= 65535
-    return seg
+    return EC.param_of(mgr, ROW)
 
 
 def assert_is_model(mgr, img, ch, bits, flags, seg):
@@ -137,114 +120,9 @@ def test_default_form_is_fl_png_encode(mgr, device_seg):
     img = XC.ten_band(37, 4)
     for ch in (3, 4):
         src = XC.source(img[:, :, :ch], ch, 8)
-        old, _ = H.encode(mgr, 'fl_png_encode', src, 37, 10, (ch,), _lib.load().fl_png_bound(37, 10, ch))
+        old, _ = EC.encode(mgr, EC.ROW['png'], src, (ch,))
         new = encode_f(mgr, src, ch, 8, 0)
         assert file_of(new) == file_of(old) == P.encode(src[:, :, :ch], device_seg) and record(new) == record(old)
-
-
-# ------------------------------------------------------------------ the whole path
-@pytest.mark.parametrize('flags', (0, X.ADAPTIVE))
-def test_whole_path_16(mgr, device_seg, flags):
-    """fl_output_png_f(bits 16) = fl_output(FL_OUT_RGBA16) + the encode: same samples, same dither states afterwards, a closed frame."""
-    lib = _lib.load()
-    w, h = 64, 48
-    dim = mgr.fb.set_dim(w, h)
-    fid = C.c_uint32()
-    _lib.check(lib.fl_frame_begin(mgr.fb.ctx, C.byref(fid)))      # first: a frame chooses the lane whose buffers the calls below use
-    _lib.check(lib.fl_debug_clear(mgr.fb.ctx, w, h, 0))
-    rs = np.random.RandomState(11)
-    front = (rs.rand(dim.ah * dim.astride, 4) * 1.3 - 0.1).astype(np.float32)
-    mgr.fb.write('front', front)
-    start = mgr.fb.read('seeds', (mgr.fb.nwalkers, 3), np.uint32)
-    plain = np.empty((h, w, 4), np.uint16)
-    _lib.check(lib.fl_output(mgr.fb.ctx, w, h, _lib.OUT['rgba16'], plain.ctypes.data, 0))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    after_plain = mgr.fb.read('seeds', (mgr.fb.nwalkers, 3), np.uint32)
-    assert not np.array_equal(start, after_plain) and plain.std() > 1000 and (plain & 255).std() > 10
-
-    for ch in (3, 4):
-        mgr.fb.write('seeds', start)                          # (the frame stays open: the same lane, the same framebuffer)
-        cap = lib.fl_png_bound_f(w, h, ch, 16, flags)
-        buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-        buf[:] = SENTINEL
-        _lib.check(lib.fl_output_png_f(mgr.fb.ctx, w, h, ch, 16, flags, buf.ctypes.data, 0, cap))
-        ms = C.c_float(-1.0)
-        _lib.check(lib.fl_frame_ms(mgr.fb.ctx, fid.value, C.byref(ms)))
-        assert ms.value >= 0.0
-        _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-        assert (buf[cap:] == SENTINEL).all()
-        data = file_of(buf)
-        ps = X.parse(data, device_seg)
-        assert (ps.w, ps.h, ps.channels, ps.bits) == (w, h, ch, 16)
-        assert np.array_equal(ps.pixels, plain[:, :, :ch])    # the decoded samples are the plain call's
-        assert data == X.encode(plain, ch, 16, flags, device_seg)
-        assert np.array_equal(mgr.fb.read('seeds', (mgr.fb.nwalkers, 3), np.uint32), after_plain)
-
-
-# ------------------------------------------------------------------ capacity, destinations, bad arguments
-def test_capacity(mgr, device_seg):
-    img = XC.ten_band(40, 8)
-    src = XC.source(img, 4, 16)
-    data = file_of(encode_f(mgr, src, 4, 16, X.ADAPTIVE))
-    need = len(data)
-    for cap in (16 + need - 1, 16 + P.HEADER_BYTES):
-        buf = encode_f(mgr, src, 4, 16, X.ADAPTIVE, cap=cap)  # (checks the sentinel at and beyond cap)
-        assert record(buf) == (need, 1, device_seg)
-    buf = encode_f(mgr, src, 4, 16, X.ADAPTIVE, cap=16 + need)
-    assert record(buf) == (need, 0, device_seg) and file_of(buf) == data
-
-
-def test_pageable_memory(mgr, device_seg):
-    img = XC.ten_band(33, 6)
-    src = XC.source(img, 3, 16)
-    cap = _lib.load().fl_png_bound_f(33, 10, 3, 16, X.ADAPTIVE)
-    buf = encode_f(mgr, src, 3, 16, X.ADAPTIVE, buf=np.empty(cap + SLACK, np.uint8))
-    assert file_of(buf) == X.encode(src, 3, 16, X.ADAPTIVE, device_seg)
-
-
-def test_device_destination(mgr, device_seg):
-    import torch
-    lib = _lib.load()
-    img = XC.ten_band(33, 8)
-    src = XC.source(img, 4, 16)
-    want = X.encode(src, 4, 16, X.ADAPTIVE, device_seg)
-    cap = 16 + len(want) + 7
-    t = upload(mgr, src.view(np.uint8))
-    out = torch.full((cap + SLACK,), SENTINEL, dtype=torch.uint8, device=t.device)
-    torch.cuda.synchronize(mgr.fb.device)
-    _lib.check(lib.fl_png_encode_f(mgr.fb.ctx, 33, 10, t.data_ptr(), 4, 16, X.ADAPTIVE, None, out.data_ptr() + 1, cap))
-    _lib.check(lib.fl_ctx_sync(mgr.fb.ctx))
-    dev = out.cpu().numpy()
-    assert dev[0] == SENTINEL and (dev[1 + cap:] == SENTINEL).all() and file_of(dev[1:]) == want
-
-
-def test_bad_arguments(mgr, device_seg):
-    lib = _lib.load()
-    img = XC.ten_band(37, 8)
-    src = XC.source(img, 4, 16)
-    want = X.encode(src, 4, 16, X.ADAPTIVE, device_seg)
-    h, w = 10, 37
-    t = upload(mgr, src.view(np.uint8))
-    cap = lib.fl_png_bound_f(w, h, 4, 16, X.ADAPTIVE)
-    buf = mgr.fb._pinned((cap + SLACK,), 'u1')
-    ctx, sp, dst = mgr.fb.ctx, t.data_ptr(), buf.ctypes.data
-    assert lib.fl_png_bound(9000, 65535, 4) != 0 == lib.fl_png_bound_f(9000, 65535, 4, 16, 0)
-    bad = [(w, h, sp, 4, 0, 0, dst, 0, cap), (w, h, sp, 4, 12, 0, dst, 0, cap), (w, h, sp, 4, 32, 1, dst, 0, cap),
-           (w, h, sp, 4, 16, 2, dst, 0, cap), (w, h, sp, 4, 8, 3, dst, 0, cap), (w, h, sp, 3, 16, 0x80000000, dst, 0, cap),
-           (9000, 65535, sp, 4, 16, 0, dst, 0, cap),                       # a frame whose fl_png_bound_f is 0 (and whose fl_png_bound is not)
-           (w, h, sp, 5, 16, 0, dst, 0, cap), (0, h, sp, 4, 16, 0, dst, 0, cap), (w, h, 0, 4, 16, 0, dst, 0, cap),
-           (w, h, sp, 4, 16, 0, None, 0, cap), (w, h, sp, 4, 16, 0, dst, 0, 16 + P.HEADER_BYTES - 1)]
-    for args in bad:
-        buf[:] = SENTINEL
-        assert lib.fl_png_encode_f(ctx, *args) == _lib.FL_E_INVAL, args
-        assert lib.fl_last_error()
-        if args[2]:
-            assert lib.fl_output_png_f(ctx, *(args[:2] + args[3:])) == _lib.FL_E_INVAL, args
-        _lib.check(lib.fl_ctx_sync(ctx))
-        assert (buf == SENTINEL).all()
-        _lib.check(lib.fl_png_encode_f(ctx, w, h, sp, 4, 16, X.ADAPTIVE, dst, 0, cap))      # ... and the next frame is still right
-        _lib.check(lib.fl_ctx_sync(ctx))
-        assert file_of(buf) == want and (buf[cap:] == SENTINEL).all()
 
 
 # ------------------------------------------------------------------ through the shim
@@ -273,9 +151,7 @@ def test_through_the_shim(built, alpha):
     block = {'type': 'png', 'encoder': 'device', 'bits': 16, 'filter': 'adaptive'}
     if alpha:
         block['alpha'] = True
-    gnm, prof = configs.cfg2(samples=2 ** 22)
-    prof = dict(prof, width=64, height=48, spp=2 ** 22 / (64.0 * 48.0), output=block)
-    gprof = profile.wrap(prof, gnm)
+    gnm, gprof = EC.small_profile(block)
     m = render.RenderManager(device=0, host_seed=7)
     try:
         rdr = render.Renderer(gnm, gprof)
