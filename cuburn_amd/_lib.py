@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get('FLAME_HIP_LIB', LIB_PATH)
 
 (FL_OK, FL_E_INVAL, FL_E_NOMEM, FL_E_HIP, FL_E_NODEV, FL_E_UNSUPPORTED) = (0, -1, -2, -3, -4, -5)
 
-FILT = dict(yuv=0, bilateral=1, logscale=2, colorclip=3, smearclip=4, haloclip=5, plainclip=6, logencode=7, de=8)
+FILT = dict(yuv=0, bilateral=1, logscale=2, colorclip=3, smearclip=4, haloclip=5, plainclip=6, logencode=7, de=8, bloom=9)
 BUF = dict(front=0, back=1, params=2, palette=3, points=4, seeds=5, atom=6, hot=7, side=8, log=9, dir=10)
 ACCUM_ATOMIC, ACCUM_BINNED = 0, 1
 FL_OP_CHAOS_CDF = 11                # include/flame_hip.h (6): dst[0..nxf-1] <- row of the chaos matrix (xaos)

@@ -845,19 +845,26 @@ static void gauss7(float stdev, float *c)      // cuburn/filters.py:11-16
     for (int i = 0; i < 7; ++i) c[i] /= s;
 }
 
-// What fl_filter refuses, found before it touches anything: an unknown id, too few scalars (or none to read), a bad `de` radius / curve.
+// What fl_filter refuses, found before it touches anything: an unknown id, too few scalars (or none to read), a bad `de` radius / curve,
+// a `bloom` whose reach is above the limit or whose scalars are not finite.
 static int check_filter(int id, const float *p, uint32_t np)
 {
     static const struct { uint32_t np; const char *msg; } need[] = {
         {0, ""}, {5, "bilateral needs sstd,cstd,dstd,dpow,gspeed"}, {2, "logscale needs k1,k2"},
         {5, "colorclip needs vib,highpow,gam,lin,lingam"}, {4, "smearclip needs width,gam_m_1,lin,lingam"}, {1, "haloclip needs gam_m_1"},
-        {4, "plainclip needs gam_m_1,lin,lingam,brightness"}, {1, "logencode needs degamma"}, {3, "de needs R,Rmin,curve"}};
-    if (id < FL_FILT_YUV || id > FL_FILT_DE) return fail(FL_E_UNSUPPORTED, "unknown filter id", __FILE__, __LINE__);
+        {4, "plainclip needs gam_m_1,lin,lingam,brightness"}, {1, "logencode needs degamma"}, {3, "de needs R,Rmin,curve"},
+        {3, "bloom needs threshold,strength,tap_0 (then tap_1 .. tap_R)"}};
+    if (id < FL_FILT_YUV || id > FL_FILT_BLOOM) return fail(FL_E_UNSUPPORTED, "unknown filter id", __FILE__, __LINE__);
     REQUIRE(np >= need[id].np, need[id].msg);
     REQUIRE(p || !need[id].np, "null filter scalars");
     if (id == FL_FILT_DE) {
         REQUIRE(!(p[0] > (float)FL_DE_MAX_RADIUS), "de: R above 96 px");
         REQUIRE(p[2] > 0.0f, "de: curve must be > 0");
+    }
+    if (id == FL_FILT_BLOOM) {
+        REQUIRE(np - 3 <= FL_BLOOM_MAX_REACH, "bloom: more than 384 taps per side");
+        for (uint32_t i = 0; i < np; ++i) REQUIRE(std::isfinite(p[i]), "bloom: non-finite threshold, strength or tap");
+        REQUIRE(p[0] >= 0.0f, "bloom: threshold must be >= 0");
     }
     return FL_OK;
 }
@@ -916,6 +923,9 @@ int fl_filter(fl_ctx *c, int id, uint32_t w, uint32_t h, const float *p, uint32_
         // in place on d_front; d_back / d_blur hold the staged sources
         launch_de_adaptive(st, d, ln.d_front, ln.d_back, ln.d_blur, ln.d_de_tmax, ln.d_de_sinv,
                            p[0], std::min(std::max(p[1], 0.0f), p[0]), p[2]);
+        break;
+    case FL_FILT_BLOOM:                  // in place on d_front; d_side holds the excess blurred along x
+        launch_bloom(st, d, ln.d_front, ln.d_side, p + 2, (int)np - 3, p[0], p[1]);
         break;
     }
     ev_end(c, e);

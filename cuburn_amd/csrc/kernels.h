@@ -106,6 +106,11 @@ void launch_de_adaptive(hipStream_t st, fl_dim d, float4 *buf, float4 *stage_c, 
 size_t de_adaptive_tiles(fl_dim d);
 void de_adaptive_norms(float *out);
 
+// bloom.hip: the `bloom` filter (FL_FILT_BLOOM), in place on front; side is scratch of nbins float4; taps[0 .. R] the centre tap and
+// one side of the symmetric kernel, R <= FL_BLOOM_MAX_REACH (fl_filter checks).  The taps travel as kernel arguments: `taps` is
+// free again when the call returns.
+void launch_bloom(hipStream_t st, fl_dim d, float4 *front, float4 *side, const float *taps, int R, float thr, float strength);
+
 // resample.hip: flam3's spatial filter + supersample decimation, src laid out as din (the ss-fold frame) -> dst laid out as dout;
 // ntaps in [ss, ss + 2 * FL_GUTTER] of the same parity as ss (fl_resample checks)
 void launch_resample(hipStream_t st, fl_dim din, fl_dim dout, int ss, float4 *dst, const float4 *src, const float *taps, int ntaps);

@@ -286,8 +286,9 @@ def order_streams(fb, device, ctx_waits):
 # over the profile's filter order).  bilateral: 8 directions x (15 taps + the 9 rows of the two nested density
 # blurs at the outermost tap, cuburn/filters.py:62-95) = 192; haloclip: den_blur_1c on patterns 2 and 3 = 2 x 3
 # rows; smearclip: full_blur on patterns 2, 3, 0, 1 = 3 x 3 rows (pattern 0 is horizontal)
-# (cuburn/filters.py:118-170); everything else is per pixel.
-FILTER_REACH = {'bilateral': 8 * 24, 'haloclip': 6, 'smearclip': 9, 'de': 96}      # de: FL_DE_MAX_RADIUS
+# (cuburn/filters.py:118-170); everything else is per pixel.  bloom's reach is above BAND_HALO: a sample-sharded frame whose chain
+# lists it is all-reduced whole.
+FILTER_REACH = {'bilateral': 8 * 24, 'haloclip': 6, 'smearclip': 9, 'de': 96, 'bloom': 384}      # FL_DE_MAX_RADIUS, FL_BLOOM_MAX_REACH
 # Rows of summed accumulator a band carries beyond its own rows on either side: a multiple of 16 (a band with its
 # halos must be a valid accumulator height), at least the reach of the profile's chain (checked per frame).
 BAND_HALO = 224

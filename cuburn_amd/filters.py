@@ -127,6 +127,41 @@ class PlainClip(_Simple):
         return [f32(gam - 1), lin, lingam, f32(gprof.filters.plainclip.brightness(tc))]
 
 
+def bloom_taps(sigma):
+    """
+    The taps of the ``bloom`` filter's Gaussian of ``sigma`` bins, cut at R = ceil(3 sigma): exp(-i^2 / (2 sigma^2)) for
+    i = -R .. R, normalised to sum 1 in float64, then float32.  sigma 0 gives the single tap 1.
+    """
+    sigma = float(sigma)
+    if not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError('bloom: sigma must be finite and >= 0 (got %g)' % sigma)
+    R = int(np.ceil(3.0 * sigma))
+    if R == 0:
+        return np.ones(1, np.float32)
+    i = np.arange(-R, R + 1, dtype=np.float64)
+    t = np.exp(-i * i / (2.0 * sigma * sigma))
+    return (t / t.sum()).astype(np.float32)
+
+
+@Filter.register('bloom')
+class Bloom(_Simple):
+    """A wide Gaussian glare of the light above ``threshold``: front += strength * blur(excess)."""
+    max_reach = 384                 # FL_BLOOM_MAX_REACH: taps per side, also the filter's reach (distributed.FILTER_REACH)
+
+    def scalars(self, gprof, params, dim, tc):
+        # sigma in 1080p pixels, as Bilateral's spatial_std: the same look at every size and on either side of `spatial`
+        radius = params.radius(tc)
+        sigma = radius * dim.w / 1920.
+        if not (sigma >= 0 and np.isfinite(sigma)):
+            raise ValueError('bloom: radius must be finite and >= 0 (got %g)' % radius)
+        R = int(np.ceil(3.0 * sigma))
+        if R > self.max_reach:
+            raise ValueError('bloom: radius %g at width %d reaches %d bins per side, above the limit of %d'
+                             % (radius, dim.w, R, self.max_reach))
+        taps = bloom_taps(sigma)
+        return [f32(params.threshold(tc)), f32(params.strength(tc))] + [f32(t) for t in taps[R:]]
+
+
 @Filter.register('logencode')
 class LogEncode(_Simple):
     def scalars(self, gprof, params, dim, tc):

@@ -49,6 +49,9 @@ filters = {
     'de': {
         'radius': scalespline(11), 'minimum': scalespline(0, max=1), 'curve': scalespline(0.6),
     },
+    'bloom': {
+        'threshold': scalespline(1.0), 'radius': scalespline(12), 'strength': scalespline(0.25),
+    },
     'haloclip': {},
     'spatial': {},
     'smearclip': {'width': scalespline(0.7, d='Spatial stdev of filter')},

@@ -232,9 +232,16 @@ enum {
     FL_FILT_HALOCLIP = 5,  /* haloclip chain   filters.py:113-130      gam_m_1                      */
     FL_FILT_PLAINCLIP = 6, /* plainclip        code/filters.py:332-350 gam_m_1,lin,lingam,brightness*/
     FL_FILT_LOGENCODE = 7, /* logencode        code/filters.py:81-90   degamma                      */
-    FL_FILT_DE = 8         /* adaptive DE      DESIGN.md §4 (flam3)    R,Rmin,curve (R <= 96, curve > 0) */
+    FL_FILT_DE = 8,        /* adaptive DE      DESIGN.md §4 (flam3)    R,Rmin,curve (R <= 96, curve > 0) */
+    FL_FILT_BLOOM = 9      /* Gaussian glare   DESIGN.md §4.18         threshold,strength,tap_0..tap_R (below) */
 };
 #define FL_DE_MAX_RADIUS 96    /* FL_FILT_DE: the largest R in px, and so the filter's reach */
+/* FL_FILT_BLOOM: front += strength * blur(E), E = (w - threshold) / w * (r, g, b, w) where w > threshold and 0 elsewhere, blurred
+ * along x then y over the whole padded buffer (sources outside it count as zero) with the symmetric kernel of 2R + 1 taps whose
+ * centre and one side are tap_0 .. tap_R: nparams = 3 + R, R <= FL_BLOOM_MAX_REACH.  The taps are used as given (not renormalised).
+ * FL_E_INVAL, before anything is queued: fewer than 3 parameters, R above the limit, a non-finite threshold, strength or tap, a
+ * negative threshold.  Never part of a deferred chain: deferred steps run first. */
+#define FL_BLOOM_MAX_REACH 384 /* FL_FILT_BLOOM: the largest R in bins (769 taps), and so the filter's reach */
 int fl_filter(fl_ctx *ctx, int filter_id, uint32_t w, uint32_t h, const float *params, uint32_t nparams);
 
 /* flam3's spatial filter + supersample decimation: front (laid out for ss*w x ss*h) -> front (laid out for w x h).
