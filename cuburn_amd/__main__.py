@@ -104,23 +104,32 @@ def render(args, prof, flame=None, ahead=None):
                 _lib.load().fl_ctx_sync(rmgr.fb.ctx)
             except Exception:
                 pass
-            rdr.out.abort()
+            for mod in [rdr.out] + [px.out for px in rdr.proxies]:
+                try:                                         # one module's failure must not leave the others' encoders running
+                    mod.abort()
+                except Exception:
+                    print('abort of %s failed: %s' % (type(mod).__name__, traceback.format_exc()), file=sys.stderr)
             raise
 
     def render_job_(name, times):
         times = list(times)
         rdr.out = output.get_output_for_profile(gprof)       # a fresh encoder per file
+        rdr.proxies = output.get_proxies_for_profile(gprof)  # ... and per proxy: <name><suffix><ext>
         for idx, (evt, frame) in _one_ahead(lambda t: rmgr.queue_frame(rdr, gnm, gprof, t), times):
             while took[0] > 2000 and not evt.query():        # long frames: poll, keep the interpreter responsive
                 time.sleep(0.2)
             evt.synchronize()
             took[0] = evt.time()
             _deliver(rdr.out, frame, name)
+            for px, pframe in zip(rdr.proxies, evt.proxies):
+                _deliver(px.out, pframe, name + px.suffix)
             if args.rawfn:
                 _preview(args.rawfn, frame)
             print('%s%s (%3d/%3d), %dms' % (tag, name, idx, len(times), took[0]), file=sys.stderr)
             sys.stderr.flush()
         _deliver(rdr.out, None, name)                        # flush: video outputs return their segment here
+        for px in rdr.proxies:
+            _deliver(px.out, None, name + px.suffix)
 
     done, lost = jobs.run_jobs(todo, render_job)
     return len(lost)

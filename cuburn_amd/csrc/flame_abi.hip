@@ -92,6 +92,15 @@ struct Pending {
     }
 };
 
+// fl_resize's tables on the device: one entry per (w, h, w2, h2, nxt, nyt) and content hash.  `first` holds xfirst then yfirst,
+// `taps` xtaps then ytaps.
+struct ResizeTables {
+    uint32_t key[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t hash = 0, used = 0;      // used 0: empty; otherwise the serial of the last call that took it (the smallest leaves first)
+    DevBuf<int32_t> first;
+    DevBuf<float> taps;
+};
+
 // One "lane" = a stream with its own framebuffers, sample log and per-frame parameter buffers.
 // Consecutive frames alternate between two lanes so that the drain + filter + output kernels of
 // frame k (bandwidth / TA bound) overlap the iterate kernel of frame k+1 (issue / latency bound),
@@ -126,6 +135,9 @@ struct Lane {
     hipEvent_t ev_out_done = nullptr;      // output-dither RNG states
     bool interp_rec = false, iter_rec = false, out_rec = false;
     Pending pend;
+    static const int kResizeTables = 4;             // fl_resize: the tables of the last few sizes (a master and its proxies)
+    ResizeTables rz[kResizeTables];
+    uint64_t rz_serial = 0;
 
     std::array<hipEvent_t *, 7> events() { return {&ev_interp_done, &ev_iter_done, &ev_out_done, &ev_it[0], &ev_ac[0], &ev_it[1], &ev_ac[1]}; }
     int quiesce(bool with_aux)
@@ -145,6 +157,7 @@ struct Lane {
     {
         release_fb();
         d_params.release(); d_palette.release(); d_enc.release(); d_enc_out.release();
+        for (ResizeTables &t : rz) { t.first.release(); t.taps.release(); t.used = 0; }
         for (int k = 0; k < 2; ++k) { d_log[k].release(); d_dir[k].release(); }
         if (aux) hipStreamDestroy(aux);
         for (hipEvent_t *ev : events()) if (*ev) hipEventDestroy(*ev);
@@ -951,6 +964,73 @@ int fl_resample(fl_ctx *c, uint32_t w, uint32_t h, uint32_t ss, const float *tap
     EvPair *e = ev_begin(c, c->filt_ev);
     if (!(rc = flush_pending(c, ln))) {                     // a deferred yuv / DE belongs to the source size
         launch_resample(ln.stream, din, dout, (int)ss, ln.d_back, ln.d_front, taps, (int)ntaps);
+        swap(ln.d_front, ln.d_back);
+    }
+    ev_end(c, e);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+// One axis of fl_resize's tables, checked on the host; folds the table into `hash` on the way.
+static int check_resize_axis(const int32_t *first, const float *taps, uint32_t n_out, uint32_t nt, uint32_t n_in, uint64_t *hash)
+{
+    REQUIRE(nt >= 1 && nt <= FL_RESIZE_MAX_TAPS && nt <= n_in, "resize: taps per output must lie in 1..50 and within the source's size");
+    uint64_t hsh = *hash;
+    for (uint32_t i = 0; i < n_out; ++i) {
+        REQUIRE(first[i] >= 0 && (uint64_t)first[i] + nt <= n_in, "resize: a window reaches outside the source");
+        hsh = (hsh ^ (uint32_t)first[i]) * 0x100000001b3ull;
+    }
+    for (size_t i = 0, n = (size_t)n_out * nt; i < n; ++i) {
+        REQUIRE(std::isfinite(taps[i]), "resize: non-finite tap");
+        uint32_t bits;
+        memcpy(&bits, taps + i, 4);
+        hsh = (hsh ^ bits) * 0x100000001b3ull;
+    }
+    *hash = hsh;
+    return FL_OK;
+}
+
+int fl_resize(fl_ctx *c, uint32_t w, uint32_t h, uint32_t w2, uint32_t h2, const int32_t *xfirst, const float *xtaps, uint32_t nxt,
+              const int32_t *yfirst, const float *ytaps, uint32_t nyt)
+{
+    REQUIRE(c && xfirst && xtaps && yfirst && ytaps, "null argument");
+    REQUIRE(w && h && w2 && h2, "resize: zero size");
+    REQUIRE(w <= 0x3fffffffu && h <= 0x3fffffffu, "resize: source size overflows");
+    REQUIRE(w2 <= w && h2 <= h, "resize: the result is larger than the source (enlarging is not supported)");
+    uint64_t hash = 0xcbf29ce484222325ull;
+    int rc;
+    if ((rc = check_resize_axis(xfirst, xtaps, w2, nxt, w, &hash)) || (rc = check_resize_axis(yfirst, ytaps, h2, nyt, h, &hash))) return rc;
+    REQUIRE(resize_rows_fit(xfirst, w2, nxt), "resize: the x windows of 64 neighbouring outputs span more than 576 source bins (not a downscale's table)");
+    HIPCHK(hipSetDevice(c->device));
+    Lane &ln = c->lane();
+    fl_dim din;
+    const fl_dim dout = calc_dim(w2, h2);
+    if ((rc = ensure_fb(ln, w, h, &din))) return rc;
+    // the lane's device copy of these tables, or the least recently used place for one
+    const uint32_t key[6] = {w, h, w2, h2, nxt, nyt};
+    ResizeTables *t = nullptr;
+    for (ResizeTables &q : ln.rz) if (q.used && q.hash == hash && !memcmp(q.key, key, sizeof key)) t = &q;
+    if (!t) {
+        t = &ln.rz[0];
+        for (ResizeTables &q : ln.rz) if (q.used < t->used) t = &q;
+        // kernels queued earlier may still read what this entry held
+        HIPCHK(hipStreamSynchronize(ln.stream));
+        t->used = 0;
+        const size_t nx = (size_t)w2 * nxt, ny = (size_t)h2 * nyt;
+        if ((rc = t->first.reserve((size_t)w2 + h2, "resize tables")) || (rc = t->taps.reserve(nx + ny, "resize tables"))) return rc;
+        HIPCHK(hipMemcpy(t->first.p, xfirst, 4 * (size_t)w2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t->first.p + w2, yfirst, 4 * (size_t)h2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t->taps.p, xtaps, 4 * nx, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t->taps.p + nx, ytaps, 4 * ny, hipMemcpyHostToDevice));
+        memcpy(t->key, key, sizeof key);
+        t->hash = hash;
+    }
+    t->used = ++ln.rz_serial;
+    EvPair *e = ev_begin(c, c->filt_ev);
+    if (!(rc = flush_pending(c, ln))) {                     // a deferred yuv / DE belongs to the source size
+        launch_resize(ln.stream, din, dout, ln.d_back, ln.d_side, ln.d_front, t->first.p, t->taps.p, (int)nxt,
+                      t->first.p + w2, t->taps.p + (size_t)w2 * nxt, (int)nyt);
         swap(ln.d_front, ln.d_back);
     }
     ev_end(c, e);

@@ -115,6 +115,17 @@ void launch_bloom(hipStream_t st, fl_dim d, float4 *front, float4 *side, const f
 // ntaps in [ss, ss + 2 * FL_GUTTER] of the same parity as ss (fl_resample checks)
 void launch_resample(hipStream_t st, fl_dim din, fl_dim dout, int ss, float4 *dst, const float4 *src, const float *taps, int ntaps);
 
+// resize.hip: Lanczos downscale (fl_resize), src laid out as din -> dst laid out as dout (dout.w <= din.w, dout.h <= din.h); side is
+// scratch of din's nbins float4.  The tables are DEVICE arrays: xfirst[dout.w], xtaps[dout.w][nxt], yfirst[dout.h], ytaps[dout.h][nyt],
+// nxt, nyt <= FL_RESIZE_MAX_TAPS, every window inside the source (fl_resize checks).  resize_rows_fit (host arrays): the x windows of
+// every FL_RESIZE_XSEG neighbouring output columns span at most FL_RESIZE_XSPAN source bins, which is what k_resize_rows stages per wave
+// (a downscale of ratio <= 8 spans at most 63 * 8 + 1 + 50 = 555).
+#define FL_RESIZE_XSEG 64
+#define FL_RESIZE_XSPAN 576
+bool resize_rows_fit(const int32_t *xfirst, uint32_t w2, uint32_t nxt);
+void launch_resize(hipStream_t st, fl_dim din, fl_dim dout, float4 *dst, float4 *side, const float4 *src,
+                   const int32_t *xfirst, const float *xtaps, int nxt, const int32_t *yfirst, const float *ytaps, int nyt);
+
 // output.hip
 void launch_f32_to_rgba(hipStream_t st, fl_dim d, const float4 *src, fl_mwc *rng, uint32_t nrng, int fmt, void *dst);
 

@@ -176,15 +176,18 @@ class FrameGather(object):
         self.n_alloc = self.n_done = 0
 
 
-def run_frame_loop(queue_frame, nframes, depth=2, gather=None, stage=None):
+def run_frame_loop(queue_frame, nframes, depth=2, gather=None, stage=None, gprof=None):
     """
     The render loop of main.py:64-76 — queue frame k+1, then wait for frame k — with ``depth``
     frames queued ahead of the one being waited for, and the finished frames handed to a
     FrameGather.  ``queue_frame(slot)`` queues one frame and returns ``(evt, h_out)`` (``slot``:
     the tensor the frame should be rendered into, or None); ``stage(slot, h_out)`` copies a host
     frame into its slot when frames are not rendered into it directly (CPU collectives).
-    Returns the number of frames completed.
+    ``gprof``: the profile the frames are rendered with; a gathered loop refuses one with ``proxies`` before it queues anything
+    (the ranks gather the master's frames alone).  Returns the number of frames completed.
     """
+    if gather is not None and gprof is not None:
+        refuse_proxies(gprof)
     if gather is not None and depth > gather.block:
         raise ValueError('run_frame_loop: %d frames queued ahead need gather blocks of at least %d frames (got %d)'
                          % (depth, depth, gather.block))
@@ -506,6 +509,13 @@ class DistComm(object):
         return sum_accumulators(acc)
 
 
+def refuse_proxies(gprof, rdr=None):
+    """Sample- and frame-sharded renders gather ONE frame per time: a profile with `proxies` is refused."""
+    if gprof.raw().get('proxies') or getattr(rdr, 'proxies', None):
+        raise ValueError('sharded rendering writes no proxies (the profile lists %d): the ranks gather the master\'s frames alone; '
+                         'distribute whole files instead (jobs.py)' % len(gprof.raw().get('proxies') or rdr.proxies))
+
+
 def sharded_frame_steps(mgr, rdr, gnm, gprof, tc, rank, world, device=None, copy=True, bands=True):
     """
     One sample-sharded frame as a generator: it yields at the frame's collectives — ``('exchange', acc2d, plan, padded)``
@@ -520,6 +530,7 @@ def sharded_frame_steps(mgr, rdr, gnm, gprof, tc, rank, world, device=None, copy
         raise ValueError('sharded rendering does not resample yet (supersample %r, filters %s): band halos are not defined '
                          'across a change of resolution; distribute whole frames instead (jobs.py)'
                          % (gprof.supersample, [f.name for f in rdr.filts]))
+    refuse_proxies(gprof, rdr)
     from . import _lib
     from .render import DurationEvent
     lib = _lib.load()

@@ -222,6 +222,56 @@ class Spatial(Filter):
         return fb.calc_dim(w, h)
 
 
+RESIZE_MAX_RATIO = 8                # the library serves FL_RESIZE_MAX_TAPS = 50 taps per output: 6 * 8 + 1
+RESIZE_MAX_TAPS = 50
+_resize_tables = {}
+
+
+def resize_tables(n_in, n_out):
+    """
+    One axis of the Lanczos-3 downscale from ``n_in`` to ``n_out`` samples as ``(first int32 [n_out], taps
+    float32 [n_out][nt])``: output i is the sum of the nt source samples from first[i] on, weighted by taps[i].  The taps are
+    Pillow's (Image.resize with LANCZOS): centre c = (i + 0.5) * n_in / n_out, support 3 * n_in / n_out, the window
+    max(0, int(c - support + 0.5)) .. min(n_in, int(c + support + 0.5)), weights normalised to sum 1 in float64 and then float32;
+    a window cut by the edge is renormalised.  nt is the axis's longest window; first[i] = min(lo_i, n_in - nt), so every row
+    stays inside the source.  The arrays are shared between calls: read-only.
+    """
+    n_in, n_out = int(n_in), int(n_out)
+    if n_out < 1 or not n_out <= n_in <= RESIZE_MAX_RATIO * n_out:
+        raise ValueError('resize: %d -> %d samples is a ratio of %s, outside 1..%d (enlarging is not supported; for more, chain two '
+                         'proxies)' % (n_in, n_out, '%.3g' % (n_in / float(n_out)) if n_out >= 1 else 'nothing', RESIZE_MAX_RATIO))
+    if (n_in, n_out) in _resize_tables:
+        return _resize_tables[n_in, n_out]
+    scale = n_in / float(n_out)
+    support = 3.0 * scale
+    c = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum((c - support + 0.5).astype(np.int64), 0)            # (astype truncates towards zero, as C's cast does)
+    hi = np.minimum((c + support + 0.5).astype(np.int64), n_in)
+    nt = int((hi - lo).max())
+    first = np.minimum(lo, n_in - nt)
+    x = first[:, None] + np.arange(nt)[None, :]
+    t = np.abs((x - c[:, None] + 0.5) / scale)
+    wt = np.where((t < 3.0) & (x >= lo[:, None]) & (x < hi[:, None]), np.sinc(t) * np.sinc(t / 3.0), 0.0)
+    taps = np.ascontiguousarray((wt / wt.sum(1, keepdims=True)).astype(np.float32))
+    first = np.ascontiguousarray(first.astype(np.int32))
+    assert nt <= RESIZE_MAX_TAPS and first.min() >= 0 and int(first.max()) + nt <= n_in
+    taps.setflags(write=False)
+    first.setflags(write=False)
+    if len(_resize_tables) >= 64:
+        _resize_tables.clear()
+    _resize_tables[n_in, n_out] = (first, taps)
+    return first, taps
+
+
+def resize(fb, dim, w2, h2):
+    """Bring the front buffer, laid out for ``dim``, down to ``w2`` x ``h2`` with the Lanczos-3 tables above (fl_resize): the
+    float frame as the filter chain left it, nothing clamped.  Returns the new Dimensions."""
+    (xf, xt), (yf, yt) = resize_tables(dim.w, w2), resize_tables(dim.h, h2)
+    _lib.check(_lib.load().fl_resize(fb.ctx, dim.w, dim.h, w2, h2, xf.ctypes.data, xt.ctypes.data, xt.shape[1],
+                                     yf.ctypes.data, yt.ctypes.data, yt.shape[1]))
+    return fb.calc_dim(w2, h2)
+
+
 def create(gprof):
     """The profile's chain.  `spatial` runs where the profile lists it (["de", "logscale", "spatial", "colorclip"] is flam3's
     late clip); a supersampled profile that does not list it gets it last (tone-map at full resolution, then filter: flam3's

@@ -123,6 +123,14 @@ profile = {
     'filter_order': list_(enum(list(filters.keys())), default_filters),
     'filters': prof_filters,
     'output': {'type': enum('jpeg png tiff x264 gif webp apng', 'jpeg')},
+    # Further, smaller deliverables of every frame (output.get_proxies_for_profile): the float frame is brought down to each size
+    # with a Lanczos-3 filter before the dither, and written by an output module of the entry's own.
+    'proxies': list_({
+        'width': Scalar(None, 'Width in pixels, at most the master\'s and at least an eighth of it'),
+        'height': Scalar(None, 'Height in pixels, likewise'),
+        'suffix': String('File name suffix in front of the extension (default: _<height>p)'),
+        'output': {'type': enum('jpeg png tiff x264 gif webp apng', 'jpeg')},
+    }, d='Smaller copies of every frame, each with an output block of its own (default: the master\'s)'),
 }
 
 toplevels = dict(animation=anim, node=node, edge=edge, profile=profile)

@@ -107,6 +107,10 @@ class View(object):
         """The underlying document (only what the file says: no defaults)."""
         return self._doc
 
+    def rebuilt(self, doc):
+        """A view of another document under this view's schema and leaf builders."""
+        return View(doc, self._schema, self._leaves)
+
     def child_schema(self, key):
         return self._schema.type if isinstance(self._schema, Map) else self._schema[key]
 

@@ -11,6 +11,7 @@ import zlib
 import numpy as np
 
 from . import _lib
+from .filters import RESIZE_MAX_RATIO       # the widest Lanczos tables the library serves: a proxy's largest step
 
 
 def _bool(key, v):
@@ -423,3 +424,91 @@ def get_output_for_profile(gprof):
 def get_suffix_for_profile(gprof):
     opts = dict(gprof.output.raw())
     return get_suffix(opts.get('type', 'jpeg'), bool(opts.get('alpha')))
+
+
+
+
+class Proxy(object):
+    """One entry of the profile's ``proxies``: a smaller copy of every frame.  ``gprof`` is the profile as this copy sees it (its
+    own width, height and output block), ``out`` its output module, ``suffix`` what its files carry in front of the extension."""
+
+    def __init__(self, width, height, suffix, gprof, out):
+        self.width, self.height, self.suffix, self.gprof, self.out = width, height, suffix, gprof, out
+
+
+def _subsamples_chroma(out):
+    """The output halves the chroma planes, so the frame's sides must be even."""
+    return (getattr(out, 'sampling', None) == '420' or getattr(out, 'fmt', None) == _lib.OUT['yuv420p10']
+            or getattr(out, 'csp', None) == 'i420' or (hasattr(out, 'csp') and bool(getattr(out, 'alpha', False)))      # (x264's alpha stream is i420)
+            or (getattr(out, 'pix_fmt', '') or '').startswith('yuv420'))
+
+
+def proxy_entries(gprof):
+    """The profile's ``proxies`` as ``[(width, height, suffix, output block)]``, from the largest to the smallest, every rule of
+    the key checked (sizes, ratio, suffixes) except what needs the output module."""
+    raw = gprof.raw().get('proxies') or []
+    if not isinstance(raw, (list, tuple)):
+        raise ValueError('proxies must be a list of {"width", "height", "suffix", "output"} entries')
+    W, H = int(gprof.width), int(gprof.height)
+    master = dict(gprof.output.raw())
+    entries, seen = [], {}
+    for k, ent in enumerate(raw):
+        who = 'proxies[%d]' % k
+        if not isinstance(ent, dict):
+            raise ValueError('%s must be an object with "width" and "height"' % who)
+        unknown = sorted(set(ent) - set(('width', 'height', 'suffix', 'output')))
+        if unknown:
+            raise ValueError('%s: unknown key %s' % (who, ', '.join(unknown)))
+        size = []
+        for key in ('width', 'height'):
+            v = ent.get(key)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError('%s.%s must be a positive integer' % (who, key))
+            size.append(v)
+        w, h = size
+        if w > W or h > H:
+            raise ValueError('%s: %d x %d is larger than the master\'s %d x %d (enlarging is not supported)' % (who, w, h, W, H))
+        suffix = ent.get('suffix', '_%dp' % h)
+        if not isinstance(suffix, str) or not suffix:
+            raise ValueError('%s.suffix must be a non-empty string: without one its files would replace the master\'s' % who)
+        if suffix in seen:
+            raise ValueError('%s and proxies[%d] have the same suffix "%s"' % (who, seen[suffix], suffix))
+        seen[suffix] = k
+        block = ent.get('output', master)
+        if not isinstance(block, dict):
+            raise ValueError('%s.output must be an output block' % who)
+        entries.append((w, h, suffix, dict(block), k))
+    entries.sort(key=lambda e: (-e[0] * e[1], e[4]))            # each is made from the one before it, the largest from the master
+    w0, h0, src = W, H, 'the master'
+    for w1, h1, _, _, k1 in entries:
+        if w1 > w0 or h1 > h0:
+            raise ValueError('proxies[%d] (%d x %d) is made from %s (%d x %d), the next larger frame, and is larger than it '
+                             'on an axis' % (k1, w1, h1, src, w0, h0))
+        if w0 > RESIZE_MAX_RATIO * w1 or h0 > RESIZE_MAX_RATIO * h1:
+            raise ValueError('proxies[%d]: %d x %d is less than 1/%d of %s (%d x %d), the frame it is made from, on an axis; '
+                             'list a size in between' % (k1, w1, h1, RESIZE_MAX_RATIO, src, w0, h0))
+        w0, h0, src = w1, h1, 'proxies[%d]' % k1
+    return entries
+
+
+def get_proxies_for_profile(gprof):
+    """``[Proxy]`` for the profile's ``proxies`` key, from the largest to the smallest, each with a fresh output module from
+    get_output_for_profile.  A profile without the key gives ``[]``."""
+    out = []
+    for w, h, suffix, block, k in proxy_entries(gprof):
+        doc = dict(gprof.raw(), width=w, height=h, output=block)
+        doc.pop('proxies', None)
+        view = gprof.rebuilt(doc)
+        try:
+            mod = get_output_for_profile(view)
+        except ValueError as e:
+            raise ValueError('proxies[%d].%s' % (k, e))
+        if _subsamples_chroma(mod) and (w % 2 or h % 2):
+            raise ValueError('proxies[%d]: %d x %d has an odd side, and its output subsamples the chroma 4:2:0' % (k, w, h))
+        out.append(Proxy(w, h, suffix, view, mod))
+    return out
+
+
+def get_proxy_files_for_profile(gprof):
+    """``[suffix + extension]`` of the files the profile's proxies add to every output, without building an output module."""
+    return [suffix + get_suffix(block.get('type', 'jpeg'), bool(block.get('alpha'))) for _, _, suffix, block, _ in proxy_entries(gprof)]

@@ -22,6 +22,18 @@ BUILTIN = {
 _OVERRIDES = 'duration fps frame_width start end skip shard spp width height supersample'.split()
 
 
+def parse_proxy(text):
+    """``WxH[:SUFFIX]`` of ``--proxy`` as an entry of the profile's ``proxies``."""
+    size, sep, suffix = text.partition(':')
+    try:
+        w, h = (int(v) for v in size.lower().split('x'))
+    except ValueError:
+        raise argparse.ArgumentTypeError('"%s" is not WxH[:SUFFIX], e.g. 960x540 or 960x540:_web' % text)
+    if w < 1 or h < 1 or (sep and not suffix):
+        raise argparse.ArgumentTypeError('"%s": the sizes must be positive and a suffix, if given, not empty' % text)
+    return dict(width=w, height=h, suffix=suffix) if sep else dict(width=w, height=h)
+
+
 def add_args(parser=None):
     """Add the profile option groups to ``parser`` (a new one if None)."""
     parser = argparse.ArgumentParser() if parser is None else parser
@@ -74,6 +86,10 @@ def add_args(parser=None):
                      help='gif animations (always encoded on the GPU): palette entries per frame, 2..256, default 256 (sets output.colors)')
     out.add_argument('--gif-dither', choices=['ordered', 'none'],
                      help='gif animations: an 8 x 8 ordered dither of one palette step, the default, or none (sets output.dither)')
+    out.add_argument('--proxy', action='append', type=parse_proxy, metavar='WxH[:SUFFIX]',
+                     help='Also write every frame at this smaller size (Lanczos-3 on the GPU, before the dither), with the same '
+                          'output block, as <name>SUFFIX<ext>; SUFFIX defaults to _<H>p.  May be given several times '
+                          '(adds to the profile\'s proxies)')
     out.add_argument('-n', metavar='NAME', type=str, dest='name', help='Prefix to use when saving files')
     out.add_argument('--suffix', metavar='NAME', type=str, dest='suffix', default='', help='Suffix for saved files')
     out.add_argument('-o', metavar='DIR', type=str, dest='dir', default='.', help='Output directory')
@@ -119,6 +135,8 @@ def get_from_args(args):
         prof['output'] = dict(prof.get('output') or {}, colors=ns['gif_colors'])
     if ns.get('gif_dither') is not None:
         prof['output'] = dict(prof.get('output') or {}, dither=ns['gif_dither'])
+    if ns.get('proxy'):
+        prof['proxies'] = list(prof.get('proxies') or []) + [dict(p) for p in ns['proxy']]
     return name, prof
 
 
@@ -155,7 +173,8 @@ def enumerate_jobs(gprof, basename, args, resume=None):
     (cuburn/profile.py:129-159).  Files are numbered ``<dir>/<name>_00001<suffix>`` — or
     ``<dir>/<name>/00001<suffix>`` with ``--subdir``, creating the directory — where ``-n`` replaces
     the genome's own name.  With ``resume`` (argument, or ``--resume`` when the argument is None)
-    outputs whose file already exists under the output module's extension are left out.
+    outputs whose file already exists under the output module's extension are left out; with ``proxies`` in the profile an
+    output counts as existing only when the master's file and every proxy's ``<path><suffix><ext>`` do.
     """
     from . import output
     stem = os.path.join(args.dir, basename if args.name is None else args.name)
@@ -164,6 +183,6 @@ def enumerate_jobs(gprof, basename, args, resume=None):
     pattern = stem + ('/' if args.subdir else '_') + '%05d' + args.suffix
     jobs = [(pattern % number, times) for number, times in enumerate_times(gprof)]
     if args.resume if resume is None else resume:
-        ext = output.get_suffix_for_profile(gprof)
-        jobs = [job for job in jobs if not os.path.isfile(job[0] + ext)]
+        exts = [output.get_suffix_for_profile(gprof)] + output.get_proxy_files_for_profile(gprof)
+        jobs = [job for job in jobs if not all(os.path.isfile(job[0] + ext) for ext in exts)]
     return jobs

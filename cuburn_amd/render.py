@@ -292,6 +292,7 @@ class Renderer(object):
         self._mod_key = None
         self.filts = filters.create(gprof)
         self.out = output.get_output_for_profile(gprof)
+        self.proxies = output.get_proxies_for_profile(gprof)      # the profile's `proxies`, largest first, each with its own module
 
     def _handle(self, fb):
         key = (id(fb), fb.generation)
@@ -394,6 +395,7 @@ class RenderManager(object):
         """
         Queue one frame at centre time ``tc``; returns ``(evt, h_out)`` (render.py:374-434).
         ``dev_out`` / ``host``: see Output.copy (frame straight into a device buffer of the caller).
+        ``evt.proxies``: the host frames of ``rdr.proxies``, in their order (empty without the profile's ``proxies``).
         """
         lib = _lib.load()
         # the accumulator, and every filter in front of `spatial`, have supersample times the output's size per axis; the sample
@@ -416,6 +418,13 @@ class RenderManager(object):
         _lib.check(lib.fl_iterate(self.fb.ctx, g, acc.w, acc.h, float(nsamps), self.fuse,
                                   self.resolve_accum_mode(acc), C.byref(run)))
         self.last_nsamples = run.value
+        return self.finish_frame(rdr, gprof, acc, tc, fid.value, dev_out=dev_out, host=host)
+
+    def finish_frame(self, rdr, gprof, acc, tc, frame_id, dev_out=0, host=True):
+        """What queue_frame does with the accumulator once the iterate is queued — the filter chain, the master's conversion and
+        copy, then the profile's proxies — on the front buffer as it stands, laid out for ``acc``; returns ``(evt, h_out)``.
+        On its own it finishes a frame whose accumulator the caller has written (``fb.write('front', ...)`` behind
+        ``fl_frame_begin``): nothing of it depends on the iterate."""
         dim = acc
         for filt in rdr.filts:
             params = getattr(gprof.filters, filt.name)
@@ -423,7 +432,15 @@ class RenderManager(object):
         assert dim == self.fb.calc_dim(gprof.width, gprof.height), 'the filter chain did not end at the output size'
         rdr.out.convert(self.fb, gprof, dim)
         h_out = rdr.out.copy(self.fb, dim, dev_out=dev_out, host=host)
-        return DurationEvent(self.fb, fid.value), h_out
+        # The profile's proxies, from the largest to the smallest: each is the float frame the one before it left, brought down
+        # once more, then converted by its own module (dither and quantisation happen once, at the final size).
+        evt = DurationEvent(self.fb, frame_id)
+        evt.proxies = []
+        for px in getattr(rdr, 'proxies', ()):
+            dim = filters.resize(self.fb, dim, px.width, px.height)
+            px.out.convert(self.fb, px.gprof, dim)
+            evt.proxies.append(px.out.copy(self.fb, dim))
+        return evt, h_out
 
     def timings_reset(self):
         _lib.check(_lib.load().fl_timings_reset(self.fb.ctx))

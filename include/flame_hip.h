@@ -259,6 +259,26 @@ int fl_filter(fl_ctx *ctx, int filter_id, uint32_t w, uint32_t h, const float *p
 #define FL_RESAMPLE_MAX_TAPS (FL_RESAMPLE_MAX_SS + 2 * FL_GUTTER)
 int fl_resample(fl_ctx *ctx, uint32_t w, uint32_t h, uint32_t ss, const float *taps, uint32_t ntaps);
 
+/* A downscale of the float frame to an arbitrary smaller size: front (laid out for w x h) -> front (laid out
+ * for w2 x h2), w2 <= w, h2 <= h.  The filter is separable and arrives as one table per axis; the caller decides its shape
+ * (filters.resize_tables: Lanczos-3 with Pillow's taps).  Output i of an axis with n_in source samples is the sum of nt source
+ * samples from first[i] on, 0 <= first[i] and first[i] + nt <= n_in, weighted by taps[i][0 .. nt-1].  x first, then y:
+ *     out[12 + Y][12 + X] = sum_j ytaps[Y][j] * (sum_i xtaps[X][i] * src[12 + yfirst[Y] + j][12 + xfirst[X] + i])
+ * for 0 <= X < w2, 0 <= Y < h2, all four channels alike, the inner sum rounded to float32.  Only the source's picture area is
+ * read, never its gutter or padding; every bin of the result's padded buffer outside its picture area is written as +0.
+ * Nothing is clamped.  xtaps is [w2][nxt], ytaps is [h2][nyt]; the arrays are the caller's again when the call returns: the
+ * lane keeps device copies of the tables of the last few (w, h, w2, h2) it has seen, found again by a hash of their contents.
+ * Deferred filter steps (a `yuv`, the DE's end) run first, at the source's size.  Recorded with the filters in fl_timings /
+ * fl_timings_detail[3].
+ * FL_E_INVAL, before anything is queued or timed: a null pointer or a zero size, w2 > w or h2 > h, nxt or nyt outside
+ * 1 .. FL_RESIZE_MAX_TAPS or above the source's size, a first below 0 or with first + nt past the source, a non-finite tap,
+ * x windows that are not a downscale's: those of 64 neighbouring output columns span more than 576 source bins (ratio 8, the
+ * largest FL_RESIZE_MAX_TAPS serves, spans 555). */
+#define FL_RESIZE_MAX_TAPS 50
+int fl_resize(fl_ctx *ctx, uint32_t w, uint32_t h, uint32_t w2, uint32_t h2,
+              const int32_t *xfirst, const float *xtaps, uint32_t nxt,
+              const int32_t *yfirst, const float *ytaps, uint32_t nyt);
+
 /* cuburn/output.py:83-88,120-125,150-158,212-219,323-338 (convert + copy of every Output class):
  * f32 -> pixel format with dither (cuburn/code/output.py:7-236), gutter cropped; async D2H into
  * host_out (or device copy when dev_out != 0).  fl_output_bytes gives the frame's size. */
